@@ -2,19 +2,40 @@
 """Headline benchmark: per-REML-evaluation factorize -> solve -> log-det of V = s2_g A + s2_e I on a simulated
 pedigree (BASELINE.json metric "REML factorize+solve wall-clock (s) and nnz(L)/s, 1M-individual pedigree").
 
-    python bench.py --gpus N --steps K --warmup W [--workload 1m|100k|300k|10k] [--budget-s S]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full] [--workload 1m|100k|300k|10k] [--budget-s S]
 
 A step = one pass of the hot path over one cohort: device assembly of V, numeric supernodal Cholesky,
 log-det, and ONE fused solve with r = c + 1 + s = 103 right-hand sides ([C | y | Z]), everything
 resident in HBM when the timed region starts.  value = nnz(L) processed by all ranks / wall time.
 
-The default workload is BASELINE configs[2] -- the 1M-individual pedigree the metric is quoted on (n = 828k after
-the unrelated-drop, nnz(L) = 1.5e10 = 123 GB, 1.6 PFLOP per factorization, ~40 s per step on one MI355X).  A driver
-that asks for --steps 20 --warmup 5 cannot get 25 such steps inside its time limit, so the step counts are BUDGETED
-by wall clock (--budget-s, default 450 s for the whole process): the first evaluation (which also builds the
-device plan) is the warm-up, then as many timed steps as fit are run (at least one); the line reports the counts
-actually run as `steps` / `warmup` and the requested ones as `steps_requested` / `warmup_requested`.  Small
-workloads (--workload 100k) fit the requested counts and run them unchanged.
+The BASELINE metric is quoted on configs[2], the 1M-individual pedigree (--workload 1m: n = 828k after the
+unrelated-drop, nnz(L) = 1.5e10 = 123 GB, 1.6 PFLOP per factorization, 27 s per step on one MI355X, 46 s of set-up
+before the first step: simulation and analysis of the cohort on the host).  A command that is run several times for every
+change, with the step counts it is given, cannot carry that: the DEFAULT workload is the 300k probe (n = 250k, nnz(L) =
+2.0e9, 7.6e13 flops per factorization, 1.4 s per step, 15 s of set-up) -- the largest cohort here whose run is dominated
+by the same dense-tail kernel as the 1M one and that sets up in seconds; `config.workload` and `config.baseline_config`
+of the line name the cohort a value was measured on, and nnz(L)/s of different cohorts are not comparable.  --full
+measures the 1M headline as well (`headline_1m`, below).
+
+--steps and --warmup are run as given: W untimed steps (the first evaluation, which also allocates the factor and the
+sweep buffers, is the first of them; with --warmup 0 it is the first timed step), then K timed ones; `ms_per_step` is the
+wall time of one timed step.  Only when --budget-s is given are the counts cut to fit that wall-clock budget of the whole process
+(at least one warm-up and one timed step); the line reports the counts actually run as `steps` / `warmup` and the
+requested ones as `steps_requested` / `warmup_requested`.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the result line.  --full adds
+what takes evaluations or runs of its own: the per-class and roofline figures (one untimed evaluation with the kernel
+classes bracketed by HIP events, one with the look-ahead launches serialised), the residual check of the last solve
+against the host matrices, the CPU baseline with its same-sample GPU figure, and `headline_1m`: the same plain
+measurement on the 1M cohort (one warm-up and one timed step in a child process: `value`, `ms_per_step`, log det V),
+unless the run itself is on that cohort.  Without --full the line's `roofline`, `cpu_baseline`, `headline_1m` and
+`config.solve_residual` are null.
+
+--dump-outputs DIR (say, bench_out) writes what the last timed step delivered to its caller as DIR/<name>.npy
+(float64): `logdet.npy` (log det V), `solve.npy` (rows of the n x 103 solution V^-1 [C | y | Z]: all of them when they
+fit 48 MB, else a fixed, seeded sample of 49152 rows) and `solve_rows.npy` (the row numbers of `solve.npy`).  The cohort,
+the right-hand sides and the variance components of every step are seeded, so the same arguments give the same inputs
+in every run.
 
 For N > 1 the N ranks factorize the SAME ONE cohort together (strong scaling, BASELINE configs[3]): the panels of the
 dense tail of the block elimination tree -- > 99.9 % of the flops and of the storage at 1M -- are owned 1-D
@@ -154,6 +175,22 @@ def cpu_baseline(A, r, sample_name):
                       % (sample_name, n, cinfo.nnzL, cinfo.flops, t_fact, r, t_solve, threads, len(os.sched_getaffinity(0))),
             "sample_workload": sample_name, "sample_nnzL": int(cinfo.nnzL), "sample_flops": cinfo.flops,
             "factor_s": t_fact, "solve_s": t_solve, "flops_per_s": cinfo.flops / t_fact, "logdet": cpu.logdet()}
+
+
+def headline_1m():
+    """--full on another cohort: the BASELINE headline (configs[2], the 1M pedigree) measured by a plain run of this file
+    in a fresh child process, one warm-up and one timed step.  Like the CPU baseline it is a reported figure, never a
+    reason to lose the line."""
+    import subprocess
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "1", "--warmup", "1", "--workload", "1m"]
+    try:
+        run = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=300)
+        d = json.loads(run.stdout.strip().splitlines()[-1])
+        return {"value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "steps": d["steps"], "warmup": d["warmup"],
+                "dtype": d["dtype"], "baseline_config": d["config"]["baseline_config"], "workload": d["config"]["workload"],
+                "nnzL": d["config"]["nnzL"], "logdet": d["config"]["logdet"], "process_wall_s": d["config"]["process_wall_s"]}
+    except Exception as e:
+        return {"value": None, "unit": "nnz(L)/s", "note": "failed: %r" % (e,)}
 
 
 def plan_only(args):
@@ -317,12 +354,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--workload", default=os.environ.get("SCILMM_BENCH_WORKLOAD", "1m"), choices=sorted(WORKLOADS))
-    ap.add_argument("--budget-s", type=float, default=float(os.environ.get("SCILMM_BENCH_BUDGET_S", "450")),
-                    help="wall-clock budget of the whole process; the step counts are cut to fit it (>= 1 timed step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--workload", default=os.environ.get("SCILMM_BENCH_WORKLOAD", "300k"), choices=sorted(WORKLOADS),
+                    help="default 300k; the BASELINE headline cohort is 1m (27 s per step, 46 s of set-up)")
+    ap.add_argument("--budget-s", type=float, default=float(os.environ.get("SCILMM_BENCH_BUDGET_S", "0")) or None,
+                    help="wall-clock budget of the whole process; when given, the step counts are cut to fit it (>= 1 warm-up, "
+                         ">= 1 timed step).  Default: no budget, --steps and --warmup are run as given")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes evaluations or runs of its own: per-class and roofline figures (two untimed "
+                         "evaluations), the residual check of the last solve, the CPU baseline with its same-sample GPU figure")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step (log det V, the solution block or a seeded row sample of it) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-clean-profile", action="store_true",
-                    help="skip the extra untimed evaluation that measures the dominant kernel's launches without overlap")
+                    help="--full without the extra untimed evaluation that measures the dominant kernel's launches without overlap")
     ap.add_argument("--components", default="A", choices=["A", "A,D"],
                     help="A,D: K = 3 (additive + dominance + identity), BASELINE configs[4]'s model -- NOT the headline metric")
     ap.add_argument("--front-bits", type=int, default=64, choices=[32, 64],
@@ -349,6 +394,8 @@ def main():
         raise SystemExit(plan_only(args))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher.  It starts the N ranks as
         # fresh children BEFORE anything here touches the GPU (it never does) and leaves with their worst exit code.
@@ -397,7 +444,7 @@ def main():
         return int(t[0])
 
     from scilmm_amd.factor import Symbolic
-    want_cpu = world == 1 and rank == 0 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
     t0 = time.time()
     # One cohort for the whole job.  Rank 0 simulates it and hands it to the other ranks through /dev/shm (N
     # simultaneous simulations of a 1M pedigree would need N x 40 GB of host memory and N x the cores).
@@ -477,14 +524,14 @@ def main():
     t_sym = time.time() - t0
     info = sym.info()
     # The timed steps run WITHOUT the engine's HIP-event brackets (14 timed events per level: 4 - 5 ms of a 52 ms factorization at
-    # the 100k config, tools/enqueue_time.py); the per-class figures of the line come from ONE extra, untimed evaluation with the
-    # brackets on, the clean per-launch figure from one more with the look-ahead launches serialised.  --serialised: every
-    # evaluation in mode 2 (a measurement mode); --no-engine-profiling: no bracketed evaluation at all.
-    prof_mode = 0 if args.no_engine_profiling else (2 if args.serialised else 1)
+    # the 100k config, tools/enqueue_time.py); with --full the per-class figures of the line come from ONE extra, untimed evaluation
+    # with the brackets on, the clean per-launch figure from one more with the look-ahead launches serialised.  --serialised: every
+    # evaluation in mode 2 (a measurement mode); a plain run and --no-engine-profiling: no bracketed evaluation at all.
+    prof_mode = 0 if args.no_engine_profiling else (2 if args.serialised else (1 if args.full else 0))
     timed_mode = 2 if args.serialised else 0
     if timed_mode:
         sym.set_profiling(timed_mode)
-    if args.no_engine_profiling or args.serialised:
+    if args.no_engine_profiling or args.serialised or not args.full:
         args.no_clean_profile = True
     if args.front_bits == 32:
         sym.set_front_precision(32)
@@ -558,26 +605,28 @@ def main():
     if args.dump_maps and rank == 0:
         with open("/proc/self/maps") as fi, open(args.dump_maps, "w") as fo:
             fo.write(fi.read())
-    t0 = time.time()
-    step(0)  # the plan-building evaluation always runs before the timed region: it is the first warm-up step
-    t_first = time.time() - t0
-    warm_done = 1
-    tm = sym.timing()  # HIP-event time of that evaluation's kernels = a good estimate of a steady-state step
-    t_step_est = (tm["assemble_ms"] + tm["factor_ms"] + tm["solve_fwd_ms"] + tm["solve_bwd_ms"]) / 1e3 * 1.05 + 0.01
-    reserve = CPU_BASELINE_RESERVE_S if want_cpu else 0.0
-    if world == 1 and not args.no_clean_profile:
-        reserve += 1.25 * t_step_est  # the serialised profiling evaluation after the timed region
-    if prof_mode == 1:
-        reserve += 1.1 * t_step_est   # the bracketed evaluation (per-class figures) after the timed region
-    remaining = args.budget_s - (time.time() - T_PROCESS_START) - reserve - 10.0
-    afford = int(remaining / max(t_step_est, 1e-9))
-    steps = max(1, min(args.steps, afford))
-    extra_warm = max(0, min(args.warmup - warm_done, afford - steps))
-    steps = agree_min(steps)
-    extra_warm = agree_min(extra_warm)
-    for i in range(extra_warm):
-        step(1 + i)
-    warm_done += extra_warm
+    steps, warm_done, t_first, t_step_est, reserve = args.steps, 0, None, None, 0.0
+    if args.warmup > 0 or args.budget_s is not None:
+        t0 = time.time()
+        step(0)  # the first evaluation (it allocates the factor and the sweep buffers) is the first warm-up step
+        t_first = time.time() - t0
+        warm_done = 1
+        extra_warm = args.warmup - warm_done
+        if args.budget_s is not None:
+            tm = sym.timing()  # HIP-event time of that evaluation's kernels = a good estimate of a steady-state step
+            t_step_est = (tm["assemble_ms"] + tm["factor_ms"] + tm["solve_fwd_ms"] + tm["solve_bwd_ms"]) / 1e3 * 1.05 + 0.01
+            reserve = CPU_BASELINE_RESERVE_S if want_cpu else 0.0
+            if world == 1 and not args.no_clean_profile:
+                reserve += 1.25 * t_step_est  # the serialised profiling evaluation after the timed region
+            if prof_mode == 1:
+                reserve += 1.1 * t_step_est   # the bracketed evaluation (per-class figures) after the timed region
+            remaining = args.budget_s - (time.time() - T_PROCESS_START) - reserve - 10.0
+            afford = int(remaining / max(t_step_est, 1e-9))
+            steps = agree_min(max(1, min(args.steps, afford)))
+            extra_warm = agree_min(max(0, min(extra_warm, afford - steps)))
+        for i in range(extra_warm):
+            step(1 + i)
+        warm_done += extra_warm
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -606,6 +655,16 @@ def main():
         hbm_used = float(hmax[0])
     nnzL_total = float(info.nnzL)  # ONE cohort, whatever the number of ranks
     logdet_total = logdets[-1]
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed to its caller: log det V and the r solution columns (every rank holds all of them);
+        # above 48 MB a fixed, seeded sample of the rows
+        rows = np.arange(n)
+        if 8 * n * r > 48 << 20:
+            rows = np.sort(np.random.default_rng(12345).choice(n, 49152, replace=False))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logdet.npy"), np.array([logdet_total], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "solve.npy"), dX[torch.from_numpy(rows).to(dev), :r].cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "solve_rows.npy"), rows.astype(np.float64))
     bracketed_factor_ms = None
     if prof_mode == 1:
         # ONE more, untimed evaluation under the default schedule with the kernel classes bracketed by HIP events: the per-class
@@ -629,13 +688,13 @@ def main():
         clean = sym.timing()
         sym.set_profiling(timed_mode)
         logdets.pop()
-    # residual check of the last solve (outside the timed region)
+    # --full: residual check of the last solve (outside the timed region)
     fac = state["fac"]
-    X = dX[:, :r].cpu().numpy()
     s2 = sigma2_of(steps - 1)
     probe = [0, c, r - 1]  # first covariate column, the phenotype, the last simulated vector (last rank's share)
-    resid = 0.0
-    if rank == 0:
+    resid = None
+    if rank == 0 and args.full:
+        X = dX[:, :r].cpu().numpy()
         VX = s2[0] * (A @ X[:, probe]) + s2[-1] * X[:, probe]
         for kq, Mq in enumerate(comps or []):
             VX += s2[1 + kq] * (Mq @ X[:, probe])
@@ -700,7 +759,7 @@ def main():
         solve_bytes = 16.0 * info.nnzL + 32.0 * n * r
         solve_flops = 4.0 * info.nnzL * r
         reasons = []
-        if steps < args.steps or warm_done != args.warmup:
+        if args.budget_s is not None and (steps < args.steps or warm_done != args.warmup):
             reasons.append("step counts budgeted by wall clock: %.1f s per step, %.0f s budget for the whole process "
                            "(generation %.0f s, analysis %.0f s, first evaluation incl. device plan %.0f s%s)"
                            % (t_step_est, args.budget_s, t_gen, t_sym, t_first,
@@ -793,8 +852,14 @@ def main():
                                        "kind": "port", "sample": "failed: %r" % (e,)}
         else:
             out["cpu_baseline"] = None
-        if args.no_engine_profiling:
+        if prof_mode == 0:
             out["roofline"] = None   # (no HIP-event brackets were taken: nothing to quote)
+        out["headline_1m"] = None
+        if args.full and world == 1 and args.workload != "1m":
+            state["fac"] = None
+            fac = sym = dB = dX = None   # (the child needs 157 GB of the HBM)
+            torch.cuda.empty_cache()
+            out["headline_1m"] = headline_1m()
         if args.serialised:
             out["config"]["mode"] = "--serialised: a measurement mode (look-ahead launches on one stream), slower than the default schedule"
         out["config"]["process_wall_s"] = time.time() - T_PROCESS_START

@@ -32,7 +32,7 @@ def main():
     res = {
         "kernels": upd, "workload": workload,
         "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py --workload %s --steps 1 "
-                  "--warmup 0 --no-cpu-baseline` (%d factorizations per pass)" % (workload, nfact),
+                  "--warmup 1` (a plain run; %d factorizations per pass)" % (workload, nfact),
         "fetch_kb_per_factorization_raw": fetch_kb, "write_kb_per_factorization_raw": write_kb,
         "correction": "FETCH_SIZE x2 (gfx950 counts 64 B per 128-B request; calibrated in round 1 on k_assemble), WRITE_SIZE as read; KB = 1000 B",
         "bytes_per_factorization": total, "launches_per_factorization": launches,
