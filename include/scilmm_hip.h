@@ -83,7 +83,11 @@ int scilmm_symbolic_info(const scilmm_symbolic* sym, scilmm_info* info);
  * Call with out == NULL to get the element count.  Names: perm, iperm, parent, colcount, sn_start, sn_parent,
  * sn_rowptr, sn_rows, sn_loff, sn_level, level_ptr, level_fronts, dense_first, tail_blk_ptr / tail_blk (block pattern
  * of the dense tail's true structure), asm_dst, diag_dst, pat_colptr, pat_row, val_slot:k / val_src:k (value-assembly
- * maps of input matrix k), upd_*, tile_*, combo_* (built on demand), level_tile_*, level_pair_*, inv_off, child_*. */
+ * maps of input matrix k), upd_*, tile_*, combo_* (built on demand), level_tile_*, level_pair_*, inv_off, child_*;
+ * deterministic mode (built on demand): pat_rowptr / pat_rowslot / pat_rowcol (int64, int64, int32: the strict lower triangle
+ * of the pattern by ROW -- per entry its pattern slot and its column, columns ascending) and the pull schedule of the forward
+ * sweep pull_seg_front / pull_seg_ptr (int64) / pull_seg_slot / pull_front_seg / pull_level_ptr (int64) / pull_level_segs /
+ * pull_fold_ptr (int64) / pull_fold (csrc/symbolic.h describes them). */
 int scilmm_symbolic_get(const scilmm_symbolic* sym, const char* what, void* out, int64_t* count);
 const char* scilmm_symbolic_error(const scilmm_symbolic* sym);
 void scilmm_symbolic_free(scilmm_symbolic* sym);
@@ -205,6 +209,28 @@ int scilmm_inverse_traces(scilmm_factor* fac, double* out);
  * scilmm_amd.factor.Factor does.  bits = 64 (default) restores the all-fp64 path.  No counterpart in the reference. */
 int scilmm_set_front_precision(scilmm_symbolic* sym, int32_t bits);
 
+/* Deterministic mode: every floating-point sum of an evaluation on this handle is taken in an order that depends on the
+ * analysis only, so the same inputs give the same BITS -- in one process, in two processes, under a profiler.  on != 0 selects
+ *   - the factorization's fixed-order schedule (the prelude's contributions to the dense tail stay on the target-coordinate
+ *     path instead of k_outside's fp64 atomics),
+ *   - the forward sweep and L*R (scilmm_solve / scilmm_lmul) in PULL form: the owner of a front's rows sums the contributions
+ *     of its update pairs in list order (k_fwd_pull; long lists in fixed segments folded in slot order) instead of k_fwd's
+ *     atomic pushes,
+ *   - Y = A_k X (scilmm_spmm / _dev, and with it the refinement of solves on fp32 fronts) with row ownership through a
+ *     transposed index of the pattern (k_spmm_row; 12 bytes per strictly lower pattern entry of device memory, allocated
+ *     only in this mode: scilmm_symbolic_get "pat_rowptr" / "pat_rowslot" / "pat_rowcol" give the counts).
+ * The backward sweep, the chain sweeps, quadratic forms, the log-determinant and the Haseman-Elston moments are order-fixed in
+ * either mode.  NOT covered: the selected inverse (scilmm_selected_inverse keeps working and keeps its atomics), and
+ * distributed handles -- the summation order of an all-reduce belongs to the communication library, so on a handle with
+ * scilmm_dist_init(world > 1) the mode is refused with SCILMM_ERR_STATE (in either call order: scilmm_dist_init refuses a
+ * deterministic handle as well).  Results in this mode differ from the default mode's in the last bits; the default
+ * schedule is unchanged.  The initial value of a handle is SCILMM_DETERMINISTIC=1 in the environment at creation.  Must be
+ * called before the first numeric call on the handle (the device plan depends on it); afterwards SCILMM_ERR_STATE.
+ * scilmm_timing.n_float_atomic_launches lets a caller check the claim.  No counterpart in the reference (CHOLMOD on one
+ * host thread is deterministic as it is). */
+int scilmm_set_deterministic(scilmm_symbolic* sym, int32_t on);
+int scilmm_get_deterministic(const scilmm_symbolic* sym, int32_t* on);
+
 /* Haseman-Elston moments on the device (reference HE, SparseCholesky.py:192-246, REML's starting
  * point at :121): *frob = sum_ij (A_k1 o A_k2)_ij over the full symmetric matrices, *diag_dot = diag(A_k1) . diag(A_k2),
  * from the value arrays already resident in HBM (one streaming pass).  y'A_k y comes from scilmm_quadforms. */
@@ -258,6 +284,9 @@ typedef struct scilmm_timing {
    * already arrived first, the newest source panel's items after the wait for its broadcast (look-ahead on the chain's
    * critical path); 0 on one GPU */
   int64_t n_late_split;
+  /* kernel launches on this handle SINCE IT WAS CREATED whose results are summed with floating-point atomics (k_outside,
+   * the atomic forms of k_fwd, k_spmm_w, k_sinv_w / k_sinv_tail): 0 in deterministic mode unless the selected inverse ran */
+  int64_t n_float_atomic_launches;
 } scilmm_timing;
 int scilmm_last_timing(const scilmm_symbolic* sym, scilmm_timing* out);
 /* Bracket every kernel class of the factorization with HIP events on the handle's stream (bench.py's

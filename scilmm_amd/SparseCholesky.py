@@ -56,7 +56,7 @@ class SparseCholesky(object):
     """
 
     def __init__(self, use_long=False, mode='supernodal', ordering_method='default', perm=None, fused=True,
-                 exact_trace=False, cache_dir=None, metrics=None, front_bits=64):
+                 exact_trace=False, cache_dir=None, metrics=None, front_bits=64, deterministic=None):
         _lib.lib()  # fail loudly when the HIP library is not built
         self._use_long = use_long
         self._mode = mode
@@ -80,6 +80,12 @@ class SparseCholesky(object):
         if front_bits not in (32, 64):
             raise ValueError("front_bits must be 32 or 64")
         self.front_bits = front_bits
+        # deterministic=True: every engine this object creates sums in a fixed order (factorization, sweeps, L*R, SpMM:
+        # scilmm_set_deterministic) -- an evaluation then repeats bit for bit, between processes as well; None follows
+        # SCILMM_DETERMINISTIC.  Not covered: exact_trace (the selected inverse keeps its atomics).
+        if deterministic is None:
+            deterministic = os.environ.get("SCILMM_DETERMINISTIC", "")[:1] == "1"
+        self.deterministic = bool(deterministic)
         self._n_eval = 0
         self._cache = {}
 
@@ -120,10 +126,11 @@ class SparseCholesky(object):
         # (a matrix with unsorted indices is copied before sorting: the caller's arrays are never touched)
         mats = [m if (sparse.isspmatrix_csr(m) and m.has_sorted_indices) else sparse.csr_matrix(m).sorted_indices()
                 for m in mats]
-        key = _pattern_key(mats)
+        key = (_pattern_key(mats), self.deterministic)  # (a deterministic and a default engine never share a handle)
         hit = self._cache.get(key)
         if hit is None:
-            sym = Symbolic(mats, perm=self._perm, ordering=self._ordering(), cache=self.cache_dir)
+            sym = Symbolic(mats, perm=self._perm, ordering=self._ordering(), cache=self.cache_dir,
+                           deterministic=self.deterministic)
             if self.front_bits == 32:
                 try:
                     sym.set_front_precision(32)
@@ -428,7 +435,8 @@ def _write_metrics(cholesky_func, mats, sig2g_array, nll, grad, seconds, reml, s
            "factor_flops": info.flops, "reml": bool(reml), "sim_num": int(sim_num), "sigma2": np.asarray(sig2g_array).tolist(),
            "nll": float(nll), "grad_sigma2": np.asarray(grad).tolist(), "seconds": seconds,
            "device_ms": {k: v for k, v in sym.timing().items() if k.endswith("_ms")},
-           "launches": int(sym.timing()["n_launches"]), "symbolic_from_cache": bool(getattr(sym, "from_cache", False))}
+           "launches": int(sym.timing()["n_launches"]), "symbolic_from_cache": bool(getattr(sym, "from_cache", False)),
+           "deterministic": bool(sym.deterministic), "float_atomic_launches": int(sym.timing()["n_float_atomic_launches"])}
     with open(cholesky_func.metrics, "a") as fh:
         fh.write(json.dumps(rec) + "\n")
 
@@ -837,7 +845,7 @@ def HE(mat_list, cov, y, MQS=False, verbose=False, sim_num=100, compute_stderr=F
     return he_est, np.sqrt(np.diag(var_he_est))
 
 
-def run_estimates(A, df_phe, df_cov, reml=False, ignore_indices=False, df_phe2=None):
+def run_estimates(A, df_phe, df_cov, reml=False, ignore_indices=False, df_phe2=None, deterministic=None):
     """Align inputs, drop unrelated individuals, standardise covariates, fit (SparseCholesky.py:350-395)."""
     A = sparse.csr_matrix(A)
     if not ignore_indices:
@@ -868,7 +876,7 @@ def run_estimates(A, df_phe, df_cov, reml=False, ignore_indices=False, df_phe2=N
     cov[:, :-1] -= cov[:, :-1].mean(axis=0)
     cov[:, :-1] /= cov[:, :-1].std(axis=0)
     if reml:
-        reml_d = REML(SparseCholesky(), [A], cov, y, verbose=True)
+        reml_d = REML(SparseCholesky(deterministic=deterministic), [A], cov, y, verbose=True)
         print("reml d are %s and %s" % (reml_d["covariance coefficients"], reml_d["covariates coefficients"]))
         return reml_d
     he_est = HE([A], cov, y, compute_stderr=True, y2=y2)
@@ -889,7 +897,7 @@ def read_relationship_matrix(path):
     return _lib.read_matrix_market(path)
 
 
-def run_estimates_from_paths(A, phe, cov, reml=False, ignore_indices=False):
+def run_estimates_from_paths(A, phe, cov, reml=False, ignore_indices=False, deterministic=None):
     """File front end (SparseCholesky.py:398-403): MatrixMarket A, header-less phenotype CSV, covariate CSV.
 
     The MatrixMarket file goes through the native streaming parser (``csrc/mmio.cpp``: memory-mapped, all host
@@ -899,7 +907,7 @@ def run_estimates_from_paths(A, phe, cov, reml=False, ignore_indices=False):
     index_col = None if ignore_indices else 0
     df_cov = pd.read_csv(cov, index_col=index_col)
     df_phe = pd.read_csv(phe, header=None, index_col=index_col)
-    return run_estimates(A, df_phe, df_cov, reml=reml, ignore_indices=ignore_indices)
+    return run_estimates(A, df_phe, df_cov, reml=reml, ignore_indices=ignore_indices, deterministic=deterministic)
 
 
 def _main(argv=None):
@@ -914,6 +922,9 @@ def _main(argv=None):
                         help="Compute using REML, default case uses the HE estimation method.")
     parser.add_argument('--ignore_indices', default=False, action='store_true',
                         help="Assume A, phenotypes and covariates are already in the same order.")
+    parser.add_argument('--deterministic', default=None, action='store_true',
+                        help="Sum in a fixed order on the device: the fit repeats bit for bit (one GPU; default follows "
+                             "SCILMM_DETERMINISTIC).")
     args = parser.parse_args(argv)
     return run_estimates_from_paths(**(args.__dict__))
 

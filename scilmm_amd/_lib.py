@@ -54,7 +54,7 @@ class Timing(C.Structure):
                 ("n_launches", C.c_int64), ("update_ms", C.c_double), ("potrf_ms", C.c_double),
                 ("trsm_ms", C.c_double), ("n_update_launches", C.c_int64), ("reduce_cells_ms", C.c_double),
                 ("update_union_ms", C.c_double), ("dense_ms", C.c_double), ("n_dense_launches", C.c_int64),
-                ("n_late_split", C.c_int64)]
+                ("n_late_split", C.c_int64), ("n_float_atomic_launches", C.c_int64)]
 
 
 # every symbol include/scilmm_hip.h declares (tests check that the library exports all of them)
@@ -72,6 +72,7 @@ SYMBOLS = [
     "scilmm_mm_read", "scilmm_mm_export", "scilmm_mm_error", "scilmm_mm_free",
     "scilmm_dominance", "scilmm_dominance_dev", "scilmm_dominance_error",
     "scilmm_csr_spmm_dev", "scilmm_csr_spmm_error",
+    "scilmm_set_deterministic", "scilmm_get_deterministic",
 ]
 
 _lib = None
@@ -142,6 +143,8 @@ def lib():
     L.scilmm_mm_free.argtypes = [vp]
     L.scilmm_mm_free.restype = None
     L.scilmm_set_front_precision.argtypes = [vp, i32]
+    L.scilmm_set_deterministic.argtypes = [vp, i32]
+    L.scilmm_get_deterministic.argtypes = [vp, P(i32)]
     L.scilmm_selected_inverse.argtypes = [vp]
     L.scilmm_inverse_traces.argtypes = [vp, vp]
     L.scilmm_he_moments.argtypes = [vp, i32, i32, P(dbl), P(dbl)]
@@ -182,7 +185,9 @@ def ptr(a):
 
 _GET_DTYPES = {"sn_rowptr": np.int64, "sn_loff": np.int64, "asm_dst": np.int64, "diag_dst": np.int64,
                "upd_ptr": np.int64, "tile_base": np.int64, "combo_ptr": np.int64, "level_tile_ptr": np.int64,
-               "level_pair_ptr": np.int64, "child_ptr": np.int64, "tail_blk_ptr": np.int64, "pat_colptr": np.int64, "inv_off": np.int64}
+               "level_pair_ptr": np.int64, "child_ptr": np.int64, "tail_blk_ptr": np.int64, "pat_colptr": np.int64, "inv_off": np.int64,
+               "pat_rowptr": np.int64, "pat_rowslot": np.int64, "pull_seg_ptr": np.int64, "pull_level_ptr": np.int64,
+               "pull_fold_ptr": np.int64}
 
 
 def symbolic_get(sym, name):

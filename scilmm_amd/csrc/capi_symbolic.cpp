@@ -10,6 +10,11 @@
 
 using scilmm::Symbolic;
 
+static bool env_deterministic() {
+  const char* e = getenv("SCILMM_DETERMINISTIC");
+  return e && e[0] == '1';
+}
+
 extern "C" {
 
 int scilmm_symbolic_create(int32_t n, int32_t K, const int64_t* const* indptr, const int32_t* const* indices,
@@ -36,6 +41,7 @@ int scilmm_symbolic_create(int32_t n, int32_t K, const int64_t* const* indptr, c
   if (perm_in && !opts) o.ordering = 2;
   scilmm_symbolic* h = new scilmm_symbolic();
   h->S = scilmm::symbolic_analyze(n, K, indptr, indices, perm_in, o);
+  h->deterministic = env_deterministic();
   *out = h;
   if (!h->S->error.empty()) {
     h->err = h->S->error;
@@ -56,7 +62,29 @@ int scilmm_symbolic_load(const char* path, uint64_t key, scilmm_symbolic** out) 
   if (!S) return SCILMM_ERR_STATE;  // no file, another key / build, or a damaged image: the caller analyses afresh
   scilmm_symbolic* h = new scilmm_symbolic();
   h->S = S;
+  h->deterministic = env_deterministic();
   *out = h;
+  return SCILMM_OK;
+}
+
+int scilmm_set_deterministic(scilmm_symbolic* h, int32_t on) {
+  if (!h || !h->S) return SCILMM_ERR_ARG;
+  if (h->device) {
+    h->err = "scilmm_set_deterministic must precede the first numeric call on this handle (the device plan depends on it)";
+    return SCILMM_ERR_STATE;
+  }
+  if (on && h->world > 1) {
+    h->err = "deterministic mode is not available on a distributed handle: the summation order of an all-reduce belongs to "
+             "the communication library";
+    return SCILMM_ERR_STATE;
+  }
+  h->deterministic = on != 0;
+  return SCILMM_OK;
+}
+
+int scilmm_get_deterministic(const scilmm_symbolic* h, int32_t* on) {
+  if (!h || !h->S || !on) return SCILMM_ERR_ARG;
+  *on = h->deterministic ? 1 : 0;
   return SCILMM_OK;
 }
 
@@ -104,6 +132,9 @@ int scilmm_symbolic_get(const scilmm_symbolic* h, const char* what, void* out, i
   scilmm::use_host_threads();
   if (!h || !h->S || !what || !count) return SCILMM_ERR_ARG;
   if (!h->S->combos_built && !std::strncmp(what, "combo_", 6)) scilmm::build_tile_combos(h->S, nullptr);
+  if (!std::strncmp(what, "pull_", 5)) scilmm::build_pull_schedule(h->S);
+  if (!std::strcmp(what, "pat_rowptr") || !std::strcmp(what, "pat_rowslot") || !std::strcmp(what, "pat_rowcol"))
+    if (!scilmm::build_row_index(h->S)) return SCILMM_ERR_STATE;  // (the host maps were released before the index was built)
   const Symbolic& S = *h->S;
   if (!std::strcmp(what, "dense_first")) {
     if (out) *(int32_t*)out = S.dense_first;
@@ -153,6 +184,18 @@ int scilmm_symbolic_get(const scilmm_symbolic* h, const char* what, void* out, i
   GET("pat_colptr", pat_colptr)
   GET("pat_row", pat_row)
   GET("inv_off", inv_off)
+  GET("pat_rowptr", pat_rowptr)
+  GET("pat_rowslot", pat_rowslot)
+  GET("pat_rowcol", pat_rowcol)
+  GET("pull_seg_front", pull_seg_front)
+  GET("pull_seg_ptr", pull_seg_ptr)
+  GET("pull_seg_slot", pull_seg_slot)
+  GET("pull_front_seg", pull_front_seg)
+  GET("pull_level_ptr", pull_level_ptr)
+  GET("pull_level_segs", pull_level_segs)
+  GET("pull_fold_ptr", pull_fold_ptr)
+  GET("pull_fold", pull_fold)
+  GET("pull_group_ptr", pull_group_ptr)
   GET("tail_blk_ptr", tail_blk_ptr)
   GET("tail_blk", tail_blk)
   GET("child_ptr", child_ptr)

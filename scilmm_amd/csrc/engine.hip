@@ -179,6 +179,17 @@ struct Dev {
   int32_t* h_chain_err = nullptr;    // pinned mirror of [0], refreshed by a queued copy after every solve
   int32_t chain_epoch = 0;
   std::vector<hipEvent_t> pev;     // 4 events per level when profiling
+  // deterministic mode (scilmm_set_deterministic): pull schedule of the forward sweep / L*R, transposed pattern index
+  bool det = false;
+  PullPlan pull{};
+  int32_t* d_pull_level_segs = nullptr;
+  int32_t* d_pull_fold = nullptr;
+  double* d_pull_partial = nullptr;     // [pull_max_slots][NB][RPMAX]
+  uint8_t* d_chain_mask = nullptr;      // [nsuper] front is swept by k_chain
+  const int64_t* d_pat_rowptr = nullptr;
+  const int64_t* d_pat_rowslot = nullptr;
+  const int32_t* d_pat_rowcol = nullptr;
+  int64_t n_float_atomic = 0;           // launches since the handle was created that sum with floating-point atomics
 };
 
 // Schedule / tuning switches (SCILMM_LOOK_DEPTH, SCILMM_CELL_LIMIT, ...) are honoured only when SCILMM_TUNING=1 is set
@@ -578,6 +589,7 @@ int ensure_device(scilmm_symbolic* sym, Dev** out) {
       sym->err = "symbolic analysis has supernode blocks wider than the kernels' block width (max_width > NB)";
       return SCILMM_ERR_ARG;
     }
+  D->det = sym->deterministic;
   const char* nm = tune_env("SCILMM_NO_MFMA");
   D->use_mfma = !(nm && nm[0] == '1');
   const char* etl = tune_env("SCILMM_TRSM_LITE");
@@ -669,14 +681,14 @@ int ensure_device(scilmm_symbolic* sym, Dev** out) {
   }
   {
     // k_outside takes over the update pairs (tail target, prelude descendant below the tail's first level) unless the
-    // caller asks for the bitwise-reproducible schedule (SCILMM_DETERMINISTIC=1) or the combos were already built
-    const char* edet = getenv("SCILMM_DETERMINISTIC");
+    // caller asks for the bitwise-reproducible schedule (scilmm_set_deterministic / SCILMM_DETERMINISTIC=1) or the combos
+    // were already built
     const char* eout = tune_env("SCILMM_OUTSIDE");
     int st = SCILMM_OK;
     D->outside_desc.assign((size_t)std::max(S.nsuper, 1), 0);
     // (switched on with the dense-tail path, by the width of the tail -- SCILMM_OUTSIDE=1 / 0 forces it)
     const int32_t tail_w2 = S.dense_first < S.nsuper ? S.n - S.sn_start[S.dense_first] : 0;
-    D->outside_on = S.dense_first < S.nsuper && !(edet && edet[0] == '1') && !sym->S->combos_built &&
+    D->outside_on = S.dense_first < S.nsuper && !D->det && !sym->S->combos_built &&
                     (eout ? eout[0] != '0' : tail_w2 >= 8192);
     if (D->outside_on) {
       D->tail_level = S.sn_level[S.dense_first];
@@ -909,6 +921,38 @@ int ensure_device(scilmm_symbolic* sym, Dev** out) {
   UP(pat_row, pat_row)
   UP(perm, perm)
 #undef UP
+  if (D->det) {
+    // ---- deterministic mode: pull schedule of the forward sweep and of L*R, row index of the pattern (k_spmm_row)
+    scilmm::build_pull_schedule(sym->S);
+    if (!scilmm::build_row_index(sym->S)) {
+      sym->err = "deterministic mode: the pattern maps of this handle are not available (released before the first numeric call)";
+      return SCILMM_ERR_STATE;
+    }
+    const int32_t* t32;
+    if ((st = upload(sym, D, S.pull_seg_front, &D->pull.seg_front)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, S.pull_seg_ptr, &D->pull.seg_ptr)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, S.pull_seg_slot, &D->pull.seg_slot)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, S.pull_front_seg, &D->pull.front_seg)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, S.pull_level_segs, &t32)) != SCILMM_OK) return st;
+    D->d_pull_level_segs = (int32_t*)t32;
+    if ((st = upload(sym, D, S.pull_fold, &t32)) != SCILMM_OK) return st;
+    D->d_pull_fold = (int32_t*)t32;
+    if (S.pull_max_slots > 0) {
+      void* pp = nullptr;
+      HIPCHK(hipMalloc(&pp, sizeof(double) * (size_t)S.pull_max_slots * NB * RPMAX));
+      D->allocs.push_back(pp);
+      D->d_pull_partial = (double*)pp;
+    }
+    if ((st = upload(sym, D, S.pat_rowptr, &D->d_pat_rowptr)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, S.pat_rowslot, &D->d_pat_rowslot)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, S.pat_rowcol, &D->d_pat_rowcol)) != SCILMM_OK) return st;
+    // (the device holds the index now: the host copy goes, like the maps scilmm_symbolic_release_host_maps frees)
+    std::vector<int64_t>().swap(sym->S->pat_rowslot);
+    std::vector<int32_t>().swap(sym->S->pat_rowcol);
+    std::vector<int64_t>().swap(sym->S->pat_rowptr);
+    sym->S->rowidx_built = false;
+    plap("deterministic mode: pull schedule, row index");
+  }
   const int32_t* tmp;
   if ((st = upload(sym, D, D->lv_tiles, &tmp)) != SCILMM_OK) return st;
   D->d_level_tiles = (int32_t*)tmp;
@@ -1687,6 +1731,13 @@ int ensure_device(scilmm_symbolic* sym, Dev** out) {
     if (D->world > 1) T = 0;  // a distributed factor is swept level by level with a collective per tail block (run_rhs)
     D->chain_T = T;
     D->chain_l0 = l0;
+    if (T > 0 && D->det) {
+      std::vector<uint8_t> mask((size_t)ns, 0);
+      for (int32_t i = 0; i < T; ++i) mask[(size_t)S.level_fronts[S.level_ptr[l0] + i]] = 1;
+      const uint8_t* t8;
+      if ((st = upload(sym, D, mask, &t8)) != SCILMM_OK) return st;
+      D->d_chain_mask = (uint8_t*)t8;
+    }
     if (T > 0) {
       std::vector<int32_t> chain(T), pos(ns, -1);
       for (int32_t i = 0; i < T; ++i) {
@@ -2263,6 +2314,7 @@ int run_factorize(scilmm_factor* fac, const double* sigma2, int32_t* bad_col, bo
                              (const int32_t*)D->d_grp_t0, fac->L);
         HIPCHK(hipGetLastError());
         launches++;
+        D->n_float_atomic++;
       }
       HIPCHK(hipEventRecord(D->out_evs[og], D->outside_st));
       }
@@ -2512,6 +2564,35 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
       return SCILMM_OK;
     };
     const size_t sm_fwd = sizeof(double) * (size_t)(NB * LDW + KCS * LDA);
+    // deterministic mode: the targets of level l pull their update pairs (k_fwd_pull), long pair lists are folded in slot order
+    // (levels [la, lb): one launch -- the caller keeps them inside one slot group when they are more than one)
+    auto launch_pull = [&](int32_t la, int32_t lb, bool lmul, const uint8_t* skip) {
+      const int64_t g0 = S.pull_level_ptr[(size_t)la], g1 = S.pull_level_ptr[(size_t)lb];
+      const int64_t h0 = S.pull_fold_ptr[(size_t)la], h1 = S.pull_fold_ptr[(size_t)lb];
+      const double* in = lmul ? (const double*)D->W : (const double*)D->X;
+      double* out = lmul ? D->X : D->W;
+      const int64_t mg = (int64_t)(((uint64_t)1 << 32) / 256) - 1;  // launches stay below 2^32 work-items
+      for (int64_t a = g0; a < g1; a += mg) {
+        const unsigned cnt = (unsigned)std::min<int64_t>(mg, g1 - a);
+        const int32_t* segs = D->d_pull_level_segs + a;
+        if (mf && lmul) hipLaunchKernelGGL((k_fwd_pull<true, 1>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
+        else if (mf) hipLaunchKernelGGL((k_fwd_pull<true, 0>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
+        else if (lmul) hipLaunchKernelGGL((k_fwd_pull<false, 1>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
+        else hipLaunchKernelGGL((k_fwd_pull<false, 0>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
+      }
+      if (h1 > h0) {
+        const int32_t* fold = D->d_pull_fold + 3 * h0;
+        if (lmul) hipLaunchKernelGGL(k_pull_fold<1>, dim3((unsigned)(h1 - h0), gy), dim3(256), 0, st, D->v, fold, (const double*)D->d_pull_partial, out, rp);
+        else hipLaunchKernelGGL(k_pull_fold<0>, dim3((unsigned)(h1 - h0), gy), dim3(256), 0, st, D->v, fold, (const double*)D->d_pull_partial, out, rp);
+      }
+    };
+    // levels from `lo` on, a launch per slot group: for targets that do not depend on each other
+    auto launch_pull_groups = [&](int32_t lo, bool lmul, const uint8_t* skip) {
+      for (size_t q = 0; q + 1 < S.pull_group_ptr.size(); ++q) {
+        const int32_t la = std::max(lo, S.pull_group_ptr[q]), lb = S.pull_group_ptr[q + 1];
+        if (la < lb) launch_pull(la, lb, lmul, skip);
+      }
+    };
     const int64_t tot = (int64_t)S.n * rp;
     const unsigned pb = (unsigned)((tot + 255) / 256);
     if (D->world > 1) {
@@ -2542,6 +2623,7 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
         hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, (const int32_t*)nullptr, dB, D->W);
         HIPCHK(hipMemsetAsync(D->X, 0, sizeof(double) * (size_t)tot, st));
         if (D->n_lmul_tiles > 0) {
+          D->n_float_atomic++;
           if (mf)
             hipLaunchKernelGGL((k_fwd<true, 1, true>), dim3((unsigned)D->n_lmul_tiles, gy), dim3(256), sm_fwd, st, D->v, D->d_lmul_tiles,
                                fac->L, (const double*)D->W, D->X, rp);
@@ -2574,6 +2656,7 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
                              fac->invD, (const double*)D->W, D->X, rp);
         // pushes of the prelude fronts of the level go to W (atomic: they may share rows), of an own tail panel to ACC
         if (tm > t0) {
+          D->n_float_atomic++;
           if (mf)
             hipLaunchKernelGGL((k_fwd<true, 0, true>), dim3((unsigned)(tm - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
                                fac->L, (const double*)D->X, D->W, rp);
@@ -2629,6 +2712,8 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
         const int64_t t0 = S.level_tile_ptr[l], t1 = S.level_tile_ptr[l + 1];
         const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];
         if (f1 == f0) continue;
+        // deterministic mode: every front of the level first collects the contributions of its (final) descendants
+        if (D->det && l > 0) launch_pull(l, l + 1, false, nullptr);
         // x_s = invL_s * W[c0:c1] -> X rows c0..c1 (final), then push to the rows below
         if (mf)
           hipLaunchKernelGGL((k_diag_solve<true, false>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v,
@@ -2636,8 +2721,9 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
         else
           hipLaunchKernelGGL((k_diag_solve<false, false>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v,
                              D->d_level_fronts + f0, fac->invD, (const double*)D->W, D->X, rp);
-        if (t1 == t0) continue;
+        if (t1 == t0 || D->det) continue;
         const bool atomic = (f1 - f0) > 1;
+        if (atomic) D->n_float_atomic++;
         if (mf && atomic)
           hipLaunchKernelGGL((k_fwd<true, 0, true>), dim3((unsigned)(t1 - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
                              fac->L, (const double*)D->X, D->W, rp);
@@ -2652,6 +2738,8 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
                              fac->L, (const double*)D->X, D->W, rp);
       }
       if (D->chain_T > 0) {
+        // (deterministic mode: what the fronts below the chain contribute to the chain blocks arrives through the pull form too)
+        if (D->det) launch_pull_groups(lend, false, (const uint8_t*)D->d_chain_mask);
         if (int e = launch_chain(false)) return e;
       }
       if (!mid_recorded) {
@@ -2700,7 +2788,11 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
       // Z = P^T (L R): R is NOT permuted on the way in (SparseCholesky.py:50-51)
       hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, (const int32_t*)nullptr, dB, D->W);
       HIPCHK(hipMemsetAsync(D->X, 0, sizeof(double) * (size_t)tot, st));
-      if (ntiles_all > 0) {
+      if (D->det) {
+        // every front owns its rows of Z: no dependencies between fronts (the level groups only bound the partial slots)
+        launch_pull_groups(0, true, nullptr);
+      } else if (ntiles_all > 0) {
+        D->n_float_atomic++;
         if (mf)
           hipLaunchKernelGGL((k_fwd<true, 1, true>), dim3((unsigned)ntiles_all, gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles, fac->L,
                              (const double*)D->W, D->X, rp);
@@ -2946,6 +3038,11 @@ int scilmm_dist_init(scilmm_symbolic* sym, int32_t rank, int32_t world, void* co
     return SCILMM_ERR_STATE;
   }
   if (world > 1 && (!fn || !comm_stream)) return SCILMM_ERR_ARG;
+  if (world > 1 && sym->deterministic) {
+    sym->err = "scilmm_dist_init: deterministic mode is not available on a distributed handle (the summation order of an "
+               "all-reduce belongs to the communication library); call scilmm_set_deterministic(sym, 0) first";
+    return SCILMM_ERR_STATE;
+  }
   sym->rank = rank;
   sym->world = world;
   sym->comm_stream = comm_stream;
@@ -3132,9 +3229,15 @@ int scilmm_spmm(scilmm_symbolic* sym, int32_t k, const double* X, int32_t r, dou
     if (S.is_diag[k])
       hipLaunchKernelGGL(k_spmm_diag, dim3(pb), dim3(256), 0, s, S.n, (const double*)D->vals[k], (const double*)D->W, rp, D->X);
     else
+    if (D->det)
+      // (deterministic mode: a workgroup per row of the product, fixed summation order, plain stores)
+      hipLaunchKernelGGL(k_spmm_row, dim3((unsigned)S.n), dim3(256), 0, s, D->v, D->d_pat_rowptr, D->d_pat_rowcol, D->d_pat_rowslot,
+                         (const double*)D->vals[k], (const double*)D->W, rp, D->X);
+    else
     {
       // (a wave per 256 pattern slots; lanes = right-hand-side columns)
       const int64_t spw = 256, nwav = (S.nnz_pattern + spw - 1) / spw;
+      D->n_float_atomic++;
       hipLaunchKernelGGL(k_spmm_w, dim3((unsigned)((nwav + 3) / 4)), dim3(256), 0, s, D->v, S.nnz_pattern, spw,
                          (const double*)D->vals[k], (const double*)D->W, rp, D->X);
     }
@@ -3168,9 +3271,15 @@ int scilmm_spmm_dev(scilmm_symbolic* sym, int32_t k, const double* dX, int32_t r
     if (S.is_diag[k])
       hipLaunchKernelGGL(k_spmm_diag, dim3(pb), dim3(256), 0, s, S.n, (const double*)D->vals[k], (const double*)D->W, rp, D->X);
     else
+    if (D->det)
+      // (deterministic mode: a workgroup per row of the product, fixed summation order, plain stores)
+      hipLaunchKernelGGL(k_spmm_row, dim3((unsigned)S.n), dim3(256), 0, s, D->v, D->d_pat_rowptr, D->d_pat_rowcol, D->d_pat_rowslot,
+                         (const double*)D->vals[k], (const double*)D->W, rp, D->X);
+    else
     {
       // (a wave per 256 pattern slots; lanes = right-hand-side columns)
       const int64_t spw = 256, nwav = (S.nnz_pattern + spw - 1) / spw;
+      D->n_float_atomic++;
       hipLaunchKernelGGL(k_spmm_w, dim3((unsigned)((nwav + 3) / 4)), dim3(256), 0, s, D->v, S.nnz_pattern, spw,
                          (const double*)D->vals[k], (const double*)D->W, rp, D->X);
     }
@@ -3498,12 +3607,14 @@ int scilmm_selected_inverse(scilmm_factor* fac) {
       if (i1 > i0) {
         const int32_t wtf = S.sn_start[tf + 1] - S.sn_start[tf];
         hipLaunchKernelGGL(k_sinv_zero, dim3(1, (unsigned)wtf), dim3(256), 0, st, D->v, (const int32_t*)(D->d_sinv_tail_fronts + jj), fac->L);
+        D->n_float_atomic++;
         hipLaunchKernelGGL(k_sinv_tail, dim3((unsigned)(i1 - i0)), dim3(512), sizeof(double) * (size_t)(2 * KBA * LDB), st, D->v,
                            S.dense_first, (const SinvWork*)(D->d_sinv_work + i0), fac->L, (const double*)D->d_ybuf,
                            (const int64_t*)D->d_yoff, (const int32_t*)D->d_col_front, (const double*)D->d_zeros);
       }
     }
     if (nwt > 0) {
+      D->n_float_atomic++;
       if (D->use_mfma)
         hipLaunchKernelGGL(k_sinv_w<true>, dim3(nwt), dim3(256), 0, st, D->v, wt, fac->L, (const double*)D->d_ybuf,
                            (const int64_t*)D->d_yoff, (const int32_t*)D->d_col_front, S.dense_first);
@@ -3587,6 +3698,7 @@ int scilmm_last_timing(const scilmm_symbolic* sym, scilmm_timing* out) {
     D->quad_pending = false;
   }
   D->timing.n_late_split = D->n_late_split;
+  D->timing.n_float_atomic_launches = D->n_float_atomic;
   *out = D->timing;
   return SCILMM_OK;
 }

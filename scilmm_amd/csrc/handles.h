@@ -16,4 +16,7 @@ struct scilmm_symbolic {
   int (*comm_fn)(void* ctx, int32_t op, int32_t buffer, int64_t offset, int64_t count, int32_t root) = nullptr;
   void* comm_ctx = nullptr;
   bool maps_released = false;          // scilmm_symbolic_release_host_maps: no further value uploads
+  // scilmm_set_deterministic (initial value: SCILMM_DETERMINISTIC=1 in the environment when the handle is created): the
+  // device plan picks the order-fixed kernels for the factorization, the sweeps, L*R and the products with A_k
+  bool deterministic = false;
 };

@@ -2065,6 +2065,155 @@ __global__ __launch_bounds__(256) void k_push_fold(DevSym S, const int32_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------
+// Deterministic mode: the PULL form of k_fwd (forward sweep of one level, and L * R).  Where k_fwd pushes the product of a
+// panel tile into the rows of W that several fronts of a level share (fp64 atomics, sums in arrival order), here the OWNER of
+// the destination rows collects them: workgroup = (segment of the update pairs of target front s, column window),
+//   MODE 0:  W[cols of s] -= sum_e L_d[p0:p1, :] x_d          (e = (d, p0, p1) over the segment's pairs, in list order)
+//   MODE 1:  Z[cols of s]  = L_ss R_s + sum_e L_d[p0:p1, :] R_d  (the diagonal block first; Xin = R, W = Z)
+// with the sums in registers and one plain store.  It is k_bwd_push transposed: same pairs, same panel bytes.  Row q of the
+// pair lands on target column rows_d[q] - c0: a column -> row map in LDS (jmap) inverts that, and the L
+// fragment of fp64 MFMA 16x16x4 is read straight from the panel, row jmap[j] at k -- zero where the pair has no such row.
+// A front with one segment stores its rows itself; the segments of a long pair list leave partial sums in their slots
+// and k_pull_fold adds them in slot order.  Nothing depends on timing: the result is bitwise reproducible.
+// skip_src (MODE 0, optional): descendants whose contributions arrive another way (the chain fronts, swept by k_chain).
+struct PullPlan {
+  const int32_t* seg_front;
+  const int64_t* seg_ptr;
+  const int32_t* seg_slot;
+  const int32_t* front_seg;
+};
+
+template <bool MFMA, int MODE>
+__global__ __launch_bounds__(256) void k_fwd_pull(DevSym S, PullPlan P, const int32_t* __restrict__ segs,
+                                                  const uint8_t* __restrict__ skip_src, const double* __restrict__ L,
+                                                  const double* __restrict__ Xin, double* W, double* __restrict__ partial,
+                                                  int32_t rp) {
+  __shared__ __attribute__((aligned(16))) double Ys[NB * LDW];  // x_d (or R_d), [k][c]
+  __shared__ int32_t jmap[NB];                                   // target column -> row of the descendant, or -1
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int c_lo = blockIdx.y * CW;
+  const int rpl = min(CW, rp - c_lo);
+  if (rpl <= 0) return;
+  const int32_t g = segs[blockIdx.x];
+  const int32_t s = P.seg_front[g];
+  const int64_t e0 = P.seg_ptr[g], e1 = P.seg_ptr[g + 1];
+  const int32_t slot = P.seg_slot[g];
+  const bool diag = MODE == 1 && P.front_seg[s] == g;
+  if (MODE == 0 && e0 == e1) return;  // (a front without update pairs: its rows of W are final as they are)
+  const int32_t c0 = S.sn_start[s], w = S.sn_start[s + 1] - c0;
+  const int ncn = rpl >> 4;
+  const int li = lane & 15, lk = lane >> 4;
+  constexpr int NH = (NJB + 3) / 4;  // 16-column blocks of the target per wave
+  d4 acc[NH][NCT];
+#pragma unroll
+  for (int h = 0; h < NH; ++h)
+#pragma unroll
+    for (int cn = 0; cn < NCT; ++cn) acc[h][cn] = (d4){0.0, 0.0, 0.0, 0.0};
+  bool staged = false;
+  for (int64_t e = diag ? e0 - 1 : e0; e < e1; ++e) {
+    const bool own = e < e0;  // MODE 1: the diagonal block of s itself
+    const int32_t d = own ? s : S.upd_src[e];
+    if (MODE == 0 && skip_src && skip_src[d]) continue;
+    const int32_t p0 = own ? 0 : S.upd_p0[e], p1 = own ? w : S.upd_p1[e];
+    const int32_t* rd = S.sn_rows + S.sn_rowptr[d];
+    const int32_t md = (int32_t)(S.sn_rowptr[d + 1] - S.sn_rowptr[d]);
+    const int32_t cd = S.sn_start[d], wd = S.sn_start[d + 1] - cd;
+    const int wd4 = (wd + 3) & ~3;
+    const double* Pd = L + S.sn_loff[d];
+    if (staged) __syncthreads();
+    staged = true;
+    {
+      // rows p0..p1-1 of d are ascending and all inside the columns of s.  Consecutive columns (every pair of a dense chain,
+      // more than half of the others): arithmetic; else the rows scatter their own numbers into the cleared map
+      const int32_t first = (own ? c0 : rd[p0]) - c0, last = (own ? c0 + w - 1 : rd[p1 - 1]) - c0;
+      if (last - first == p1 - 1 - p0) {
+        if (tid < NB) jmap[tid] = (tid >= first && tid <= last) ? p0 + (tid - first) : -1;
+      } else {
+        if (tid < NB) jmap[tid] = -1;
+        __syncthreads();
+        if (tid < p1 - p0) jmap[rd[p0 + tid] - c0] = p0 + tid;
+      }
+    }
+    {
+      const int c = tid & 63;
+      if (c < LDW)
+        for (int k = tid >> 6; k < wd4; k += 4)
+          Ys[k * LDW + c] = (k < wd && c < rpl) ? Xin[(int64_t)(cd + k) * rp + c_lo + c] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int jb = wv + 4 * h;
+      if (16 * jb >= w) continue;
+      if (MFMA) {
+        const int32_t q = jmap[16 * jb + li];
+        if (__ballot(q >= 0) == 0ull) continue;  // none of the 16 columns has a row in this pair
+        const double* col = Pd + (q >= 0 ? q : 0);
+        for (int k4 = 0; k4 < wd4; k4 += 4) {
+          const int k = k4 + lk;
+          const double a = (q >= 0 && k < wd) ? col[(int64_t)k * md] : 0.0;
+#pragma unroll
+          for (int cn = 0; cn < NCT; ++cn)
+            if (cn < ncn) acc[h][cn] = mfma_f64(a, Ys[k * LDW + 16 * cn + li], acc[h][cn]);
+        }
+      } else {
+        int32_t qr[4];
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          qr[r] = jmap[16 * jb + lk + 4 * r];
+          any = any || qr[r] >= 0;
+        }
+        if (__ballot(any) == 0ull) continue;
+        for (int k = 0; k < wd; ++k)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double a = qr[r] >= 0 ? Pd[(int64_t)k * md + qr[r]] : 0.0;
+#pragma unroll
+            for (int cn = 0; cn < NCT; ++cn)
+              if (cn < ncn) acc[h][cn][r] += a * Ys[k * LDW + 16 * cn + li];
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    const int jb = wv + 4 * h;
+#pragma unroll
+    for (int cn = 0; cn < NCT; ++cn)
+      if (cn < ncn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int jr = 16 * jb + lk + 4 * r;
+          if (jr < w) {
+            const int cc = c_lo + 16 * cn + li;
+            if (slot >= 0) partial[((int64_t)slot * NB + jr) * rp + cc] = acc[h][cn][r];
+            else if (MODE == 0) W[(int64_t)(c0 + jr) * rp + cc] -= acc[h][cn][r];
+            else W[(int64_t)(c0 + jr) * rp + cc] = acc[h][cn][r];
+          }
+        }
+  }
+}
+
+// the partial sums the segments of a long pair list left, added in slot order:  MODE 0: W[cols of s] -= sum;  MODE 1: Z = sum
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pull_fold(DevSym S, const int32_t* __restrict__ fold, const double* __restrict__ partial,
+                                                   double* __restrict__ W, int32_t rp) {
+  const int32_t s = fold[3 * blockIdx.x], slot0 = fold[3 * blockIdx.x + 1], ns = fold[3 * blockIdx.x + 2];
+  const int c_lo = blockIdx.y * CW;
+  const int rpl = min(CW, rp - c_lo);
+  const int32_t c0 = S.sn_start[s], w = S.sn_start[s + 1] - c0;
+  const int cc = threadIdx.x % CW;
+  if (cc >= rpl) return;
+  for (int k = threadIdx.x / CW; k < w; k += 256 / CW) {
+    double sum = 0.0;
+    for (int sl = 0; sl < ns; ++sl) sum += partial[((int64_t)(slot0 + sl) * NB + k) * rp + c_lo + cc];
+    if (MODE == 0) W[(int64_t)(c0 + k) * rp + c_lo + cc] -= sum;
+    else W[(int64_t)(c0 + k) * rp + c_lo + cc] = sum;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Dense-chain sweeps.  The last levels of the elimination tree are a chain of single fronts (the blocks of
 // the trailing dense clique): level-by-level kernels spend ~170 us per block there, almost all of it latency.
 // These two kernels run the whole chain in ONE launch each: workgroup (chain block i, RHS window c) PULLS the
@@ -2530,6 +2679,46 @@ __global__ __launch_bounds__(256) void k_spmm_w(DevSym S, int64_t nnz, int64_t s
     }
   }
   flush();
+}
+
+// Deterministic mode: Y = A X with ROW ownership.  One workgroup (four waves) owns row i of the symmetric product; lanes own the
+// right-hand-side columns (c, c + 64) as in k_spmm_w.  The terms of the row are taken in one fixed list order -- first the
+// entries (i, j < i) in ascending j through the transposed index (rowptr / rowcol / rowslot), then the stored column i from
+// the diagonal down -- cut into four equal parts, one per wave; the four partial sums meet in LDS and wave 0 adds them in
+// wave order and stores the row once.  The cut depends on the length of the list only: bitwise reproducible, no atomics.
+__global__ __launch_bounds__(256) void k_spmm_row(DevSym S, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ rowcol,
+                                                  const int64_t* __restrict__ rowslot, const double* __restrict__ vals,
+                                                  const double* __restrict__ X, int32_t rp, double* __restrict__ Y) {
+  __shared__ double part[4][RPMAX];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int32_t i = blockIdx.x;
+  const int64_t r0 = rowptr[i], nr = rowptr[i + 1] - r0;
+  const int64_t k0 = S.pat_colptr[i], nc = S.pat_colptr[i + 1] - k0;
+  const int64_t len = nr + nc, per = (len + 3) / 4;
+  const int64_t t0 = min(len, per * wv), t1 = min(len, t0 + per);
+  const bool h0 = lane < rp, h1 = lane + 64 < rp;
+  double a0 = 0.0, a1 = 0.0;
+  for (int64_t t = t0; t < t1; ++t) {
+    int32_t j;
+    double a;
+    if (t < nr) {
+      j = rowcol[r0 + t];
+      a = vals[rowslot[r0 + t]];
+    } else {
+      j = S.pat_row[k0 + (t - nr)];
+      a = vals[k0 + (t - nr)];
+    }
+    if (a == 0.0) continue;
+    if (h0) a0 += a * X[(int64_t)j * rp + lane];
+    if (h1) a1 += a * X[(int64_t)j * rp + lane + 64];
+  }
+  part[wv][lane] = a0;
+  part[wv][lane + 64] = a1;
+  __syncthreads();
+  if (wv == 0) {
+    if (h0) Y[(int64_t)i * rp + lane] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+    if (h1) Y[(int64_t)i * rp + lane + 64] = ((part[0][lane + 64] + part[1][lane + 64]) + part[2][lane + 64]) + part[3][lane + 64];
+  }
 }
 
 __global__ void k_spmm_diag(int32_t n, const double* __restrict__ dvals, const double* __restrict__ X, int32_t rp,

@@ -1345,6 +1345,95 @@ void image_fields(ImageIO& io, Symbolic& S) {
 }
 }  // namespace
 
+void build_pull_schedule(Symbolic* Sp) {
+  Symbolic& S = *Sp;
+  if (S.pull_built) return;
+  const int32_t ns = S.nsuper;
+  S.pull_seg_front.clear();
+  S.pull_seg_ptr.clear();
+  S.pull_front_seg.assign((size_t)ns + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) {
+    S.pull_front_seg[(size_t)s] = (int32_t)S.pull_seg_front.size();
+    int64_t e = S.upd_ptr[(size_t)s];
+    const int64_t e1 = S.upd_ptr[(size_t)s + 1];
+    do {
+      S.pull_seg_front.push_back(s);
+      S.pull_seg_ptr.push_back(e);
+      e = std::min<int64_t>(e1, e + Symbolic::kPullSegPairs);
+    } while (e < e1);
+  }
+  S.pull_front_seg[(size_t)ns] = (int32_t)S.pull_seg_front.size();
+  S.pull_seg_ptr.push_back(ns > 0 ? S.upd_ptr[(size_t)ns] : 0);
+  S.pull_seg_slot.assign(S.pull_seg_front.size(), -1);
+  S.pull_level_ptr.assign(1, 0);
+  S.pull_fold_ptr.assign(1, 0);
+  S.pull_level_segs.clear();
+  S.pull_fold.clear();
+  S.pull_max_slots = 0;
+  S.pull_group_ptr.assign(1, 0);
+  int32_t slots = 0;  // slots taken in the current group of levels
+  for (int32_t l = 0; l < S.nlevels; ++l) {
+    int32_t need = 0;
+    for (int32_t q = S.level_ptr[(size_t)l]; q < S.level_ptr[(size_t)l + 1]; ++q) {
+      const int32_t s = S.level_fronts[(size_t)q];
+      const int32_t ng = S.pull_front_seg[(size_t)s + 1] - S.pull_front_seg[(size_t)s];
+      if (ng > 1) need += ng;
+    }
+    if (slots > 0 && slots + need > Symbolic::kPullSlotBudget) {
+      S.pull_group_ptr.push_back(l);
+      slots = 0;
+    }
+    for (int32_t q = S.level_ptr[(size_t)l]; q < S.level_ptr[(size_t)l + 1]; ++q) {
+      const int32_t s = S.level_fronts[(size_t)q];
+      const int32_t g0 = S.pull_front_seg[(size_t)s], g1 = S.pull_front_seg[(size_t)s + 1];
+      for (int32_t g = g0; g < g1; ++g) {
+        S.pull_level_segs.push_back(g);
+        if (g1 - g0 > 1) S.pull_seg_slot[(size_t)g] = slots + (g - g0);
+      }
+      if (g1 - g0 > 1) {
+        S.pull_fold.push_back(s);
+        S.pull_fold.push_back(slots);
+        S.pull_fold.push_back(g1 - g0);
+        slots += g1 - g0;
+      }
+    }
+    S.pull_max_slots = std::max(S.pull_max_slots, slots);
+    S.pull_level_ptr.push_back((int64_t)S.pull_level_segs.size());
+    S.pull_fold_ptr.push_back((int64_t)S.pull_fold.size() / 3);
+  }
+  S.pull_group_ptr.push_back(S.nlevels);
+  S.pull_built = true;
+}
+
+bool build_row_index(Symbolic* Sp) {
+  Symbolic& S = *Sp;
+  if (S.rowidx_built) return true;
+  if ((int64_t)S.pat_row.size() != S.nnz_pattern || (int64_t)S.pat_colptr.size() != (int64_t)S.n + 1) return false;
+  const int32_t n = S.n;
+  S.pat_rowptr.assign((size_t)n + 1, 0);
+  // counting sort by row; the columns are visited in ascending order, so every row's entries come out ascending in j
+  for (int32_t j = 0; j < n; ++j)
+    for (int64_t e = S.pat_colptr[(size_t)j]; e < S.pat_colptr[(size_t)j + 1]; ++e) {
+      const int32_t i = S.pat_row[(size_t)e];
+      if (i != j) S.pat_rowptr[(size_t)i + 1]++;
+    }
+  for (int32_t i = 0; i < n; ++i) S.pat_rowptr[(size_t)i + 1] += S.pat_rowptr[(size_t)i];
+  const int64_t cnt = S.pat_rowptr[(size_t)n];
+  S.pat_rowslot.assign((size_t)cnt, 0);
+  S.pat_rowcol.assign((size_t)cnt, 0);
+  std::vector<int64_t> fill(S.pat_rowptr.begin(), S.pat_rowptr.end() - 1);
+  for (int32_t j = 0; j < n; ++j)
+    for (int64_t e = S.pat_colptr[(size_t)j]; e < S.pat_colptr[(size_t)j + 1]; ++e) {
+      const int32_t i = S.pat_row[(size_t)e];
+      if (i == j) continue;
+      const int64_t t = fill[(size_t)i]++;
+      S.pat_rowslot[(size_t)t] = e;
+      S.pat_rowcol[(size_t)t] = j;
+    }
+  S.rowidx_built = true;
+  return true;
+}
+
 bool symbolic_save(const Symbolic& S, const char* path, uint64_t key) {
   // a name of this writer's own (pid + clock + address entropy): ranks that miss the cache at the same time each write a
   // complete image and the LAST rename wins -- none truncates a file another one is still writing

@@ -122,6 +122,36 @@ struct Symbolic {
   double update_flops = 0; // flops of all supernodal updates as EXECUTED (lower-triangular count; includes the padding of the dense tail)
   double dense_flops = 0;       // algorithmic update flops among the dense-tail fronts (true structure)
   double update_flops_pad = 0;  // part of update_flops that is padding of the dense tail (executed - algorithmic)
+  // ---- deterministic mode (built on demand: build_pull_schedule / build_row_index; not part of the saved image)
+  // PULL schedule of the atomic-free forward sweep and L*R: the owner of a target front sums the contributions of its
+  // update pairs in list order.  Every front has at least one segment; segment g belongs to front pull_seg_front[g] and
+  // takes the pairs [pull_seg_ptr[g], pull_seg_ptr[g+1]) of upd_*; the segments of front s are
+  // [pull_front_seg[s], pull_front_seg[s+1]), consecutive and in list order.  A front with more than one segment leaves
+  // partial sums in the slots pull_seg_slot[g] (consecutive per front) that are folded in slot order (pull_fold: triples
+  // front, first slot, segments); pull_seg_slot = -1: the segment writes its rows itself.  Slots are numbered from 0 inside
+  // every GROUP of consecutive levels [pull_group_ptr[q], pull_group_ptr[q+1]) -- as many levels as fit kPullSlotBudget
+  // slots -- so that the levels of a group can share one launch where no dependencies separate them (L*R; the prelude's
+  // contributions to the chain blocks) and the slot buffer stays bounded.
+  // Boundaries depend on the pair lists only (at most kPullSegPairs pairs per segment).
+  static constexpr int32_t kPullSegPairs = 32;
+  static constexpr int32_t kPullSlotBudget = 1024;
+  bool pull_built = false;
+  std::vector<int32_t> pull_seg_front;   // [nseg]
+  std::vector<int64_t> pull_seg_ptr;     // [nseg+1]
+  std::vector<int32_t> pull_seg_slot;    // [nseg]
+  std::vector<int32_t> pull_front_seg;   // [nsuper+1]
+  std::vector<int64_t> pull_level_ptr;   // [nlevels+1] into pull_level_segs
+  std::vector<int32_t> pull_level_segs;  // segments grouped by the level of their front (level_fronts order)
+  std::vector<int64_t> pull_fold_ptr;    // [nlevels+1] into the triples of pull_fold
+  std::vector<int32_t> pull_fold;        // triples (front, first slot, segments), by level
+  std::vector<int32_t> pull_group_ptr;   // [ngroups+1] level ranges that number their slots jointly
+  int32_t pull_max_slots = 0;            // most slots any group needs
+  // TRANSPOSED index of the strict lower triangle of the pattern (row ownership of Y = A_k X): row i has the entries
+  // [pat_rowptr[i], pat_rowptr[i+1]), each with its column pat_rowcol (ascending) and its pattern slot pat_rowslot
+  bool rowidx_built = false;
+  std::vector<int64_t> pat_rowptr;   // [n+1]
+  std::vector<int64_t> pat_rowslot;  // [nnz_pattern - n]
+  std::vector<int32_t> pat_rowcol;   // [nnz_pattern - n]
   std::string error;
 };
 
@@ -136,6 +166,11 @@ Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, c
 // with implicit, descriptor-free work items).
 // skip_desc (optional, [nsuper]): descendants whose contributions to dense-tail targets are computed elsewhere (k_outside).
 void build_tile_combos(Symbolic* S, const uint8_t* keep_front, bool skip_dense = false, const uint8_t* skip_desc = nullptr);
+
+// Deterministic mode: the pull schedule of the sweeps (needs upd_* and the level lists) and the transposed pattern index
+// (needs pat_colptr / pat_row: false once the host maps were released and it had not been built).
+void build_pull_schedule(Symbolic* S);
+bool build_row_index(Symbolic* S);
 
 // Binary image of an analysis (everything but the lazily built tile combos); `key` = the caller's hash of the inputs the
 // analysis depends on (patterns, permutation, options): symbolic_load returns NULL unless it matches.

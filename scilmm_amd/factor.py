@@ -47,7 +47,9 @@ def _as_csr(m):
 class Symbolic(object):
     """Symbolic analysis of the pattern of V = sum_k s2_k mats[k]; built once, reused for every sigma2."""
 
-    def __init__(self, mats, perm=None, ordering="amd", upload=True, **opts):
+    def __init__(self, mats, perm=None, ordering="amd", upload=True, deterministic=None, **opts):
+        """deterministic: True / False selects or clears the bitwise-reproducible mode of the handle (factorization, solves,
+        L*R, SpMM in a fixed summation order: ``scilmm_set_deterministic``); None follows SCILMM_DETERMINISTIC."""
         mats = [_as_csr(m) for m in mats]
         self.n = n = mats[0].shape[0]
         for m in mats:
@@ -87,6 +89,8 @@ class Symbolic(object):
         self._h = h
         self._uploaded = False
         self.front_bits = 64
+        if deterministic is not None:
+            check(lib().scilmm_set_deterministic(h, 1 if deterministic else 0), h)
         if upload:
             self.upload_values()
 
@@ -223,6 +227,13 @@ class Symbolic(object):
         With 32 the factor has a ~1e-7 relative backward error; ``Factor.__call__`` then refines its solves."""
         check(lib().scilmm_set_front_precision(self._h, int(bits)), self._h)
         self.front_bits = int(bits)
+
+    @property
+    def deterministic(self):
+        """True when every sum of an evaluation on this handle runs in a fixed order (``scilmm_set_deterministic``)."""
+        on = C.c_int32(0)
+        check(lib().scilmm_get_deterministic(self._h, C.byref(on)), self._h)
+        return bool(on.value)
 
     def set_profiling(self, on=True):
         """True / 1: HIP-event brackets per kernel class; 2: also queue the look-ahead launches on one stream (clean
