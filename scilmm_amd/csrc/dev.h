@@ -1,0 +1,335 @@
+// Device state of a symbolic handle (struct Dev), the schedule switches (struct Tuning) and the small helpers shared by
+// the two device translation units: plan.hip builds the state once per handle, engine.hip runs the launch sequences on it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <optional>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/scilmm_hip.h"
+#include "plan_types.h"
+#include "handles.h"
+
+namespace scilmm {
+
+// Schedule / tuning switches.  They are honoured only when SCILMM_TUNING=1 is set as well, so that a stray variable in a
+// production environment cannot change the schedule.  Every value of every such switch gives the same factor to
+// rounding (parity-tested); switches that would change RESULTS (the timing ablations) exist only in builds with
+// -DSCILMM_DIAG.  A std::optional member is a switch whose default is decided from the matrix: unset -> decide.
+// (INTEGRATION.md section 3 has the table; keep the two in step.)
+struct Tuning {
+  // -- read when the device plan of a handle is built (Dev::tune)
+  int reserve_cus = 0;                 // SCILMM_RESERVE_CUS     CUs the look-ahead side streams leave free (CU mask); 0: none
+  int side_streams = 2;                // SCILMM_SIDE_STREAMS    1 / 2 / 3 side streams for the early updates
+  bool no_mfma = false;                // SCILMM_NO_MFMA=1       scalar kernels
+  bool trsm_lite = true;               // SCILMM_TRSM_LITE=0     k_trsm<true> instead of k_trsm_lite
+  std::optional<bool> dense;           // SCILMM_DENSE=1/0       dense-tail path (k_dense_b); unset: tails of 8192+ columns
+  std::optional<bool> outside;         // SCILMM_OUTSIDE=1/0     k_outside; unset: tails of 8192+ columns
+  bool outside_merge = true;           // SCILMM_OUTSIDE_MERGE=0 no groups of descendants with identical tail rows
+  std::optional<int> outside_chunks;   // SCILMM_OUTSIDE_CHUNKS  launches of k_outside; unset: one per ~16k block pairs, 4 .. 32
+  bool outside_prio = false;           // SCILMM_OUTSIDE_PRIO=1  k_outside on a stream of the chain's priority
+  std::optional<double> cell_limit;    // SCILMM_CELL_LIMIT      pairs with cells*width up to this take the cell-wise path;
+                                       //                        unset: 4096, lowered until the plan has < 1.5e9 cells
+  bool no_lookahead = false;           // SCILMM_NO_LOOKAHEAD=1  every update on the main stream
+  int look_depth = 2;                  // SCILMM_LOOK_DEPTH      "late" = descendants at most this many levels below (>= 1)
+  bool host_cells = false;             // SCILMM_HOST_CELLS=1    cell lists enumerated on the host
+  bool no_splitk = false;              // SCILMM_NO_SPLITK=1     one work item per tile and launch
+  int64_t target_items = 1024;         // SCILMM_TARGET_ITEMS    explicit work items per launch (target)
+  int64_t min_item = 24;               // SCILMM_MIN_ITEM        cost units of an item, lower bound
+  int64_t max_item = 96;               // SCILMM_MAX_ITEM        ... and upper bound (>= min_item)
+  std::optional<int64_t> dense_items;  // SCILMM_DENSE_ITEMS     k_dense_b items per launch (>= 64); unset: 128 / 512 / 1024
+                                       //                        for tails below 24576 / below 32768 / wider
+  int64_t dense_fill = 256;            // SCILMM_DENSE_FILL      workgroups per round the dense item counts are fitted to; 0: off
+  std::optional<bool> dense_taper;     // SCILMM_DENSE_TAPER=1/0 shorter items at the end of an early dense launch;
+                                       //                        unset: on for launches of 1024 items
+  std::optional<int> dist_group;       // SCILMM_DIST_GROUP      source-group size of a distributed tail; unset: >= 8
+  bool dist_nosplit = false;           // SCILMM_DIST_NOSPLIT=1  no look-ahead split of a distributed target's late update
+  int chain_cap = 2048;                // SCILMM_CHAIN_CAP       fronts the chain sweep takes at most
+  int chain_wide = 12;                 // SCILMM_CHAIN_WIDE      a level joins the chain while it has at most this many fronts
+  bool no_chain = false;               // SCILMM_NO_CHAIN=1      level kernels only
+  int64_t push_slice = 512;            // SCILMM_PUSH_SLICE      rows per slice of a long backward push group (>= 256)
+  // -- read per call (the parity tests force each value on one handle)
+  bool shadow = true;                  // SCILMM_SHADOW=0        run_factorize: k_dense32 instead of the fp32 shadow (k_dense_h)
+  int chain_wide_t = 256;              // SCILMM_CHAIN_WIDE_T    run_rhs: chains from this length on sweep 64-column windows
+  int chain_full_t = 768;              // SCILMM_CHAIN_FULL_T    run_rhs: ... and from this length on one 112-column window
+  bool sinv_generic = false;           // SCILMM_SINV_GENERIC=1  selected inverse: the gather kernel for the dense tail too
+};
+
+// The environment is read on every call: tests switch SCILMM_TUNING and a switch on and off inside one process.
+inline Tuning read_tuning() {
+  Tuning t;
+  const char* gate = getenv("SCILMM_TUNING");
+  if (!(gate && gate[0] == '1')) return t;
+  auto env = [](const char* name) { return getenv(name); };
+  auto is1 = [&](const char* name) { const char* e = env(name); return e && e[0] == '1'; };
+  auto not0 = [&](const char* name) { const char* e = env(name); return !(e && e[0] == '0'); };
+  const char* e;
+  if ((e = env("SCILMM_RESERVE_CUS"))) t.reserve_cus = atoi(e);
+  if ((e = env("SCILMM_SIDE_STREAMS"))) t.side_streams = atoi(e);
+  t.no_mfma = is1("SCILMM_NO_MFMA");
+  t.trsm_lite = not0("SCILMM_TRSM_LITE");
+  if ((e = env("SCILMM_DENSE"))) t.dense = e[0] != '0';
+  if ((e = env("SCILMM_OUTSIDE"))) t.outside = e[0] != '0';
+  t.outside_merge = not0("SCILMM_OUTSIDE_MERGE");
+  if ((e = env("SCILMM_OUTSIDE_CHUNKS"))) t.outside_chunks = atoi(e);
+  t.outside_prio = is1("SCILMM_OUTSIDE_PRIO");
+  if ((e = env("SCILMM_CELL_LIMIT"))) t.cell_limit = atof(e);
+  t.no_lookahead = is1("SCILMM_NO_LOOKAHEAD");
+  if ((e = env("SCILMM_LOOK_DEPTH"))) t.look_depth = std::max(1, atoi(e));
+  t.host_cells = is1("SCILMM_HOST_CELLS");
+  t.no_splitk = is1("SCILMM_NO_SPLITK");
+  if ((e = env("SCILMM_TARGET_ITEMS"))) t.target_items = atoll(e);
+  if ((e = env("SCILMM_MIN_ITEM"))) t.min_item = atoll(e);
+  if ((e = env("SCILMM_MAX_ITEM"))) t.max_item = atoll(e);
+  if ((e = env("SCILMM_DENSE_ITEMS"))) t.dense_items = atoll(e);
+  if ((e = env("SCILMM_DENSE_FILL"))) t.dense_fill = atoll(e);
+  if ((e = env("SCILMM_DENSE_TAPER"))) t.dense_taper = e[0] == '1';
+  if ((e = env("SCILMM_DIST_GROUP"))) t.dist_group = atoi(e);
+  t.dist_nosplit = is1("SCILMM_DIST_NOSPLIT");
+  if ((e = env("SCILMM_CHAIN_CAP"))) t.chain_cap = atoi(e);
+  if ((e = env("SCILMM_CHAIN_WIDE"))) t.chain_wide = atoi(e);
+  t.no_chain = is1("SCILMM_NO_CHAIN");
+  if ((e = env("SCILMM_PUSH_SLICE"))) t.push_slice = atoll(e);
+  t.shadow = not0("SCILMM_SHADOW");
+  if ((e = env("SCILMM_CHAIN_WIDE_T"))) t.chain_wide_t = atoi(e);
+  if ((e = env("SCILMM_CHAIN_FULL_T"))) t.chain_full_t = atoi(e);
+  t.sinv_generic = is1("SCILMM_SINV_GENERIC");
+  return t;
+}
+
+// SCILMM_VERBOSE only prints (the [scilmm plan] lines); it is not gated by SCILMM_TUNING.
+inline bool verbose() { return getenv("SCILMM_VERBOSE") != nullptr; }
+
+struct Dev {
+  int device = 0;                  // HIP device the handle was created on; every entry point runs on it (DevGuard)
+  hipStream_t stream = nullptr;
+  Tuning tune;                     // the schedule switches as they were when this state was created
+  int prio_lo = 0, prio_hi = 0;    // stream priority range of the device (hi: the main stream's)
+  DevSym v{};
+  std::vector<void*> allocs;
+  int32_t* d_level_tiles = nullptr;
+  int32_t* d_level_fronts = nullptr;
+  int32_t* d_level_pairs = nullptr;
+  int32_t* d_all_fronts = nullptr;  // multi-GPU: Symbolic::level_fronts unfiltered (the forward sweep solves every
+                                    // tail block on every rank: the inverse diagonal blocks are replicated)
+  std::vector<double*> vals;       // per matrix: pattern-order values or diagonal values
+  std::vector<uint8_t> have_vals;
+  double* W = nullptr;             // n x RPMAX workspaces (permuted right-hand sides)
+  double* X = nullptr;
+  double* IO = nullptr;            // staging for host<->device dense transfers
+  size_t io_cap = 0;
+  double* partial = nullptr;
+  int64_t nwaves_quad = 0;
+  double* d_out = nullptr;         // RPMAX doubles
+  bool use_mfma = true;
+  bool trsm_lite = true;           // k_trsm_lite instead of k_trsm<true> (SCILMM_TUNING=1 SCILMM_TRSM_LITE=0: the round-1 kernel)
+  hipEvent_t ev[8];
+  scilmm_timing timing{};
+  bool quad_pending = false;           // a scilmm_quadforms_dev call whose timer has not been read yet
+  bool attrs_set = false;
+  // update-kernel plan: flattened combo descriptors, per-level work items (split-K), partial slots
+  ComboDesc* d_combos = nullptr;
+  UpdWork* d_work = nullptr;
+  std::vector<int64_t> work_ptr;   // [nlevels+1] LATE items (descendants one level below the target): main stream
+  UpdWork* d_work_early = nullptr; // EARLY items (older descendants): side stream, overlaps the previous level
+  std::vector<int64_t> early_ptr;  // [nlevels+1]
+  int64_t max_slots = 0;           // partial slabs per scratch half (scratch is double-buffered by level parity)
+  hipStream_t side = nullptr;
+  hipStream_t side2 = nullptr;     // early updates alternate between two side streams (their tails overlap)
+  hipStream_t side3 = nullptr;     // optional third one (SCILMM_SIDE_STREAMS=3)
+  int nside = 2;
+  bool serial_early = false;       // profiling mode 2: every early launch on ONE side stream (launch durations do not overlap)
+  std::vector<hipEvent_t> lev_ev;  // 2 per level: [2l] = level l finished, [2l+1] = early update of level l finished
+  hipEvent_t ev_asm = nullptr;
+  hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;  // main <-> comm stream hand-offs (multi-GPU)
+  int32_t* d_tile_pslot = nullptr;   // late partial slabs of a tile (main stream)
+  int32_t* d_tile_pnseg = nullptr;
+  int32_t* d_tile_pslot_e = nullptr; // early partial slabs of a tile (side stream)
+  int32_t* d_tile_pnseg_e = nullptr;
+  int32_t* d_red_tiles_e = nullptr;
+  std::vector<int64_t> red_ptr_e;
+  std::vector<int64_t> lev_cost_e, lev_cost_l;  // per-level dense update cost units (diagnostics)
+  double* scratch = nullptr;       // max slots per level * TM*NB doubles
+  int32_t* d_red_tiles = nullptr;  // tiles that carry partial slabs, grouped by level
+  // cell-wise path for small update pairs: set 0 = early (side stream), set 1 = late (main stream)
+  struct CellSet {
+    int64_t* dst = nullptr;
+    int64_t* grp = nullptr;
+    int64_t* srct = nullptr;
+    int64_t* srcq = nullptr;
+    int32_t* md = nullptr;
+    int32_t* wd = nullptr;
+    std::vector<int64_t> level_ptr;    // [nlevels+1] over unique target cells
+    std::vector<int64_t> level_short;  // [nlevels] short groups (listed first) per level
+  } cellset[3];  // 0 = early (side streams), 1 = late (main stream); 2 unused (kept for the device cell plan's key layout)
+  int64_t n_dense_combos = 0, n_sparse_combos = 0, n_cells = 0;
+  std::vector<int64_t> red_ptr;    // [nlevels+1]
+  bool profiling = false;
+  int ablate = 0;
+  // multi-GPU: the fronts of the dense tail (>= dist_first) are owned 1-D block-cyclically.  A rank STORES the prelude
+  // (replicated), its own tail panels and a ring of dist_G slots through which the other ranks' panels pass (fan-out:
+  // a received panel is applied to every own target that needs it and then dropped) -- see DistLayout.
+  int32_t rank = 0, world = 1;
+  int32_t dist_first = 0;               // first distributed front (nsuper: nothing is distributed)
+  int32_t dist_Wg = 8, dist_G = 32;     // source-group size of the batched updates; ring slots
+  std::vector<int64_t> loff;            // [nsuper+1] rank-local panel offsets (== Symbolic::sn_loff when world == 1)
+  int64_t nL_local = 0;                 // doubles of rank-local panel storage (prelude + own tail + ring)
+  std::vector<uint8_t> keep_front;      // [nsuper] this rank computes the panel of front s
+  std::vector<int32_t> tail_of_level;   // [nlevels] the distributed front of level l, or -1
+  // level lists without the tail fronts of other ranks (== the Symbolic's when world == 1)
+  std::vector<int32_t> lv_ptr, lv_fronts, lv_tiles, lv_pairs;  // lv_ptr: [nlevels+1] into lv_fronts
+  std::vector<int64_t> lv_tile_ptr, lv_tile_mid, lv_pair_ptr;  // lv_tile_mid[l]: first tile of the level's own distributed panel
+  int32_t* d_lmul_tiles = nullptr;      // tiles this rank multiplies in L*R (own tail; the prelude on rank 0 only)
+  int64_t n_lmul_tiles = 0;
+  DenseWork* d_dwork_b = nullptr;       // batch items of the distributed tail
+  std::vector<int64_t> dbatch_ptr;      // [ngroups+1]
+  std::vector<hipEvent_t> batch_ev;     // [ngroups] batch g applied to all own targets
+  std::vector<hipEvent_t> bpev;         // profiling: [2 ngroups] begin / end of batch g on the batches' stream
+  std::vector<int32_t> last_own_level;  // [ngroups] level of this rank's last own tail front in group g, or -1
+  hipStream_t bstream = nullptr;        // the batches' stream
+  hipStream_t comm = nullptr;           // caller-owned stream the collectives are issued on
+  std::vector<hipEvent_t> done_ev;      // per level with a distributed front: this rank's kernels of the level finished
+  double* ACC = nullptr;                // forward sweep: contributions of this rank's own tail panels, n x RPMAX (dist)
+  // selected inverse (scilmm_selected_inverse): column -> front, per-front offset of Y inside the per-level scratch
+  int32_t* d_col_front = nullptr;
+  int64_t* d_yoff = nullptr;
+  double* d_ybuf = nullptr;
+  int32_t* d_sinv_pre_tiles = nullptr;        // tiles of the non-tail fronts, by level (k_sinv_w)
+  std::vector<int64_t> sinv_pre_ptr;          // [nlevels+1]
+  std::vector<int32_t> sinv_tail_front;       // [nlevels] the dense-tail front of the level, or -1
+  int32_t* d_sinv_tail_fronts = nullptr;      // the tail fronts, one per entry (k_sinv_zero takes a list)
+  SinvWork* d_sinv_work = nullptr;            // items of k_sinv_tail, grouped by tail front
+  std::vector<int64_t> sinv_work_ptr;         // [ntail+1]
+  bool work_external = false;           // W / X / ACC belong to the caller (scilmm_dist_set_work)
+  // dense tail (Symbolic::dense_first): implicit work items of k_dense, early (side streams) and late (main stream)
+  // prelude -> tail contributions in descendant coordinates (k_outside; fp64 atomics): one launch between the last
+  // prelude level and the first tail level
+  bool outside_on = false;
+  int32_t tail_level = 0;               // level of the first tail front
+  std::vector<uint8_t> outside_desc;    // [nsuper] descendant handled by k_outside
+  OutsideWork* d_owork = nullptr;
+  int32_t* d_grp_next = nullptr;   // [nsuper] k_outside: next descendant with the same tail rows as this one, or -1
+  int32_t* d_grp_t0 = nullptr;     // [nsuper] its first tail row
+  int64_t n_owork = 0;
+  int32_t* d_tail_front = nullptr;
+  uint8_t* d_keep_front = nullptr;
+  hipStream_t outside_st = nullptr;
+  // PROGRESSIVE k_outside: the items are sorted by the FIRST tail panel they touch and cut into chunks; chunk g is one launch
+  // and one event, and whatever touches tail panel f (its early / late updates, its potrf) waits only for the last chunk that
+  // holds an item reaching f or an earlier panel -- left-looking updates write nothing but the level's own panel, so the rest
+  // of the atomic contributions (to LATER panels only) overlaps with the first levels of the tail, which are chain-bound
+  std::vector<int64_t> ochunk_ptr;       // [nchunks + 1] into d_owork
+  std::vector<hipEvent_t> out_evs;       // [nchunks]
+  std::vector<int32_t> out_wait_chunk;   // [nlevels] chunk the level's tail front waits for, -1: none
+  bool dense_on = false;
+  int front_bits = 64;                  // 32: dense-tail products on the fp32 matrix pipe (k_dense32), sums in fp64
+  double* d_zeros = nullptr;            // 2 KiB of zeros: source of the B k-rows past a descendant's end (k_dense_b)
+  DenseWork* d_dwork_e = nullptr;
+  DenseWork* d_dwork_l = nullptr;
+  std::vector<int64_t> dwork_e_ptr, dwork_l_ptr;  // [nlevels+1]
+  // distributed tail, look-ahead split of an own target's late update: items [dwork_l_ptr[l], dwork_l_mid[l]) take the sources
+  // that arrived EARLIER (they run while the newest source panel is still being factored / broadcast), items
+  // [dwork_l_mid[l], dwork_l_ptr[l+1]) the newest source alone (== dwork_l_ptr[l+1] where nothing is split)
+  std::vector<int64_t> dwork_l_mid;               // [nlevels]
+  int64_t n_late_split = 0;                       // levels of the last factorization whose late launch was split
+  int look_depth = 2;      // "late" = descendants at most this many levels below the target; older ones are "early"
+  int rhs_pending = -1;            // mode of the last run_rhs whose events have not been read yet
+  // dense-chain sweeps (k_chain): the last chain_T levels are single fronts whose mutual update pairs are contiguous
+  int32_t chain_T = 0, chain_l0 = 0;
+  int32_t* d_chain = nullptr;
+  int32_t* d_colmap = nullptr;     // forward: column -> row maps of the non-contiguous chain pairs
+  int32_t* d_cf_ptr = nullptr;     // forward: pairs of chain target i (descendants ascending)
+  ChainPair* d_cf = nullptr;
+  int32_t* d_cb_ptr = nullptr;     // backward: pairs of chain descendant i (targets descending)
+  ChainPair* d_cb = nullptr;
+  int64_t* d_cg_ptr = nullptr;     // backward: pairs (chain target, non-chain descendant) grouped by descendant
+  int32_t* d_cg_pairs = nullptr;
+  int64_t chain_groups = 0;
+  // long groups are cut into row slices that write partial sums; k_push_fold adds them up in fixed order
+  int32_t* d_cg_slot = nullptr;      // per work item: partial slot or -1 (subtract straight from X)
+  int32_t* d_fold = nullptr;         // triples (descendant, first slot, slices)
+  int64_t n_fold = 0;
+  double* d_push_partial = nullptr;  // [slots][NB][RPMAX]
+  int32_t* d_chain_flags = nullptr;  // [chain_T * RPMAX/CW] epoch stamps
+  int32_t* d_chain_err = nullptr;    // [0] error flag, [1] progress beacon, [2] ticket counter of the running sweep
+  int32_t* h_chain_err = nullptr;    // pinned mirror of [0], refreshed by a queued copy after every solve
+  int32_t chain_epoch = 0;
+  std::vector<hipEvent_t> pev;     // 4 events per level when profiling
+  // deterministic mode (scilmm_set_deterministic): pull schedule of the forward sweep / L*R, transposed pattern index
+  bool det = false;
+  PullPlan pull{};
+  int32_t* d_pull_level_segs = nullptr;
+  int32_t* d_pull_fold = nullptr;
+  double* d_pull_partial = nullptr;     // [pull_max_slots][NB][RPMAX]
+  uint8_t* d_chain_mask = nullptr;      // [nsuper] front is swept by k_chain
+  const int64_t* d_pat_rowptr = nullptr;
+  const int64_t* d_pat_rowslot = nullptr;
+  const int32_t* d_pat_rowcol = nullptr;
+  int64_t n_float_atomic = 0;           // launches since the handle was created that sum with floating-point atomics
+};
+
+#define HIPCHK(call)                                                                                   \
+  do {                                                                                                 \
+    hipError_t _e = (call);                                                                            \
+    if (_e != hipSuccess) {                                                                            \
+      sym->err = std::string(#call) + ": " + hipGetErrorString(_e);                                    \
+      return SCILMM_ERR_DEVICE;                                                                        \
+    }                                                                                                  \
+  } while (0)
+
+// Makes the handle's device current for the duration of an entry point and restores the caller's device afterwards
+// (a handle may be used from a thread whose current device is a different one).
+struct DevGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DevGuard(const scilmm_symbolic* sym) {
+    const Dev* D = sym ? (const Dev*)sym->device : nullptr;
+    if (D) enter(D->device);
+  }
+  explicit DevGuard(int device) { enter(device); }
+  void enter(int device) {
+    if (device < 0) return;
+    if (hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
+    if (!switched) (void)hipGetLastError();  // never leave a failed hipSetDevice behind as the thread's "last error"
+  }
+  ~DevGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+};
+
+// (out: a T* or const T* of the device state)
+template <typename T, typename P>
+int upload(scilmm_symbolic* sym, Dev* D, const std::vector<T>& h, P** out) {
+  static_assert(std::is_same<typename std::remove_const<P>::type, T>::value, "upload: pointer type != element type");
+  void* p = nullptr;
+  size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
+  HIPCHK(hipMalloc(&p, bytes));
+  D->allocs.push_back(p);
+  if (!h.empty()) HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  *out = (P*)p;
+  return SCILMM_OK;
+}
+
+// Rank-local storage of a distributed factor (world > 1).  Tail front dense_first + jj belongs to rank jj % world.
+//   [ prelude panels, as in the Symbolic | own tail panels, packed | ring: G slots of the largest tail panel ]
+// A panel of another rank lives in slot jj % G from its broadcast until every own target has consumed it: the batch of
+// its source group g = jj / Wg (applied when the group is complete) and the late updates of the own targets of groups
+// g and g + 1 -- so a slot is free again well before panel jj + G arrives (G = 4 Wg; the level loop still orders the
+// re-use with events).  Per rank: nnz(L_tail) / world + G panels instead of the whole factor.
+struct DistLayout {
+  int32_t first = 0, Wg = 8, G = 32;
+  std::vector<int64_t> loff;
+  int64_t nL = 0, ring_base = 0, slot = 0;
+};
+
+// plan.hip: what engine.hip calls across the boundary
+void dev_free(void* p);
+void dist_layout(const Symbolic& S, int32_t rank, int32_t world, const Tuning& tune, DistLayout* o);
+int ensure_device(scilmm_symbolic* sym, Dev** out);
+int ensure_sinv_plan(scilmm_symbolic* sym, Dev* D);
+
+}  // namespace scilmm

@@ -7,7 +7,7 @@
 struct scilmm_symbolic {
   scilmm::Symbolic* S = nullptr;
   std::string err;
-  void* device = nullptr;              // owned by engine.hip
+  void* device = nullptr;              // struct Dev (dev.h): built by plan.hip, released through device_free
   void (*device_free)(void*) = nullptr;
   // multi-GPU (scilmm_dist_init): this process is rank `rank` of `world`; collectives go through comm_fn, issued on
   // comm_stream (a hipStream_t owned by the caller, e.g. the raw handle of a torch stream)

@@ -13,59 +13,22 @@
 //   lane l receives D[(l>>4) + 4*reg][l&15], reg = 0..3.
 #pragma once
 #include <hip/hip_runtime.h>
-#ifndef SCILMM_KC
-#define SCILMM_KC 16
-#endif
-#ifndef SCILMM_NB
-#define SCILMM_NB 128
-#endif
 #ifndef SCILMM_UPD_WAVES
 #define SCILMM_UPD_WAVES 2
 #endif
 #include <stdint.h>
 
+#include "plan_types.h"
+
 namespace scilmm {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr int NB = SCILMM_NB; // max supernode block width (symbolic max_width must be <= NB)
 constexpr int NJB = NB / 16;  // 16-column MFMA tiles across a block
-constexpr int TM = 128;       // target rows per tile
 constexpr int KCS = 16;       // k-chunk of the trsm / solve kernels
-constexpr int KC = SCILMM_KC;  // k-chunk of the update kernel: 2 buffers x 16 x (144 + 144) doubles = 74 KB -> two workgroups per CU
 constexpr int LDA = TM + 16;  // k-major LDS leading dims: (ld*8 B) == 128 mod 256 -> conflict-free b64 reads
 constexpr int LDB = NB + 16;
-constexpr int RPMAX = 128;    // max padded RHS columns per pass
 constexpr int LDP = 34;       // [k][q] LDS image of a panel slice (q-chunk of 32)
-
-struct DevSym {
-  int32_t n, nsuper;
-  const int32_t* sn_start;
-  const int64_t* sn_rowptr;
-  const int32_t* sn_rows;
-  const int64_t* sn_loff;
-  const int64_t* inv_off;
-  const int32_t* upd_src;
-  const int32_t* upd_p0;
-  const int32_t* upd_p1;
-  const int32_t* tile_front;
-  const int64_t* tile_base;
-  const int64_t* combo_ptr;
-  const int32_t* combo_pair;
-  const int32_t* combo_ta;
-  const int32_t* combo_tb;
-  const int64_t* asm_dst;
-  const int64_t* diag_dst;
-  const int64_t* pat_colptr;
-  const int32_t* pat_row;
-  const int32_t* perm;
-};
-
-struct ValPtrs {
-  const double* v[8];
-  double s2[8];
-  int32_t count;
-};
 
 __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -166,24 +129,6 @@ __device__ __forceinline__ void tile_mma(const double* __restrict__ As, const do
 // chunk i+1 are in flight in registers while chunk i feeds the MFMAs; one barrier per chunk.
 // A work item is (tile, combo range [cb,ce), slot): slot < 0 subtracts straight into the panel,
 // slot >= 0 writes the partial product to scratch (split-K; folded in by k_reduce).
-struct ComboDesc {
-  int64_t loff;     // L offset of the descendant panel
-  int64_t rowoff;   // offset of its row list in sn_rows
-  int32_t md, wd;   // panel rows (leading dimension) and width (K extent)
-  int32_t ta, nt;   // descendant rows [ta, ta+nt) land in this tile
-  int32_t p0, nq;   // descendant rows [p0, p0+nq) are the target's columns
-  int32_t ip0;      // >= 0: rows land at consecutive tile positions ip0..; -1: look each one up
-  int32_t jp0;      // >= 0: columns land at consecutive target columns jp0..; -1: look each one up
-  int32_t ilo, ihi; // first / last tile position touched (rows are sorted, so everything lies in between)
-  int32_t jlo, jhi; // first / last target column touched
-};
-
-struct UpdWork {
-  int32_t tile;
-  int32_t slot;     // partial-slot index or -1
-  int64_t cb, ce;   // combo range
-};
-
 constexpr int UPD_THREADS = 512;  // update kernel: eight waves per workgroup
 
 // Eight-wave variant of the tile product: wave wv owns 16 target rows, acc[jb] is the 16 x 16 tile of columns 16 jb..
@@ -454,14 +399,6 @@ __global__ __launch_bounds__(UPD_THREADS, SCILMM_UPD_WAVES) void k_update2(DevSy
 // target's columns), one workgroup per CU so that the accumulators (64 doubles per lane) fit the register file.
 // k_dense_b is the fp64 form, k_dense32 the fp32-product form; the register-staged and the both-operands-by-DMA
 // predecessors live in csrc/tools/retired_kernels.hip.h (tuning harness only).
-struct DenseWork {
-  int32_t front;       // target front j (>= dense_first)
-  int32_t ti0;         // first of the (one or two) target tiles
-  int32_t ntiles;      // 1 or 2
-  int32_t k0, k1;      // descendants dense_first + k0 .. dense_first + k1 - 1
-  int32_t slot0, slot1;  // partial slab of each tile, or -1: subtract straight from the panel
-  int32_t pad;
-};
 #ifndef SCILMM_DENSE_ABL
 #define SCILMM_DENSE_ABL 0  // tuning-harness ablations (csrc/tools/dense_bench.hip only): 1 no epilogue, 2 no global loads, 3 no LDS stores
 #endif
@@ -1027,12 +964,6 @@ __global__ __launch_bounds__(512, SCILMM_DENSE_H_WGS) void k_dense_h(DevSym S, i
 // to run; SCILMM_DETERMINISTIC=1 keeps these updates on the target-coordinate path (fixed order).
 // One workgroup (4 waves, wave = 32 rows x 128 columns) per lower block pair (bi >= bj) of one descendant; the
 // launch runs while nothing else touches the tail panels (after the last prelude level, before the first tail level).
-struct OutsideWork {
-  int32_t d;        // descendant front (below the dense tail)
-  int32_t t0;       // first row of its panel that lies in the tail
-  int32_t bi, bj;   // 128-row blocks of those rows: target rows / target columns
-};
-
 // SCATTER: 0 = atomic subtraction (the product), 1 = nothing, 2 = plain stores (timing ablations of diagnostic builds)
 template <bool MFMA, int SCATTER = 0>
 __global__ __launch_bounds__(256) void k_outside(DevSym S, int32_t dense_first, const OutsideWork* __restrict__ work,
@@ -1171,8 +1102,6 @@ __device__ __forceinline__ double cell_dot(const double* __restrict__ L, int64_t
   }
   return acc;
 }
-
-struct CellSrc { int64_t st, sq; int32_t md, wd; };
 
 // groups [first, first+n_short) : one thread each;  groups [first+n_short, first+count) : one wave each
 __global__ __launch_bounds__(256) void k_sparse_cells(int64_t first, int64_t n_short, int64_t count,
@@ -1785,10 +1714,6 @@ __device__ __forceinline__ void rhs_mma(const double* __restrict__ A_lds, int ld
 // Right-hand-side kernels work on a window of CW = 32 columns selected by blockIdx.y (gridDim.y =
 // ceil(rp / CW)): four times the workgroups per level, a quarter of the MFMA chain and of the staging per
 // workgroup, 24 KB LDS images.  Global RHS rows keep the full stride rp.
-#ifndef SCILMM_CW
-#define SCILMM_CW 32
-#endif
-constexpr int CW = SCILMM_CW;  // RHS columns per workgroup
 constexpr int LDW = 48;        // LDS leading dimension of [k][c] images (== 16 mod 32, >= CW)
 constexpr int NCT = CW / 16;   // 16-column MFMA tiles per window
 
@@ -2076,13 +2001,6 @@ __global__ __launch_bounds__(256) void k_push_fold(DevSym S, const int32_t* __re
 // A front with one segment stores its rows itself; the segments of a long pair list leave partial sums in their slots
 // and k_pull_fold adds them in slot order.  Nothing depends on timing: the result is bitwise reproducible.
 // skip_src (MODE 0, optional): descendants whose contributions arrive another way (the chain fronts, swept by k_chain).
-struct PullPlan {
-  const int32_t* seg_front;
-  const int64_t* seg_ptr;
-  const int32_t* seg_slot;
-  const int32_t* front_seg;
-};
-
 template <bool MFMA, int MODE>
 __global__ __launch_bounds__(256) void k_fwd_pull(DevSym S, PullPlan P, const int32_t* __restrict__ segs,
                                                   const uint8_t* __restrict__ skip_src, const double* __restrict__ L,
@@ -2232,13 +2150,6 @@ __global__ __launch_bounds__(256) void k_pull_fold(DevSym S, const int32_t* __re
 // requirement (decoupled look-back argument); the wait is bounded as well (err flag), so every wave always exits.
 // The L fragments are read straight from global memory into the MFMA A operand BEFORE the wait: only the
 // 128 x 32 x-window of the block just finished is on the critical path.
-struct ChainPair {
-  int32_t other;  // chain position of the other block (descendant j forward, target t backward)
-  int32_t p0, nq; // rows [p0, p0+nq) of the descendant panel ...
-  int32_t jp0;    // ... are columns jp0.. of the target block when >= 0 (contiguous: every pair of a dense chain)
-  int32_t map;    // jp0 < 0, forward: offset into the column -> row map (NB entries, -1 = no such row)
-};
-
 
 __device__ __forceinline__ bool chain_wait(const int32_t* flag, int32_t epoch, int32_t* err, int behind) {
   // one thread spins; returns false on timeout / earlier error (the caller then leaves quietly).  `behind` = how
@@ -2781,12 +2692,6 @@ __global__ __launch_bounds__(256) void k_dot_diag(int32_t n, const int64_t* __re
 // (rows = all later columns) and by bisection in a prelude front's row list.  Twice the factorization's flops; the
 // factor is consumed (it has to be refactorized before the next solve).  tr(V^-1 A_k) is then one pass over A_k's
 // pattern slots: sum_e c_e vals_k[e] Z[asm_dst[e]] (k_sinv_trace), c_e = 2 off the diagonal.
-struct SinvOwner {  // where the entries Z(., lo) with lo in one front live
-  int64_t loff;       // panel offset
-  const int32_t* rows;  // row list of the front (prelude fronts: searched)
-  int32_t c0, m;      // first column, panel rows
-  int32_t tail;       // rows = c0 .. n-1: position by arithmetic
-};
 __device__ __forceinline__ SinvOwner sinv_owner(const DevSym& S, const int32_t* __restrict__ col_front, int32_t dense_first, int32_t col) {
   const int32_t a = col_front[col];
   SinvOwner o;
@@ -2977,11 +2882,6 @@ __global__ __launch_bounds__(256) void k_sinv_w(DevSym S, const int32_t* __restr
 //    diagonal need no special case.
 //  * the sum is ADDED to the panel with fp64 atomics (the front's rows were zeroed after Y was taken): several K ranges
 //    of one row tile run as separate workgroups, which is what keeps a launch at >= 1000 items for every front.
-struct SinvWork {
-  int32_t front;   // tail front s
-  int32_t q;       // rows [256 q, 256 q + 256) of R
-  int32_t ka, kb;  // source fronts [ka, kb) (absolute front ids, all > s)
-};
 __global__ __launch_bounds__(512, 1) void k_sinv_tail(DevSym S, int32_t dense_first, const SinvWork* __restrict__ work, double* L,
                                                       const double* __restrict__ Ybuf, const int64_t* __restrict__ yoff,
                                                       const int32_t* __restrict__ col_front, const double* __restrict__ zeros) {

@@ -1,0 +1,117 @@
+// Plain structs and constants shared by the kernels (kernels.hip.h) and the host code that builds their plans
+// (plan.hip): what a kernel takes as an argument or reads from a device array.  No device code in here.
+#pragma once
+#include <stdint.h>
+#ifndef SCILMM_KC
+#define SCILMM_KC 16
+#endif
+#ifndef SCILMM_NB
+#define SCILMM_NB 128
+#endif
+#ifndef SCILMM_CW
+#define SCILMM_CW 32
+#endif
+
+namespace scilmm {
+
+constexpr int NB = SCILMM_NB; // max supernode block width (symbolic max_width must be <= NB)
+constexpr int TM = 128;       // target rows per tile
+constexpr int KC = SCILMM_KC;  // k-chunk of the update kernel: 2 buffers x 16 x (144 + 144) doubles = 74 KB -> two workgroups per CU
+constexpr int RPMAX = 128;    // max padded RHS columns per pass
+constexpr int CW = SCILMM_CW;  // RHS columns per workgroup
+
+struct DevSym {
+  int32_t n, nsuper;
+  const int32_t* sn_start;
+  const int64_t* sn_rowptr;
+  const int32_t* sn_rows;
+  const int64_t* sn_loff;
+  const int64_t* inv_off;
+  const int32_t* upd_src;
+  const int32_t* upd_p0;
+  const int32_t* upd_p1;
+  const int32_t* tile_front;
+  const int64_t* tile_base;
+  const int64_t* asm_dst;
+  const int64_t* diag_dst;
+  const int64_t* pat_colptr;
+  const int32_t* pat_row;
+  const int32_t* perm;
+};
+
+struct ValPtrs {
+  const double* v[8];
+  double s2[8];
+  int32_t count;
+};
+
+// k_update2 (a work item is (tile, combo range [cb,ce), slot)): one descendant's contribution to one target tile
+struct ComboDesc {
+  int64_t loff;     // L offset of the descendant panel
+  int64_t rowoff;   // offset of its row list in sn_rows
+  int32_t md, wd;   // panel rows (leading dimension) and width (K extent)
+  int32_t ta, nt;   // descendant rows [ta, ta+nt) land in this tile
+  int32_t p0, nq;   // descendant rows [p0, p0+nq) are the target's columns
+  int32_t ip0;      // >= 0: rows land at consecutive tile positions ip0..; -1: look each one up
+  int32_t jp0;      // >= 0: columns land at consecutive target columns jp0..; -1: look each one up
+  int32_t ilo, ihi; // first / last tile position touched (rows are sorted, so everything lies in between)
+  int32_t jlo, jhi; // first / last target column touched
+};
+
+struct UpdWork {
+  int32_t tile;
+  int32_t slot;     // partial-slot index or -1
+  int64_t cb, ce;   // combo range
+};
+
+// k_dense_b / k_dense32 / k_dense_h
+struct DenseWork {
+  int32_t front;       // target front j (>= dense_first)
+  int32_t ti0;         // first of the (one or two) target tiles
+  int32_t ntiles;      // 1 or 2
+  int32_t k0, k1;      // descendants dense_first + k0 .. dense_first + k1 - 1
+  int32_t slot0, slot1;  // partial slab of each tile, or -1: subtract straight from the panel
+  int32_t pad;
+};
+
+// k_outside
+struct OutsideWork {
+  int32_t d;        // descendant front (below the dense tail)
+  int32_t t0;       // first row of its panel that lies in the tail
+  int32_t bi, bj;   // 128-row blocks of those rows: target rows / target columns
+};
+
+struct CellSrc { int64_t st, sq; int32_t md, wd; };
+
+// k_fwd_pull (pull schedule of the forward sweep and of L*R)
+struct PullPlan {
+  const int32_t* seg_front;
+  const int64_t* seg_ptr;
+  const int32_t* seg_slot;
+  const int32_t* front_seg;
+};
+
+// k_chain
+struct ChainPair {
+  int32_t other;  // chain position of the other block (descendant j forward, target t backward)
+  int32_t p0, nq; // rows [p0, p0+nq) of the descendant panel ...
+  int32_t jp0;    // ... are columns jp0.. of the target block when >= 0 (contiguous: every pair of a dense chain)
+  int32_t map;    // jp0 < 0, forward: offset into the column -> row map (NB entries, -1 = no such row)
+};
+
+// selected inverse
+struct SinvOwner {  // where the entries Z(., lo) with lo in one front live
+  int64_t loff;       // panel offset
+  const int32_t* rows;  // row list of the front (prelude fronts: searched)
+  int32_t c0, m;      // first column, panel rows
+  int32_t tail;       // rows = c0 .. n-1: position by arithmetic
+};
+
+// k_sinv_tail
+struct SinvWork {
+  int32_t front;   // tail front s
+  int32_t q;       // rows [256 q, 256 q + 256) of R
+  int32_t ka, kb;  // source fronts [ka, kb) (absolute front ids, all > s)
+};
+
+}  // namespace scilmm
