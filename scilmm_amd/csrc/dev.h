@@ -258,7 +258,7 @@ struct Dev {
   int32_t* d_chain_err = nullptr;    // [0] error flag, [1] progress beacon, [2] ticket counter of the running sweep
   int32_t* h_chain_err = nullptr;    // pinned mirror of [0], refreshed by a queued copy after every solve
   int32_t chain_epoch = 0;
-  std::vector<hipEvent_t> pev;     // 4 events per level when profiling
+  std::vector<hipEvent_t> pev;     // profiling: PEV_PER_LEVEL events per level (enum ProfEvent, engine.hip)
   // deterministic mode (scilmm_set_deterministic): pull schedule of the forward sweep / L*R, transposed pattern index
   bool det = false;
   PullPlan pull{};

@@ -2,6 +2,14 @@
 // (factorize / solve / L*R / quadratic forms) and the numeric C-ABI entry points of include/scilmm_hip.h.
 // The device state they run on (struct Dev, dev.h) is built once per handle by plan.hip.  Everything runs on one
 // HIP stream per symbolic handle; host entry points synchronise only where they hand data back to the caller.
+//
+// A launch sequence is a struct that lives for one call, with one method per step (the kernels go through the typed
+// launchers of launch.hip.h):
+//   Factorization (run_factorize): prepare_shadow, assemble, prepare_profiling, early(l), late_updates(l), factor_panel(l),
+//     broadcast_tail(l), batch(grp), outside_and_deferred_early(l), exchange_status;
+//     finish_factorize waits for it, ProfRead turns the profiling events (enum ProfEvent) into scilmm_timing;
+//   Sweep (run_rhs): solve_single, solve_dist, lmul_single, lmul_dist per block of RPMAX columns, built from pull /
+//     pull_groups (deterministic mode), chain, handoff (distributed) and mark_mid.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -89,9 +97,323 @@ struct scilmm_factor {
   int32_t* h_status = nullptr;  // pinned host copy of *status, filled by the queued copy
 };
 
+#include "launch.hip.h"
+
 namespace {
 
+#define TRY(call)                      \
+  do {                                 \
+    int _rc = (call);                  \
+    if (_rc != SCILMM_OK) return _rc;  \
+  } while (0)
+
+// Profiling events of one level: Dev::pev[PEV_PER_LEVEL * l + slot].  The late brackets are recorded on the main stream, the
+// early ones on the level's side stream; consecutive main-stream slots bracket the reduce / cells, k_potrf and k_trsm parts.
+enum ProfEvent {
+  PEV_LATE_BEGIN,     // before the late update items ...
+  PEV_LATE_END,       // ... behind the late dense items
+  PEV_CELLS_END,      // behind the late cells (= before k_potrf)
+  PEV_POTRF_END,      // (= before k_trsm)
+  PEV_LEVEL_END,      // behind k_trsm and the level's shadow
+  PEV_EARLY_BEGIN,    // side stream: before the early update items ...
+  PEV_EARLY_END,      // ... behind the early dense items (before their reduce and cells)
+  PEV_DENSE_E_BEGIN,  // side stream: the early dense items alone
+  PEV_DENSE_E_END,
+  PEV_DENSE_L_BEGIN,  // the late dense items (of a split level: the older sources' only)
+  PEV_DENSE_L_END,
+  PEV_DENSE_N_BEGIN,  // split level: the newest source's items, behind the wait for its arrival
+  PEV_DENSE_N_END,
+  PEV_PER_LEVEL
+};
+
 int finish_factorize(scilmm_factor* fac, int32_t* bad_col);
+
+// One factorization being queued: the steps of run_factorize, in the order it calls them.
+struct Factorization : FactorLaunch {
+  scilmm_symbolic* const sym;
+  const Symbolic& S;
+  const hipStream_t st;  // the main stream
+  const bool prof;
+  const bool dist;       // the dense tail is distributed
+  const size_t half;     // doubles of one scratch half (three for the side streams, the fourth for the main stream)
+  int32_t last_tail_level = -1;
+
+  Factorization(scilmm_factor* f, Dev* d)
+      : FactorLaunch{d, f}, sym(f->sym), S(*f->sym->S), st(d->stream), prof(d->profiling),
+        dist(d->world > 1 && d->dist_first < S.nsuper), half((size_t)d->max_slots * TM * NB) {}
+
+  double* late_scratch() const { return D->scratch + (size_t)3 * half; }
+  int32_t tail_front(int32_t l) const { return dist ? D->tail_of_level[l] : -1; }  // the distributed front of level l
+  bool has_early(int32_t l) const {
+    return D->early_ptr[l + 1] > D->early_ptr[l] || D->cellset[0].level_ptr[l + 1] > D->cellset[0].level_ptr[l] ||
+           D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l];
+  }
+  // (early launches of tail levels are deferred until the k_outside launch has been queued: outside_and_deferred_early)
+  bool deferred(int32_t le) const { return D->outside_on && le >= D->tail_level; }
+  int mark(int32_t l, ProfEvent e, hipStream_t stream) {
+    if (prof) HIPCHK(hipEventRecord(D->pev[(size_t)PEV_PER_LEVEL * l + e], stream));
+    return SCILMM_OK;
+  }
+
+  int prepare_shadow() {
+    // front precision 32: the dense-tail kernel reads an fp32 shadow of the finished tail panels (k_dense_h) -- of the rank's own
+    // panels and of its ring slots when the tail is distributed (same rank-local offsets as L, minus the prelude).  It is
+    // allocated with the first such factorization and kept (zeroed once: the kernel may read a few entries past a panel, into
+    // the next panel's or the slack's, which must be finite); a device without room for it keeps k_dense32 (fp64 operands
+    // rounded while they are staged).  SCILMM_TUNING=1 SCILMM_SHADOW=0: k_dense32.
+    const bool want = D->front_bits == 32 && D->dense_on && read_tuning().shadow;
+    if (want && !fac->L32) {
+      fac->base32 = S.sn_loff[S.dense_first];  // (= the prelude's size: the prelude is replicated and stored first on every rank)
+      const size_t cnt32 = (size_t)(D->nL_local - fac->base32) + 16384;
+      if (hipMalloc((void**)&fac->L32, sizeof(float) * cnt32) != hipSuccess) {
+        (void)hipGetLastError();
+        fac->L32 = nullptr;
+      } else {
+        HIPCHK(hipMemsetAsync(fac->L32, 0, sizeof(float) * cnt32, st));
+      }
+    } else if (!want && fac->L32) {
+      HIPCHK(hipStreamSynchronize(st));
+      (void)hipFree(fac->L32);
+      fac->L32 = nullptr;
+    }
+    return SCILMM_OK;
+  }
+
+  // L = sum_k sigma2[k] A_k on the stored pattern, the status word, and every other stream behind it
+  int assemble(const double* sigma2) {
+    HIPCHK(hipEventRecord(D->ev[0], st));
+    HIPCHK(hipMemsetAsync(fac->L, 0, sizeof(double) * (size_t)std::max<int64_t>(D->nL_local, 1), st));
+    int32_t big = 0x7fffffff;
+    HIPCHK(hipMemcpyAsync(fac->status, &big, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    ValPtrs gen{}, dia{};
+    for (int k = 0; k < S.K; ++k) {
+      ValPtrs& t = S.is_diag[k] ? dia : gen;
+      if (t.count >= 8) {
+        sym->err = "more than 8 matrices of one kind";
+        return SCILMM_ERR_ARG;
+      }
+      t.v[t.count] = D->vals[k];
+      t.s2[t.count] = sigma2[k];
+      t.count++;
+    }
+    if (S.nnz_pattern > 0) {
+      int blocks = (int)std::min<int64_t>((S.nnz_pattern + 255) / 256, 256 * 16);
+      hipLaunchKernelGGL(k_assemble, dim3(blocks), dim3(256), 0, st, S.nnz_pattern, D->v.asm_dst, gen, fac->L);
+      launches++;
+    }
+    if (dia.count > 0 && S.n > 0) {
+      hipLaunchKernelGGL(k_add_diag, dim3((S.n + 255) / 256), dim3(256), 0, st, S.n, D->v.diag_dst, dia, fac->L);
+      launches++;
+    }
+    HIPCHK(hipEventRecord(D->ev[1], st));
+    HIPCHK(hipEventRecord(D->ev_asm, st));
+    HIPCHK(hipStreamWaitEvent(D->side, D->ev_asm, 0));
+    HIPCHK(hipStreamWaitEvent(D->side2, D->ev_asm, 0));
+    if (D->side3) HIPCHK(hipStreamWaitEvent(D->side3, D->ev_asm, 0));
+    if (D->outside_st) HIPCHK(hipStreamWaitEvent(D->outside_st, D->ev_asm, 0));
+    if (dist) {
+      // nothing may land in the ring (or be read-modify-written by a batch) before the storage is cleared and assembled
+      HIPCHK(hipStreamWaitEvent(D->bstream, D->ev_asm, 0));
+      HIPCHK(hipStreamWaitEvent(D->comm, D->ev_asm, 0));
+    }
+    return SCILMM_OK;
+  }
+
+  int prepare_profiling() {
+    D->n_late_split = 0;
+    if (prof && D->pev.size() < (size_t)PEV_PER_LEVEL * S.nlevels) {
+      size_t old = D->pev.size();
+      D->pev.resize((size_t)PEV_PER_LEVEL * S.nlevels, nullptr);
+      for (size_t i = old; i < D->pev.size(); ++i) HIPCHK(hipEventCreate(&D->pev[i]));
+    }
+    if (prof && dist && D->bpev.size() < 2 * D->batch_ev.size()) {
+      size_t old = D->bpev.size();
+      D->bpev.resize(2 * D->batch_ev.size(), nullptr);
+      for (size_t i = old; i < D->bpev.size(); ++i) HIPCHK(hipEventCreate(&D->bpev[i]));
+    }
+    return SCILMM_OK;
+  }
+
+  // Look-ahead: the EARLY part of level l (descendants finished at levels <= l - look_depth - 1) runs on a side stream
+  // while the main stream works through an earlier level's latency-bound tail (late update, cells, potrf, trsm).
+  int early(int32_t l) {
+    const int64_t e0 = D->early_ptr[l], e1 = D->early_ptr[l + 1];
+    if (!has_early(l)) return SCILMM_OK;
+    const int sidx = D->serial_early ? 0 : l % D->nside;
+    hipStream_t sd = sidx == 0 ? D->side : (sidx == 1 ? D->side2 : D->side3);
+    double* scratch = D->scratch + (size_t)sidx * half;
+    // its youngest descendants sit look_depth + 1 levels below
+    if (l >= D->look_depth + 1) HIPCHK(hipStreamWaitEvent(sd, D->lev_ev[2 * (l - D->look_depth - 1)], 0));
+    // tail targets: the atomic contributions of the prelude (k_outside) must have landed before anything else
+    // reads-modifies-writes a tail panel (the event has been recorded: these launches are deferred until it is)
+    if (D->outside_on && l >= D->tail_level && D->out_wait_chunk[(size_t)l] >= 0)
+      HIPCHK(hipStreamWaitEvent(sd, D->out_evs[(size_t)D->out_wait_chunk[(size_t)l]], 0));
+    TRY(mark(l, PEV_EARLY_BEGIN, sd));
+    update(sd, D->d_work_early + e0, e1 - e0, scratch);
+    TRY(mark(l, PEV_DENSE_E_BEGIN, sd));
+    dense(sd, D->d_dwork_e + D->dwork_e_ptr[l], D->dwork_e_ptr[l + 1] - D->dwork_e_ptr[l], scratch);
+    TRY(mark(l, PEV_DENSE_E_END, sd));
+    TRY(mark(l, PEV_EARLY_END, sd));
+    // fold the early partial slabs on the side stream as well: the main stream keeps only its own (rare) ones
+    reduce(sd, D->d_red_tiles_e + D->red_ptr_e[l], D->red_ptr_e[l + 1] - D->red_ptr_e[l], D->d_tile_pslot_e, D->d_tile_pnseg_e, scratch);
+    TRY(cells(sd, 0, l));  // early cells: same stream, after the early MFMA update of the same panels
+    HIPCHK(hipEventRecord(D->lev_ev[2 * l + 1], sd));
+    return SCILMM_OK;
+  }
+
+  // the main stream's waits of level l, then its late update and dense items
+  int late_updates(int32_t l) {
+    double* sh = late_scratch();
+    // (progressive k_outside: this level's tail panel needs the chunks that reach it, not the whole launch sequence)
+    if (D->outside_on && l >= D->tail_level && D->out_wait_chunk[(size_t)l] >= 0 &&
+        (l == D->tail_level || D->out_wait_chunk[(size_t)l] != D->out_wait_chunk[(size_t)l - 1]))
+      HIPCHK(hipStreamWaitEvent(st, D->out_evs[(size_t)D->out_wait_chunk[(size_t)l]], 0));
+    const int32_t tf = tail_front(l), Wg = D->dist_Wg;
+    const int32_t jj = tf >= 0 ? tf - D->dist_first : -1, grp = tf >= 0 ? jj / Wg : -1;
+    const bool own_tail = tf >= 0 && D->keep_front[tf];
+    // look-ahead split of an own tail panel's late dense items: the older sources' first, the newest source's behind its arrival
+    const bool split_late = own_tail && D->dwork_l_mid[(size_t)l] < D->dwork_l_ptr[l + 1];
+    if (has_early(l)) HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * l + 1], 0));
+    if (own_tail) {
+      // own tail panel: every batch up to group grp - 2 has been applied to it; its late sources -- the panels of the
+      // group before and of its own group so far -- have arrived (own ones: their level event)
+      if (grp >= 2) HIPCHK(hipStreamWaitEvent(st, D->batch_ev[grp - 2], 0));
+      // (look-ahead split: the wait for the NEWEST source, panel jj - 1, comes after the launch of the older sources' items)
+      const int32_t q_end = split_late ? jj - 1 : jj;
+      for (int32_t q = std::max(0, (grp - 1) * Wg); q < q_end; ++q) HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * S.sn_level[D->dist_first + q]], 0));
+    }
+    TRY(mark(l, PEV_LATE_BEGIN, st));
+    update(st, D->d_work + D->work_ptr[l], D->work_ptr[l + 1] - D->work_ptr[l], sh);
+    TRY(mark(l, PEV_DENSE_L_BEGIN, st));
+    dense(st, D->d_dwork_l + D->dwork_l_ptr[l], (split_late ? D->dwork_l_mid[(size_t)l] : D->dwork_l_ptr[l + 1]) - D->dwork_l_ptr[l], sh);
+    TRY(mark(l, PEV_DENSE_L_END, st));
+    if (split_late) {
+      // the older sources' items are queued (they run while panel jj - 1 is still on its way); now its arrival, then its items
+      HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * S.sn_level[D->dist_first + jj - 1]], 0));
+      TRY(mark(l, PEV_DENSE_N_BEGIN, st));
+      dense(st, D->d_dwork_l + D->dwork_l_mid[(size_t)l], D->dwork_l_ptr[l + 1] - D->dwork_l_mid[(size_t)l], sh);
+      TRY(mark(l, PEV_DENSE_N_END, st));
+      D->n_late_split++;
+    }
+    return mark(l, PEV_LATE_END, st);
+  }
+
+  // late cells, k_potrf, k_trsm and the fp32 shadow of the level's fronts
+  int factor_panel(int32_t l) {
+    const int64_t t0 = D->lv_tile_ptr[l], t1 = D->lv_tile_ptr[l + 1];
+    const int32_t f0 = D->lv_ptr[l], f1 = D->lv_ptr[l + 1];
+    const double* sh = late_scratch();
+    // (the late slabs are folded by k_potrf / k_trsm on load: no k_reduce launch on the main stream's chain)
+    TRY(cells(st, 1, l));
+    TRY(mark(l, PEV_CELLS_END, st));
+    if (f1 > f0) {
+      const size_t sm_potrf = sizeof(double) * (size_t)((NB / 2) * (NB + 1) + NJB * 16 * 17 + 32);
+      hipLaunchKernelGGL(k_potrf, dim3((unsigned)(f1 - f0)), dim3(256), sm_potrf, st, D->v, D->d_level_fronts + f0, fac->L,
+                         fac->invD, fac->logd, fac->status, (const int32_t*)D->d_tile_pslot, (const int32_t*)D->d_tile_pnseg, sh);
+      launches++;
+    }
+    TRY(mark(l, PEV_POTRF_END, st));
+    trsm(st, D->d_level_tiles + t0, t1 - t0, sh);
+    if (fac->L32) {
+      // front precision 32: the level's finished tail panel -> its fp32 shadow, before the level's event (the look-ahead
+      // launches of later targets read the shadow only)
+      for (int32_t q = f0; q < f1; ++q) {
+        const int32_t fr = D->lv_fronts[(size_t)q];  // (the level's fronts THIS rank holds: another rank's panel is shadowed when it arrives: broadcast_tail)
+        if (fr < S.dense_first || !D->keep_front[fr]) continue;
+        shadow(st, fr, S.sn_loff[fr + 1] - S.sn_loff[fr]);
+      }
+    }
+    return mark(l, PEV_LEVEL_END, st);
+  }
+
+  void shadow(hipStream_t stream, int32_t fr, int64_t cnt) {
+    hipLaunchKernelGGL(k_shadow, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, stream,
+                       (const double*)(fac->L + D->loff[fr]), fac->L32 + (D->loff[fr] - fac->base32), cnt);
+    launches++;
+  }
+
+  // Level with a distributed tail panel: the owner's panel (+ inverse diagonal block + log-sum) goes to every rank -- into
+  // the receiver's ring slot.  The level is complete (lev_ev) when the panel has arrived AND this rank's own kernels of
+  // the level (its prelude fronts) have finished.
+  int broadcast_tail(int32_t l) {
+    const int32_t tf = tail_front(l), jj = tf - D->dist_first;
+    const int32_t root = jj % D->world;
+    HIPCHK(hipEventRecord(D->done_ev[l], st));
+    HIPCHK(hipStreamWaitEvent(D->comm, D->done_ev[l], 0));
+    if (!D->keep_front[tf]) {
+      // ring re-use: the slot's previous occupant (panel jj - G, group gd) must have been consumed -- by its batch and by
+      // the late updates of this rank's targets of groups gd and gd + 1
+      const int32_t gd = (jj - D->dist_G) / D->dist_Wg;
+      if (jj >= D->dist_G) {
+        HIPCHK(hipStreamWaitEvent(D->comm, D->batch_ev[gd], 0));
+        for (int32_t q = std::min<int32_t>(gd + 1, (int32_t)D->last_own_level.size() - 1); q >= 0; --q)
+          if (D->last_own_level[q] >= 0) {
+            HIPCHK(hipStreamWaitEvent(D->comm, D->done_ev[D->last_own_level[q]], 0));
+            break;
+          }
+      }
+    }
+    const int64_t pm = S.sn_rowptr[tf + 1] - S.sn_rowptr[tf], pw = S.sn_start[tf + 1] - S.sn_start[tf];
+    int rcm = sym->comm_fn(sym->comm_ctx, 0, 0, D->loff[tf], pm * pw, root);
+    if (rcm == 0) rcm = sym->comm_fn(sym->comm_ctx, 0, 1, S.inv_off[tf], pw * pw, root);
+    if (rcm == 0) rcm = sym->comm_fn(sym->comm_ctx, 0, 2, tf, 1, root);
+    if (rcm != 0) {
+      sym->err = "multi-GPU: the communication callback failed";
+      return SCILMM_ERR_DEVICE;
+    }
+    // front precision 32: the arrived panel's fp32 shadow, on the communication stream behind the broadcast
+    if (fac->L32 && !D->keep_front[tf]) shadow(D->comm, tf, pm * pw);
+    HIPCHK(hipEventRecord(D->lev_ev[2 * l], D->comm));
+    last_tail_level = l;
+    return SCILMM_OK;
+  }
+
+  // source group grp is complete on this rank: its batch (every own target at least two groups ahead), on the batches' stream
+  int batch(int32_t grp) {
+    hipStream_t bs = D->bstream;
+    const int32_t q_end = std::min((grp + 1) * D->dist_Wg, S.nsuper - D->dist_first);
+    for (int32_t q = grp * D->dist_Wg; q < q_end; ++q) HIPCHK(hipStreamWaitEvent(bs, D->lev_ev[2 * S.sn_level[D->dist_first + q]], 0));
+    if (D->outside_on) HIPCHK(hipStreamWaitEvent(bs, D->out_evs.back(), 0));  // (a batch writes targets up to the last panel)
+    if (prof) HIPCHK(hipEventRecord(D->bpev[2 * (size_t)grp], bs));
+    dense(bs, D->d_dwork_b + D->dbatch_ptr[grp], D->dbatch_ptr[grp + 1] - D->dbatch_ptr[grp], nullptr);
+    if (prof) HIPCHK(hipEventRecord(D->bpev[2 * (size_t)grp + 1], bs));
+    HIPCHK(hipEventRecord(D->batch_ev[grp], bs));
+    return SCILMM_OK;
+  }
+
+  // Every prelude front below the tail's first level is final (l = tail_level - 1): its contribution to the tail, in ITS
+  // coordinates, with atomic subtraction (k_outside), a chunk of items and an event at a time; nothing else touches a tail
+  // panel meanwhile.  Then the early launches of the tail levels that were held back for it.
+  int outside_and_deferred_early(int32_t l) {
+    HIPCHK(hipStreamWaitEvent(D->outside_st, D->lev_ev[2 * l], 0));
+    for (size_t og = 0; og + 1 < D->ochunk_ptr.size(); ++og) {
+      outside(D->outside_st, (const OutsideWork*)D->d_owork + D->ochunk_ptr[og], D->ochunk_ptr[og + 1] - D->ochunk_ptr[og]);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(D->out_evs[og], D->outside_st));
+    }
+    for (int32_t le = std::max(D->tail_level, 1); le <= l + D->look_depth && le < S.nlevels; ++le) TRY(early(le));
+    return SCILMM_OK;
+  }
+
+  // Distributed tail: the main stream joins the communication and batch streams.  The status word (first non-positive pivot,
+  // or "none") is written by the owner of the failing panel only: every rank takes the minimum, so that all of them report
+  // SCILMM_ERR_NOT_PD together
+  int exchange_status() {
+    if (last_tail_level >= 0) HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * last_tail_level], 0));
+    if (!D->batch_ev.empty()) HIPCHK(hipStreamWaitEvent(st, D->batch_ev.back(), 0));
+    hipLaunchKernelGGL(k_status_pack, dim3(1), dim3(1), 0, st, (const int32_t*)fac->status, fac->logd + S.nsuper);
+    HIPCHK(hipEventRecord(D->ev_x0, st));
+    HIPCHK(hipStreamWaitEvent(D->comm, D->ev_x0, 0));
+    if (sym->comm_fn(sym->comm_ctx, 2, 2, S.nsuper, 1, 0) != 0) {
+      sym->err = "multi-GPU: the communication callback failed";
+      return SCILMM_ERR_DEVICE;
+    }
+    HIPCHK(hipEventRecord(D->ev_x1, D->comm));
+    HIPCHK(hipStreamWaitEvent(st, D->ev_x1, 0));
+    hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(1), 0, st, (const double*)(fac->logd + S.nsuper), fac->status);
+    return SCILMM_OK;
+  }
+};
 
 int run_factorize(scilmm_factor* fac, const double* sigma2, int32_t* bad_col, bool wait = true) {
   scilmm_symbolic* sym = fac->sym;
@@ -116,446 +438,100 @@ int run_factorize(scilmm_factor* fac, const double* sigma2, int32_t* bad_col, bo
     sym->err = "multi-GPU: the factor must live in caller-owned storage (scilmm_factor_create_external)";
     return SCILMM_ERR_STATE;
   }
-  {
-    int stc = set_attrs(sym, D);
-    if (stc != SCILMM_OK) return stc;
-  }
-  const bool dist = D->world > 1 && D->dist_first < S.nsuper;
-  const size_t sm_upd = sizeof(double) * (size_t)(2 * KC * LDA + 2 * KC * LDB) + sizeof(int32_t) * TM;
-  const size_t sm_potrf = sizeof(double) * (size_t)((NB / 2) * (NB + 1) + NJB * 16 * 17 + 32);
-  hipStream_t st = D->stream;
-  int64_t launches = 0;
-  {
-    // front precision 32: the dense-tail kernel reads an fp32 shadow of the finished tail panels (k_dense_h) -- of the rank's own
-    // panels and of its ring slots when the tail is distributed (same rank-local offsets as L, minus the prelude).  It is
-    // allocated with the first such factorization and kept (zeroed once: the kernel may read a few entries past a panel, into
-    // the next panel's or the slack's, which must be finite); a device without room for it keeps k_dense32 (fp64 operands
-    // rounded while they are staged).  SCILMM_TUNING=1 SCILMM_SHADOW=0: k_dense32.
-    const bool want = D->front_bits == 32 && D->dense_on && read_tuning().shadow;
-    if (want && !fac->L32) {
-      fac->base32 = S.sn_loff[S.dense_first];  // (= the prelude's size: the prelude is replicated and stored first on every rank)
-      const size_t cnt32 = (size_t)(D->nL_local - fac->base32) + 16384;
-      if (hipMalloc((void**)&fac->L32, sizeof(float) * cnt32) != hipSuccess) {
-        (void)hipGetLastError();
-        fac->L32 = nullptr;
-      } else {
-        HIPCHK(hipMemsetAsync(fac->L32, 0, sizeof(float) * cnt32, st));
-      }
-    } else if (!want && fac->L32) {
-      HIPCHK(hipStreamSynchronize(st));
-      (void)hipFree(fac->L32);
-      fac->L32 = nullptr;
-    }
-  }
-  HIPCHK(hipEventRecord(D->ev[0], st));
-  HIPCHK(hipMemsetAsync(fac->L, 0, sizeof(double) * (size_t)std::max<int64_t>(D->nL_local, 1), st));
-  int32_t big = 0x7fffffff;
-  HIPCHK(hipMemcpyAsync(fac->status, &big, sizeof(int32_t), hipMemcpyHostToDevice, st));
-  ValPtrs gen{}, dia{};
-  for (int k = 0; k < S.K; ++k) {
-    ValPtrs& t = S.is_diag[k] ? dia : gen;
-    if (t.count >= 8) {
-      sym->err = "more than 8 matrices of one kind";
-      return SCILMM_ERR_ARG;
-    }
-    t.v[t.count] = D->vals[k];
-    t.s2[t.count] = sigma2[k];
-    t.count++;
-  }
-  if (S.nnz_pattern > 0) {
-    int blocks = (int)std::min<int64_t>((S.nnz_pattern + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(k_assemble, dim3(blocks), dim3(256), 0, st, S.nnz_pattern, D->v.asm_dst, gen, fac->L);
-    launches++;
-  }
-  if (dia.count > 0 && S.n > 0) {
-    hipLaunchKernelGGL(k_add_diag, dim3((S.n + 255) / 256), dim3(256), 0, st, S.n, D->v.diag_dst, dia, fac->L);
-    launches++;
-  }
-  HIPCHK(hipEventRecord(D->ev[1], st));
-  HIPCHK(hipEventRecord(D->ev_asm, st));
-  HIPCHK(hipStreamWaitEvent(D->side, D->ev_asm, 0));
-  HIPCHK(hipStreamWaitEvent(D->side2, D->ev_asm, 0));
-  if (D->side3) HIPCHK(hipStreamWaitEvent(D->side3, D->ev_asm, 0));
-  if (D->outside_st) HIPCHK(hipStreamWaitEvent(D->outside_st, D->ev_asm, 0));
-  if (dist) {
-    // nothing may land in the ring (or be read-modify-written by a batch) before the storage is cleared and assembled
-    HIPCHK(hipStreamWaitEvent(D->bstream, D->ev_asm, 0));
-    HIPCHK(hipStreamWaitEvent(D->comm, D->ev_asm, 0));
-  }
-  const bool prof = D->profiling;
-  constexpr int PE = 14;  // profiling events per level
-  D->n_late_split = 0;
-  if (prof && D->pev.size() < (size_t)PE * S.nlevels) {
-    size_t old = D->pev.size();
-    D->pev.resize((size_t)PE * S.nlevels, nullptr);
-    for (size_t i = old; i < D->pev.size(); ++i) HIPCHK(hipEventCreate(&D->pev[i]));
-  }
-  if (prof && dist && D->bpev.size() < 2 * D->batch_ev.size()) {
-    size_t old = D->bpev.size();
-    D->bpev.resize(2 * D->batch_ev.size(), nullptr);
-    for (size_t i = old; i < D->bpev.size(); ++i) HIPCHK(hipEventCreate(&D->bpev[i]));
-  }
-  // A dispatch counts WORK-ITEMS in 32 bits: cnt workgroups of `threads` threads must stay below 2^32 of them.
-  // Every launch helper below cuts its grid at max_groups(threads) workgroups (k_outside was the only
-  // chunked launch; the 1M plan has single launches of several million workgroups).
-  auto max_groups = [](unsigned threads) -> int64_t { return (int64_t)(((uint64_t)1 << 32) / threads) - 1; };
-  auto launch_update = [&](hipStream_t stream, const UpdWork* work, int64_t cnt, double* scratch_half) {
-#ifdef SCILMM_DIAG
-    if (D->ablate == 4) return;  // timing ablation: no explicit MFMA update items at all (WRONG numbers)
-#endif
-    for (int64_t o = 0; o < cnt; o += max_groups(UPD_THREADS)) {
-      const unsigned c = (unsigned)std::min<int64_t>(cnt - o, max_groups(UPD_THREADS));
-      if (D->use_mfma)
-        hipLaunchKernelGGL((k_update2<true>), dim3(c), dim3(UPD_THREADS), sm_upd, stream, D->v, work + o, D->d_combos, fac->L, scratch_half);
-      else
-        hipLaunchKernelGGL((k_update2<false>), dim3(c), dim3(UPD_THREADS), sm_upd, stream, D->v, work + o, D->d_combos, fac->L, scratch_half);
-      launches++;
-    }
-  };
-  auto launch_dense = [&](hipStream_t stream, const DenseWork* dw, int64_t cnt, double* scratch_half) {
-    for (int64_t o = 0; o < cnt; o += max_groups(1024)) {
-      const unsigned c = (unsigned)std::min<int64_t>(cnt - o, max_groups(1024));  // (k_dense_h launches 2 c workgroups of 512)
-      if (D->front_bits == 32 && fac->L32)
-        // (two workgroups per work item: one per 128-row tile)
-        hipLaunchKernelGGL(k_dense_h, dim3(2 * c), dim3(512), dense_h_lds, stream, D->v, S.dense_first, dw + o, fac->L, (const float*)fac->L32,
-                           fac->base32, scratch_half, (const float*)D->d_zeros);
-      else if (D->front_bits == 32)
-        hipLaunchKernelGGL(k_dense32, dim3(c), dim3(512), sizeof(float) * (size_t)(2 * KC * LDA2F + 2 * KC * LDBF), stream, D->v,
-                           S.dense_first, dw + o, fac->L, scratch_half);
-      else
-        hipLaunchKernelGGL(k_dense_b, dim3(c), dim3(512), sizeof(double) * (size_t)(2 * KBA * LDB), stream, D->v, S.dense_first, dw + o,
-                           fac->L, scratch_half, (const double*)D->d_zeros);
-      launches++;
-    }
-  };
-  const size_t half = (size_t)D->max_slots * TM * NB;
-  auto launch_cells = [&](hipStream_t stream, int which, int32_t l) {
-    const Dev::CellSet& CS = D->cellset[which];
-    const int64_t u0 = CS.level_ptr[l], u1 = CS.level_ptr[l + 1];
-    if (u1 <= u0) return;
-#ifdef SCILMM_DIAG
-    if (D->ablate == 5) return;  // timing ablation: no cell-path updates (WRONG numbers)
-#endif
-    const int64_t nshort = CS.level_short[l], nlong = (u1 - u0) - nshort;
-    const int64_t nblk = (nshort + 255) / 256 + (nlong + 3) / 4;
-    if (nblk > max_groups(256)) {  // 2^24 workgroups = 4e9 cells of one level: beyond any plan the cell limit admits
-      sym->err = "cell plan: one level has more target cells than a dispatch can hold";
-      return;
-    }
-    hipLaunchKernelGGL(k_sparse_cells, dim3((unsigned)nblk), dim3(256), 0, stream, u0, nshort, u1 - u0, (const int64_t*)CS.dst,
-                       (const int64_t*)CS.grp, (const int64_t*)CS.srct, (const int64_t*)CS.srcq, (const int32_t*)CS.md,
-                       (const int32_t*)CS.wd, fac->L);
-    launches++;
-  };
-  auto launch_reduce = [&](hipStream_t stream, const int32_t* tiles, int64_t cnt, const int32_t* pslot, const int32_t* pnseg,
-                           const double* slabs) {
-    const int64_t per = max_groups(128) / (NB / 4);  // tiles per dispatch
-    for (int64_t o = 0; o < cnt; o += per) {
-      const int64_t c = std::min(cnt - o, per);
-      hipLaunchKernelGGL(k_reduce, dim3((unsigned)((NB / 4) * c)), dim3(128), 0, stream, D->v, tiles + o, pslot, pnseg, slabs, fac->L);
-      launches++;
-    }
-  };
-  auto has_early = [&](int32_t l) -> bool {
-    return D->early_ptr[l + 1] > D->early_ptr[l] || D->cellset[0].level_ptr[l + 1] > D->cellset[0].level_ptr[l] ||
-           D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l];
-  };
-  // Look-ahead: the EARLY part of level l+1 (descendants finished at levels <= l-1) runs on the side stream
-  // while the main stream works through level l's latency-bound tail (late update, reduce, cells, potrf, trsm).
-  auto launch_early = [&](int32_t l) -> int {
-    const int64_t e0 = D->early_ptr[l], e1 = D->early_ptr[l + 1];
-    if (!has_early(l)) return SCILMM_OK;
-    const int sidx = D->serial_early ? 0 : l % D->nside;
-    hipStream_t sd = sidx == 0 ? D->side : (sidx == 1 ? D->side2 : D->side3);
-    // its youngest descendants sit look_depth + 1 levels below
-    if (l >= D->look_depth + 1) HIPCHK(hipStreamWaitEvent(sd, D->lev_ev[2 * (l - D->look_depth - 1)], 0));
-    // tail targets: the atomic contributions of the prelude (k_outside) must have landed before anything else
-    // reads-modifies-writes a tail panel (the event has been recorded: these launches are deferred until it is)
-    if (D->outside_on && l >= D->tail_level && D->out_wait_chunk[(size_t)l] >= 0)
-      HIPCHK(hipStreamWaitEvent(sd, D->out_evs[(size_t)D->out_wait_chunk[(size_t)l]], 0));
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 5], sd));
-    if (e1 > e0) launch_update(sd, D->d_work_early + e0, e1 - e0, D->scratch + (size_t)sidx * half);
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 8], sd));
-    launch_dense(sd, D->d_dwork_e + D->dwork_e_ptr[l], D->dwork_e_ptr[l + 1] - D->dwork_e_ptr[l], D->scratch + (size_t)sidx * half);
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 9], sd));
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 6], sd));
-    // fold the early partial slabs on the side stream as well: the main stream keeps only its own (rare) ones
-    launch_reduce(sd, D->d_red_tiles_e + D->red_ptr_e[l], D->red_ptr_e[l + 1] - D->red_ptr_e[l], D->d_tile_pslot_e, D->d_tile_pnseg_e,
-                  (const double*)(D->scratch + (size_t)sidx * half));
-    launch_cells(sd, 0, l);  // early cells: same stream, after the early MFMA update of the same panels
-    HIPCHK(hipEventRecord(D->lev_ev[2 * l + 1], sd));
-    return SCILMM_OK;
-  };
-  // (early launches of tail levels are deferred until the k_outside launch has been queued: see below)
-  auto deferred = [&](int32_t le) -> bool { return D->outside_on && le >= D->tail_level; };
-  for (int32_t l = 1; l <= D->look_depth && l < S.nlevels; ++l) {
-    if (deferred(l)) continue;
-    int rc = launch_early(l);
-    if (rc != SCILMM_OK) return rc;
-  }
-  const int32_t nT = S.nsuper - D->dist_first, Wg = D->dist_Wg;
-  int32_t last_tail_level = -1;
+  TRY(set_attrs(sym, D));
+  Factorization F(fac, D);
+  TRY(F.prepare_shadow());
+  TRY(F.assemble(sigma2));
+  TRY(F.prepare_profiling());
+  for (int32_t l = 1; l <= D->look_depth && l < S.nlevels; ++l)
+    if (!F.deferred(l)) TRY(F.early(l));
   for (int32_t l = 0; l < S.nlevels; ++l) {
-    const int64_t t0 = D->lv_tile_ptr[l], t1 = D->lv_tile_ptr[l + 1];
-    const int32_t f0 = D->lv_ptr[l], f1 = D->lv_ptr[l + 1];
-    double* sh = D->scratch + (size_t)3 * half;
     // early(l + depth) may start as soon as level l-1 is finished: issue it before this level's own kernels
-    if (l >= 1 && l + D->look_depth < S.nlevels && !(l < D->tail_level && deferred(l + D->look_depth))) {
-      int rc = launch_early(l + D->look_depth);
-      if (rc != SCILMM_OK) return rc;
-    }
-    // (progressive k_outside: this level's tail panel needs the chunks that reach it, not the whole launch sequence)
-    if (D->outside_on && l >= D->tail_level && D->out_wait_chunk[(size_t)l] >= 0 &&
-        (l == D->tail_level || D->out_wait_chunk[(size_t)l] != D->out_wait_chunk[(size_t)l - 1]))
-      HIPCHK(hipStreamWaitEvent(st, D->out_evs[(size_t)D->out_wait_chunk[(size_t)l]], 0));
-    const int64_t w0 = D->work_ptr[l], w1 = D->work_ptr[l + 1];
-    const int32_t tf = dist ? D->tail_of_level[l] : -1;  // the distributed front of this level
-    const int32_t jj = tf >= 0 ? tf - D->dist_first : -1, grp = tf >= 0 ? jj / Wg : -1;
-    if (has_early(l)) HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * l + 1], 0));
-    if (tf >= 0 && D->keep_front[tf]) {
-      // own tail panel: every batch up to group grp - 2 has been applied to it; its late sources -- the panels of the
-      // group before and of its own group so far -- have arrived (own ones: their level event)
-      if (grp >= 2) HIPCHK(hipStreamWaitEvent(st, D->batch_ev[grp - 2], 0));
-      // (look-ahead split: the wait for the NEWEST source, panel jj - 1, comes after the launch of the older sources' items)
-      const int32_t q_end = D->dwork_l_mid[(size_t)l] < D->dwork_l_ptr[l + 1] ? jj - 1 : jj;
-      for (int32_t q = std::max(0, (grp - 1) * Wg); q < q_end; ++q) HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * S.sn_level[D->dist_first + q]], 0));
-    }
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 0], st));
-    if (w1 > w0) launch_update(st, D->d_work + w0, w1 - w0, sh);
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 10], st));
-    const bool split_late = tf >= 0 && D->keep_front[tf] && D->dwork_l_mid[(size_t)l] < D->dwork_l_ptr[l + 1];
-    launch_dense(st, D->d_dwork_l + D->dwork_l_ptr[l], (split_late ? D->dwork_l_mid[(size_t)l] : D->dwork_l_ptr[l + 1]) - D->dwork_l_ptr[l], sh);
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 11], st));
-    if (split_late) {
-      // the older sources' items are queued (they run while panel jj - 1 is still on its way); now its arrival, then its items
-      HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * S.sn_level[D->dist_first + jj - 1]], 0));
-      if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 12], st));
-      launch_dense(st, D->d_dwork_l + D->dwork_l_mid[(size_t)l], D->dwork_l_ptr[l + 1] - D->dwork_l_mid[(size_t)l], sh);
-      if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 13], st));
-      D->n_late_split++;
-    }
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 1], st));
-    // (the late slabs are folded by k_potrf / k_trsm on load: no k_reduce launch on the main stream's chain)
-    launch_cells(st, 1, l);
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 2], st));
-    if (f1 > f0) {
-      hipLaunchKernelGGL(k_potrf, dim3((unsigned)(f1 - f0)), dim3(256), sm_potrf, st, D->v, D->d_level_fronts + f0, fac->L,
-                         fac->invD, fac->logd, fac->status, (const int32_t*)D->d_tile_pslot, (const int32_t*)D->d_tile_pnseg,
-                         (const double*)sh);
-      launches++;
-    }
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 3], st));
-    if (t1 > t0) {
-      if (D->use_mfma && D->trsm_lite && (t1 - t0) < ((int64_t)1 << 29))
-        // (four workgroups of 32 rows per tile, register-light and LDS-free: starts beside the resident update kernel)
-        hipLaunchKernelGGL(k_trsm_lite, dim3((unsigned)(4 * (t1 - t0))), dim3(256), 0, st, D->v, D->d_level_tiles + t0, fac->L, fac->invD,
-                           (const int32_t*)D->d_tile_pslot, (const int32_t*)D->d_tile_pnseg, (const double*)sh);
-      else if (D->use_mfma)
-        hipLaunchKernelGGL(k_trsm<true>, dim3((unsigned)(t1 - t0)), dim3(256), 0, st, D->v, D->d_level_tiles + t0, fac->L, fac->invD,
-                           (const int32_t*)D->d_tile_pslot, (const int32_t*)D->d_tile_pnseg, (const double*)sh);
-      else
-        hipLaunchKernelGGL(k_trsm<false>, dim3((unsigned)(t1 - t0)), dim3(256), 0, st, D->v, D->d_level_tiles + t0, fac->L, fac->invD,
-                           (const int32_t*)D->d_tile_pslot, (const int32_t*)D->d_tile_pnseg, (const double*)sh);
-      launches++;
-    }
-    if (fac->L32) {
-      // front precision 32: the level's finished tail panel -> its fp32 shadow, before the level's event (the look-ahead
-      // launches of later targets read the shadow only)
-      for (int32_t q = f0; q < f1; ++q) {
-        const int32_t fr = D->lv_fronts[(size_t)q];  // (the level's fronts THIS rank holds: another rank's panel is shadowed when it arrives, below)
-        if (fr < S.dense_first || !D->keep_front[fr]) continue;
-        const int64_t cnt = S.sn_loff[fr + 1] - S.sn_loff[fr];
-        hipLaunchKernelGGL(k_shadow, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, st,
-                           (const double*)(fac->L + D->loff[fr]), fac->L32 + (D->loff[fr] - fac->base32), cnt);
-        launches++;
-      }
-    }
-    if (prof) HIPCHK(hipEventRecord(D->pev[PE * l + 4], st));
+    const int32_t le = l + D->look_depth;
+    if (l >= 1 && le < S.nlevels && !(l < D->tail_level && F.deferred(le))) TRY(F.early(le));
+    TRY(F.late_updates(l));
+    TRY(F.factor_panel(l));
+    const int32_t tf = F.tail_front(l);
     if (tf < 0) {
-      HIPCHK(hipEventRecord(D->lev_ev[2 * l], st));
+      HIPCHK(hipEventRecord(D->lev_ev[2 * l], F.st));
     } else {
-      // ---- level with a distributed tail panel: the owner's panel (+ inverse diagonal block + log-sum) goes to every
-      //      rank -- into the receiver's ring slot.  The level is complete (lev_ev) when the panel has arrived AND this
-      //      rank's own kernels of the level (its prelude fronts) have finished.
-      const int32_t root = jj % D->world;
-      HIPCHK(hipEventRecord(D->done_ev[l], st));
-      HIPCHK(hipStreamWaitEvent(D->comm, D->done_ev[l], 0));
-      if (!D->keep_front[tf]) {
-        // ring re-use: the slot's previous occupant (panel jj - G, group gd) must have been consumed -- by its batch and by
-        // the late updates of this rank's targets of groups gd and gd + 1
-        const int32_t gd = (jj - D->dist_G) / Wg;
-        if (jj >= D->dist_G) {
-          HIPCHK(hipStreamWaitEvent(D->comm, D->batch_ev[gd], 0));
-          for (int32_t q = std::min<int32_t>(gd + 1, (int32_t)D->last_own_level.size() - 1); q >= 0; --q)
-            if (D->last_own_level[q] >= 0) {
-              HIPCHK(hipStreamWaitEvent(D->comm, D->done_ev[D->last_own_level[q]], 0));
-              break;
-            }
-        }
-      }
-      const int64_t pm = S.sn_rowptr[tf + 1] - S.sn_rowptr[tf], pw = S.sn_start[tf + 1] - S.sn_start[tf];
-      int rcm = sym->comm_fn(sym->comm_ctx, 0, 0, D->loff[tf], pm * pw, root);
-      if (rcm == 0) rcm = sym->comm_fn(sym->comm_ctx, 0, 1, S.inv_off[tf], pw * pw, root);
-      if (rcm == 0) rcm = sym->comm_fn(sym->comm_ctx, 0, 2, tf, 1, root);
-      if (rcm != 0) {
-        sym->err = "multi-GPU: the communication callback failed";
-        return SCILMM_ERR_DEVICE;
-      }
-      if (fac->L32 && !D->keep_front[tf]) {
-        // front precision 32: the arrived panel's fp32 shadow, on the communication stream behind the broadcast
-        hipLaunchKernelGGL(k_shadow, dim3((unsigned)std::min<int64_t>((pm * pw + 255) / 256, 8192)), dim3(256), 0, D->comm,
-                           (const double*)(fac->L + D->loff[tf]), fac->L32 + (D->loff[tf] - fac->base32), pm * pw);
-        launches++;
-      }
-      HIPCHK(hipEventRecord(D->lev_ev[2 * l], D->comm));
-      last_tail_level = l;
-      if ((jj + 1) % Wg == 0 || jj == nT - 1) {
-        // ---- source group grp is complete on this rank: its batch (every own target at least two groups ahead)
-        hipStream_t bs = D->bstream;
-        for (int32_t q = grp * Wg; q <= jj; ++q) HIPCHK(hipStreamWaitEvent(bs, D->lev_ev[2 * S.sn_level[D->dist_first + q]], 0));
-        if (D->outside_on) HIPCHK(hipStreamWaitEvent(bs, D->out_evs.back(), 0));  // (a batch writes targets up to the last panel)
-        if (prof) HIPCHK(hipEventRecord(D->bpev[2 * (size_t)grp], bs));
-        launch_dense(bs, D->d_dwork_b + D->dbatch_ptr[grp], D->dbatch_ptr[grp + 1] - D->dbatch_ptr[grp], nullptr);
-        if (prof) HIPCHK(hipEventRecord(D->bpev[2 * (size_t)grp + 1], bs));
-        HIPCHK(hipEventRecord(D->batch_ev[grp], bs));
-      }
+      TRY(F.broadcast_tail(l));
+      const int32_t jj = tf - D->dist_first;
+      if ((jj + 1) % D->dist_Wg == 0 || jj == S.nsuper - D->dist_first - 1) TRY(F.batch(jj / D->dist_Wg));
     }
-    if (D->outside_on && l == D->tail_level - 1) {
-      // ---- every prelude front below the tail's first level is final: its contribution to the tail, in ITS
-      //      coordinates, with atomic subtraction (k_outside); nothing else touches a tail panel meanwhile
-      HIPCHK(hipStreamWaitEvent(D->outside_st, D->lev_ev[2 * l], 0));
-      for (size_t og = 0; og + 1 < D->ochunk_ptr.size(); ++og) {
-      for (int64_t o0 = D->ochunk_ptr[og]; o0 < D->ochunk_ptr[og + 1]; o0 += max_groups(256)) {
-        const unsigned cnt = (unsigned)std::min<int64_t>(max_groups(256), D->ochunk_ptr[og + 1] - o0);
-        const OutsideWork* ow = (const OutsideWork*)D->d_owork + o0;
-#ifdef SCILMM_DIAG
-        if (D->ablate == 6)  // timing ablations: no scatter / plain stores (WRONG numbers)
-          hipLaunchKernelGGL((k_outside<true, 1>), dim3(cnt), dim3(256), 0, D->outside_st, D->v, S.dense_first, ow,
-                             (const int32_t*)D->d_tail_front, (const uint8_t*)D->d_keep_front, (const int32_t*)D->d_grp_next,
-                             (const int32_t*)D->d_grp_t0, fac->L);
-        else if (D->ablate == 7)
-          hipLaunchKernelGGL((k_outside<true, 2>), dim3(cnt), dim3(256), 0, D->outside_st, D->v, S.dense_first, ow,
-                             (const int32_t*)D->d_tail_front, (const uint8_t*)D->d_keep_front, (const int32_t*)D->d_grp_next,
-                             (const int32_t*)D->d_grp_t0, fac->L);
-        else
-#endif
-        if (D->use_mfma)
-          hipLaunchKernelGGL(k_outside<true>, dim3(cnt), dim3(256), 0, D->outside_st, D->v, S.dense_first, ow,
-                             (const int32_t*)D->d_tail_front, (const uint8_t*)D->d_keep_front, (const int32_t*)D->d_grp_next,
-                             (const int32_t*)D->d_grp_t0, fac->L);
-        else
-          hipLaunchKernelGGL(k_outside<false>, dim3(cnt), dim3(256), 0, D->outside_st, D->v, S.dense_first, ow,
-                             (const int32_t*)D->d_tail_front, (const uint8_t*)D->d_keep_front, (const int32_t*)D->d_grp_next,
-                             (const int32_t*)D->d_grp_t0, fac->L);
-        HIPCHK(hipGetLastError());
-        launches++;
-        D->n_float_atomic++;
-      }
-      HIPCHK(hipEventRecord(D->out_evs[og], D->outside_st));
-      }
-      for (int32_t le = D->tail_level; le <= l + D->look_depth && le < S.nlevels; ++le) {
-        if (le < 1) continue;
-        int rc = launch_early(le);
-        if (rc != SCILMM_OK) return rc;
-      }
-    }
+    if (D->outside_on && l == D->tail_level - 1) TRY(F.outside_and_deferred_early(l));
   }
-  if (!sym->err.empty() && sym->err.rfind("cell plan:", 0) == 0) return SCILMM_ERR_ARG;
-  if (dist) {
-    if (last_tail_level >= 0) HIPCHK(hipStreamWaitEvent(st, D->lev_ev[2 * last_tail_level], 0));
-    if (!D->batch_ev.empty()) HIPCHK(hipStreamWaitEvent(st, D->batch_ev.back(), 0));
-    // the status word (first non-positive pivot, or "none") is written by the owner of the failing panel only: every
-    // rank takes the minimum, so that all of them report SCILMM_ERR_NOT_PD together
-    hipLaunchKernelGGL(k_status_pack, dim3(1), dim3(1), 0, st, (const int32_t*)fac->status, fac->logd + S.nsuper);
-    HIPCHK(hipEventRecord(D->ev_x0, st));
-    HIPCHK(hipStreamWaitEvent(D->comm, D->ev_x0, 0));
-    if (sym->comm_fn(sym->comm_ctx, 2, 2, S.nsuper, 1, 0) != 0) {
-      sym->err = "multi-GPU: the communication callback failed";
-      return SCILMM_ERR_DEVICE;
-    }
-    HIPCHK(hipEventRecord(D->ev_x1, D->comm));
-    HIPCHK(hipStreamWaitEvent(st, D->ev_x1, 0));
-    hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(1), 0, st, (const double*)(fac->logd + S.nsuper), fac->status);
-  }
-  HIPCHK(hipEventRecord(D->ev[2], st));
+  if (F.dist) TRY(F.exchange_status());
+  HIPCHK(hipEventRecord(D->ev[2], F.st));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(fac->h_status, fac->status, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  D->timing.n_launches = launches;
+  HIPCHK(hipMemcpyAsync(fac->h_status, fac->status, sizeof(int32_t), hipMemcpyDeviceToHost, F.st));
+  D->timing.n_launches = F.launches;
   fac->pending = true;
   if (!wait) return SCILMM_OK;
   return finish_factorize(fac, bad_col);
 }
 
-// second half of a factorization: wait for the queued work, read the event timings and the status word
-int finish_factorize(scilmm_factor* fac, int32_t* bad_col) {
-  scilmm_symbolic* sym = fac->sym;
-  Dev* D = (Dev*)sym->device;
-  const Symbolic& S = *sym->S;
-  hipStream_t st = D->stream;
-  const bool prof = D->profiling;
-  constexpr int PE = 14;
-  fac->pending = false;
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipStreamSynchronize(D->side));
-  HIPCHK(hipStreamSynchronize(D->side2));
-  if (D->side3) HIPCHK(hipStreamSynchronize(D->side3));
-  if (D->bstream) HIPCHK(hipStreamSynchronize(D->bstream));
-  if (D->world > 1 && D->comm) HIPCHK(hipStreamSynchronize(D->comm));
-  if (D->outside_st) HIPCHK(hipStreamSynchronize(D->outside_st));
-  float a = 0, f = 0;
-  HIPCHK(hipEventElapsedTime(&a, D->ev[0], D->ev[1]));
-  HIPCHK(hipEventElapsedTime(&f, D->ev[1], D->ev[2]));
-  D->timing.assemble_ms = a;
-  D->timing.factor_ms = f;
-  const int32_t status = *fac->h_status;
-  if (prof) {
+// Reads the profiling events of a finished factorization into scilmm_timing.  hipEventElapsedTime errors are kept (the
+// first one) and reported by finish_factorize.
+struct ProfRead {
+  Dev* const D;
+  const Symbolic& S;
+  hipError_t err = hipSuccess;
+
+  float elapsed_ms(hipEvent_t a, hipEvent_t b) {
+    float x = 0;
+    const hipError_t e = hipEventElapsedTime(&x, a, b);
+    if (e != hipSuccess && err == hipSuccess) err = e;
+    return x;
+  }
+  hipEvent_t pev(int32_t l, ProfEvent e) const { return D->pev[(size_t)PEV_PER_LEVEL * l + e]; }
+  float span(int32_t l, ProfEvent a, ProfEvent b) { return elapsed_ms(pev(l, a), pev(l, b)); }
+  float since_assembly(int32_t l, ProfEvent e) { return elapsed_ms(D->ev[1], pev(l, e)); }
+  // which of a level's launches exist (an empty bracket is not read)
+  bool upd_l(int32_t l) const { return D->work_ptr[l + 1] > D->work_ptr[l]; }
+  bool upd_e(int32_t l) const { return D->early_ptr[l + 1] > D->early_ptr[l]; }
+  bool dense_l(int32_t l) const { return D->dwork_l_ptr[l + 1] > D->dwork_l_ptr[l]; }
+  bool dense_e(int32_t l) const { return D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l]; }
+
+  // sums of the launch durations per kernel class
+  void level_sums() {
     double tu = 0, tp = 0, tt = 0, tmid = 0, td = 0;
     int64_t nu = 0, nd = 0;
     for (int32_t l = 0; l < S.nlevels; ++l) {
-      float x = 0;
-      if (D->work_ptr[l + 1] > D->work_ptr[l] || D->dwork_l_ptr[l + 1] > D->dwork_l_ptr[l]) {
-        HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 0], D->pev[PE * l + 1]));
-        tu += x;
-        nu += (D->work_ptr[l + 1] > D->work_ptr[l]) + (D->dwork_l_ptr[l + 1] > D->dwork_l_ptr[l]);
+      if (upd_l(l) || dense_l(l)) {
+        tu += span(l, PEV_LATE_BEGIN, PEV_LATE_END);
+        nu += upd_l(l) + dense_l(l);
       }
-      if (D->early_ptr[l + 1] > D->early_ptr[l] || D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l]) {
-        HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 5], D->pev[PE * l + 6]));
-        tu += x;
-        nu += (D->early_ptr[l + 1] > D->early_ptr[l]) + (D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l]);
+      if (upd_e(l) || dense_e(l)) {
+        tu += span(l, PEV_EARLY_BEGIN, PEV_EARLY_END);
+        nu += upd_e(l) + dense_e(l);
       }
-      if (D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l]) {
-        HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 8], D->pev[PE * l + 9]));
-        td += x;
+      if (dense_e(l)) {
+        td += span(l, PEV_DENSE_E_BEGIN, PEV_DENSE_E_END);
         nd++;
       }
-      if (D->dwork_l_ptr[l + 1] > D->dwork_l_ptr[l]) {
+      if (dense_l(l)) {
         const bool split = D->world > 1 && D->dwork_l_mid[(size_t)l] < D->dwork_l_ptr[l + 1] && D->tail_of_level[l] >= 0 &&
                            D->keep_front[D->tail_of_level[l]];
         if (!split || D->dwork_l_mid[(size_t)l] > D->dwork_l_ptr[l]) {
-          HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 10], D->pev[PE * l + 11]));
-          td += x;
+          td += span(l, PEV_DENSE_L_BEGIN, PEV_DENSE_L_END);
           nd++;
         }
         if (split) {  // (the newest source's items: their own bracket, so that the wait for its broadcast is not counted as kernel time)
-          HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 12], D->pev[PE * l + 13]));
-          td += x;
+          td += span(l, PEV_DENSE_N_BEGIN, PEV_DENSE_N_END);
           nd++;
         }
       }
-      HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 1], D->pev[PE * l + 2]));
-      tmid += x;
-      HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 2], D->pev[PE * l + 3]));
-      tp += x;
-      HIPCHK(hipEventElapsedTime(&x, D->pev[PE * l + 3], D->pev[PE * l + 4]));
-      tt += x;
+      tmid += span(l, PEV_LATE_END, PEV_CELLS_END);
+      tp += span(l, PEV_CELLS_END, PEV_POTRF_END);
+      tt += span(l, PEV_POTRF_END, PEV_LEVEL_END);
     }
     if (D->world > 1 && D->dist_first < S.nsuper && D->bpev.size() >= 2 * D->batch_ev.size()) {
       // distributed tail: the batches (one launch sequence per complete source group, on their own stream) carry the bulk of
       // this rank's dense-tail flops; the per-level "late" launches above the rest
       for (size_t g = 0; g < D->batch_ev.size(); ++g) {
         if (D->dbatch_ptr[g + 1] <= D->dbatch_ptr[g]) continue;
-        float x = 0;
-        HIPCHK(hipEventElapsedTime(&x, D->bpev[2 * g], D->bpev[2 * g + 1]));
+        const float x = elapsed_ms(D->bpev[2 * g], D->bpev[2 * g + 1]);
         td += x;
         tu += x;
         nd++;
@@ -569,65 +545,86 @@ int finish_factorize(scilmm_factor* fac, int32_t* bad_col) {
     D->timing.n_update_launches = nu;
     D->timing.dense_ms = td;          // k_dense launches alone (early + late; they overlap each other on the two side streams)
     D->timing.n_dense_launches = nd;
-    {
-      // union of the update launches' [start, end] intervals, measured from the end of the assembly
-      std::vector<std::pair<float, float>> iv;
-      for (int32_t l = 0; l < S.nlevels; ++l) {
-        float a0 = 0, a1 = 0;
-        if (D->work_ptr[l + 1] > D->work_ptr[l] || D->dwork_l_ptr[l + 1] > D->dwork_l_ptr[l]) {
-          HIPCHK(hipEventElapsedTime(&a0, D->ev[1], D->pev[PE * l + 0]));
-          HIPCHK(hipEventElapsedTime(&a1, D->ev[1], D->pev[PE * l + 1]));
-          iv.push_back({a0, a1});
-        }
-        if (D->early_ptr[l + 1] > D->early_ptr[l] || D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l]) {
-          HIPCHK(hipEventElapsedTime(&a0, D->ev[1], D->pev[PE * l + 5]));
-          HIPCHK(hipEventElapsedTime(&a1, D->ev[1], D->pev[PE * l + 6]));
-          iv.push_back({a0, a1});
-        }
+  }
+
+  // union of the update launches' [start, end] intervals, measured from the end of the assembly
+  void update_union() {
+    std::vector<std::pair<float, float>> iv;
+    for (int32_t l = 0; l < S.nlevels; ++l) {
+      if (upd_l(l) || dense_l(l)) {
+        const float a0 = since_assembly(l, PEV_LATE_BEGIN);
+        iv.push_back({a0, since_assembly(l, PEV_LATE_END)});
       }
-      std::sort(iv.begin(), iv.end());
-      double uni = 0.0;
-      float cur0 = 0, cur1 = -1;
-      for (auto& q : iv) {
-        if (cur1 < cur0 || q.first > cur1) {
-          if (cur1 >= cur0) uni += cur1 - cur0;
-          cur0 = q.first;
-          cur1 = q.second;
-        } else {
-          cur1 = std::max(cur1, q.second);
-        }
-      }
-      if (cur1 >= cur0) uni += cur1 - cur0;
-      D->timing.update_union_ms = uni;
-    }
-    if (const char* dump = getenv("SCILMM_LEVEL_DUMP")) {
-      // diagnostic: one line per level (durations in ms; cost = combos + K-chunks of the level's dense work)
-      if (FILE* fp = fopen(dump, "w")) {
-        fprintf(fp, "level,fronts,tiles,items_early,items_late,cost_early,cost_late,early_ms,late_ms,mid_ms,potrf_ms,trsm_ms,t_potrf_ms,t_early0_ms,t_early1_ms,dense_early_ms,dense_late_ms\n");
-        for (int32_t l = 0; l < S.nlevels; ++l) {
-          float xe = 0, xl = 0, xm = 0, xp = 0, xt = 0;
-          if (D->work_ptr[l + 1] > D->work_ptr[l]) HIPCHK(hipEventElapsedTime(&xl, D->pev[PE * l + 0], D->pev[PE * l + 1]));
-          if (D->early_ptr[l + 1] > D->early_ptr[l]) HIPCHK(hipEventElapsedTime(&xe, D->pev[PE * l + 5], D->pev[PE * l + 6]));
-          HIPCHK(hipEventElapsedTime(&xm, D->pev[PE * l + 1], D->pev[PE * l + 2]));
-          HIPCHK(hipEventElapsedTime(&xp, D->pev[PE * l + 2], D->pev[PE * l + 3]));
-          HIPCHK(hipEventElapsedTime(&xt, D->pev[PE * l + 3], D->pev[PE * l + 4]));
-          // absolute times since the start of the factorization: this level's potrf, its early dense launch (begin, end)
-          float tp = 0, te0 = 0, te1 = 0, de = 0, dl = 0;
-          HIPCHK(hipEventElapsedTime(&tp, D->ev[1], D->pev[PE * l + 2]));
-          if (D->dwork_e_ptr[l + 1] > D->dwork_e_ptr[l]) {
-            HIPCHK(hipEventElapsedTime(&te0, D->ev[1], D->pev[PE * l + 8]));
-            HIPCHK(hipEventElapsedTime(&te1, D->ev[1], D->pev[PE * l + 9]));
-            de = te1 - te0;
-          }
-          if (D->dwork_l_ptr[l + 1] > D->dwork_l_ptr[l]) HIPCHK(hipEventElapsedTime(&dl, D->pev[PE * l + 10], D->pev[PE * l + 11]));
-          fprintf(fp, "%d,%d,%lld,%lld,%lld,%lld,%lld,%.4f,%.4f,%.4f,%.4f,%.4f,%.3f,%.3f,%.3f,%.4f,%.4f\n", l, S.level_ptr[l + 1] - S.level_ptr[l],
-                  (long long)(S.level_tile_ptr[l + 1] - S.level_tile_ptr[l]), (long long)(D->early_ptr[l + 1] - D->early_ptr[l]),
-                  (long long)(D->work_ptr[l + 1] - D->work_ptr[l]), (long long)D->lev_cost_e[l], (long long)D->lev_cost_l[l], xe, xl,
-                  xm, xp, xt, tp, te0, te1, de, dl);
-        }
-        fclose(fp);
+      if (upd_e(l) || dense_e(l)) {
+        const float a0 = since_assembly(l, PEV_EARLY_BEGIN);
+        iv.push_back({a0, since_assembly(l, PEV_EARLY_END)});
       }
     }
+    std::sort(iv.begin(), iv.end());
+    double uni = 0.0;
+    float cur0 = 0, cur1 = -1;
+    for (auto& q : iv) {
+      if (cur1 < cur0 || q.first > cur1) {
+        if (cur1 >= cur0) uni += cur1 - cur0;
+        cur0 = q.first;
+        cur1 = q.second;
+      } else {
+        cur1 = std::max(cur1, q.second);
+      }
+    }
+    if (cur1 >= cur0) uni += cur1 - cur0;
+    D->timing.update_union_ms = uni;
+  }
+
+  // SCILMM_LEVEL_DUMP diagnostic: one line per level (durations in ms; cost = combos + K-chunks of the level's dense work)
+  void level_dump(const char* path) {
+    FILE* fp = fopen(path, "w");
+    if (!fp) return;
+    fprintf(fp, "level,fronts,tiles,items_early,items_late,cost_early,cost_late,early_ms,late_ms,mid_ms,potrf_ms,trsm_ms,t_potrf_ms,t_early0_ms,t_early1_ms,dense_early_ms,dense_late_ms\n");
+    for (int32_t l = 0; l < S.nlevels; ++l) {
+      const float xl = upd_l(l) ? span(l, PEV_LATE_BEGIN, PEV_LATE_END) : 0;
+      const float xe = upd_e(l) ? span(l, PEV_EARLY_BEGIN, PEV_EARLY_END) : 0;
+      const float xm = span(l, PEV_LATE_END, PEV_CELLS_END);
+      const float xp = span(l, PEV_CELLS_END, PEV_POTRF_END);
+      const float xt = span(l, PEV_POTRF_END, PEV_LEVEL_END);
+      // absolute times since the end of the assembly: this level's potrf, its early dense launch (begin, end)
+      const float tp = since_assembly(l, PEV_CELLS_END);
+      const float te0 = dense_e(l) ? since_assembly(l, PEV_DENSE_E_BEGIN) : 0;
+      const float te1 = dense_e(l) ? since_assembly(l, PEV_DENSE_E_END) : 0;
+      const float dl = dense_l(l) ? span(l, PEV_DENSE_L_BEGIN, PEV_DENSE_L_END) : 0;
+      fprintf(fp, "%d,%d,%lld,%lld,%lld,%lld,%lld,%.4f,%.4f,%.4f,%.4f,%.4f,%.3f,%.3f,%.3f,%.4f,%.4f\n", l, S.level_ptr[l + 1] - S.level_ptr[l],
+              (long long)(S.level_tile_ptr[l + 1] - S.level_tile_ptr[l]), (long long)(D->early_ptr[l + 1] - D->early_ptr[l]),
+              (long long)(D->work_ptr[l + 1] - D->work_ptr[l]), (long long)D->lev_cost_e[l], (long long)D->lev_cost_l[l], xe, xl,
+              xm, xp, xt, tp, te0, te1, te1 - te0, dl);
+    }
+    fclose(fp);
+  }
+};
+
+// second half of a factorization: wait for the queued work, read the event timings and the status word
+int finish_factorize(scilmm_factor* fac, int32_t* bad_col) {
+  scilmm_symbolic* sym = fac->sym;
+  Dev* D = (Dev*)sym->device;
+  fac->pending = false;
+  HIPCHK(hipStreamSynchronize(D->stream));
+  HIPCHK(hipStreamSynchronize(D->side));
+  HIPCHK(hipStreamSynchronize(D->side2));
+  if (D->side3) HIPCHK(hipStreamSynchronize(D->side3));
+  if (D->bstream) HIPCHK(hipStreamSynchronize(D->bstream));
+  if (D->world > 1 && D->comm) HIPCHK(hipStreamSynchronize(D->comm));
+  if (D->outside_st) HIPCHK(hipStreamSynchronize(D->outside_st));
+  ProfRead T{D, *sym->S};
+  D->timing.assemble_ms = T.elapsed_ms(D->ev[0], D->ev[1]);
+  D->timing.factor_ms = T.elapsed_ms(D->ev[1], D->ev[2]);
+  const int32_t status = *fac->h_status;
+  if (D->profiling && T.err == hipSuccess) {
+    T.level_sums();
+    T.update_union();
+    if (const char* dump = getenv("SCILMM_LEVEL_DUMP")) T.level_dump(dump);
+  }
+  if (T.err != hipSuccess) {
+    sym->err = std::string("hipEventElapsedTime: ") + hipGetErrorString(T.err);
+    return SCILMM_ERR_DEVICE;
   }
   if (status != 0x7fffffff) {
     if (bad_col) *bad_col = status;
@@ -636,6 +633,184 @@ int finish_factorize(scilmm_factor* fac, int32_t* bad_col) {
   fac->valid = true;
   return SCILMM_OK;
 }
+
+// One solve / L*R call: the sequences of a block of up to RPMAX right-hand-side columns, which sit permuted in W
+// (solve) or unpermuted (L*R) and leave through X.
+struct Sweep : SweepLaunch {
+  scilmm_symbolic* const sym;
+  const Symbolic& S;
+  int64_t tot = 0;  // doubles of the block: n * rp
+  int chain_wide_T = 0, chain_full_T = 0;
+  bool mid_recorded = false;
+
+  Sweep(scilmm_factor* f, Dev* d) : SweepLaunch{d, f, d->stream}, sym(f->sym), S(*f->sym->S) {}
+
+  void set_block(int rc) {
+    rp = rp_of(rc);
+    gy = (unsigned)((rp + CW - 1) / CW);
+    tot = (int64_t)S.n * rp;
+    // the chain sweeps pick their own window width: 64 columns for long chains (every window streams the whole dense
+    // tail once), 32 for short ones (twice the workgroups on the latency-bound chain)
+    // (read per call: the parity tests force each width on small chains)
+    const Tuning tune = read_tuning();
+    chain_wide_T = tune.chain_wide_t;
+    chain_full_T = tune.chain_full_t;
+  }
+
+  // the event between the forward and the backward half (of the call's first block)
+  int mark_mid() {
+    if (!mid_recorded) HIPCHK(hipEventRecord(D->ev[4], st));
+    mid_recorded = true;
+    return SCILMM_OK;
+  }
+
+  int chain(bool bwd) {
+    const bool mf = D->use_mfma;
+    const bool wide = D->chain_T >= chain_wide_T;
+    const bool full = D->chain_T >= chain_full_T && rp > 64;  // every column in one 112-wide window
+    const int32_t cwc = full ? 112 : wide ? 64 : 32;
+    const int32_t gyc = (int32_t)((rp + cwc - 1) / cwc);
+    const unsigned grid = (unsigned)D->chain_T * (unsigned)gyc;
+    const int32_t ep = ++D->chain_epoch;
+    HIPCHK(hipMemsetAsync(D->d_chain_err + 2, 0, sizeof(int32_t), st));
+    const int32_t* cptr = bwd ? (const int32_t*)D->d_cb_ptr : (const int32_t*)D->d_cf_ptr;
+    const ChainPair* cpairs = bwd ? (const ChainPair*)D->d_cb : (const ChainPair*)D->d_cf;
+#define SCILMM_CHAIN_LAUNCH(MF, BW, NC)                                                                                                  \
+  hipLaunchKernelGGL((k_chain<MF, BW, NC>), dim3(grid), dim3(512), 0, st, D->v, D->chain_T, (const int32_t*)D->d_chain, cptr, cpairs, \
+                     (const int32_t*)D->d_colmap, (const double*)fac->L, (const double*)fac->invD, (const double*)D->W, D->X, rp, gyc,  \
+                     D->d_chain_flags, ep, D->d_chain_err, D->d_chain_err + 2)
+    if (mf) {
+      if (bwd) { if (full) SCILMM_CHAIN_LAUNCH(true, true, 7); else if (wide) SCILMM_CHAIN_LAUNCH(true, true, 4); else SCILMM_CHAIN_LAUNCH(true, true, 2); }
+      else { if (full) SCILMM_CHAIN_LAUNCH(true, false, 7); else if (wide) SCILMM_CHAIN_LAUNCH(true, false, 4); else SCILMM_CHAIN_LAUNCH(true, false, 2); }
+    } else {
+      if (bwd) SCILMM_CHAIN_LAUNCH(false, true, 2); else SCILMM_CHAIN_LAUNCH(false, false, 2);
+    }
+#undef SCILMM_CHAIN_LAUNCH
+    return SCILMM_OK;
+  }
+
+  // deterministic mode: the targets of levels [la, lb) pull their update pairs, long pair lists are folded in slot order
+  // (one launch: the caller keeps the levels inside one slot group when they are more than one)
+  void pull(int32_t la, int32_t lb, bool lmul, const uint8_t* skip) {
+    const int64_t g0 = S.pull_level_ptr[(size_t)la], g1 = S.pull_level_ptr[(size_t)lb];
+    const int64_t h0 = S.pull_fold_ptr[(size_t)la], h1 = S.pull_fold_ptr[(size_t)lb];
+    double* out = lmul ? D->X : D->W;
+    fwd_pull(lmul, D->d_pull_level_segs + g0, g1 - g0, skip, lmul ? D->W : D->X, out);
+    pull_fold(lmul, D->d_pull_fold + 3 * h0, h1 - h0, out);
+  }
+  // levels from `lo` on, a launch per slot group: for targets that do not depend on each other
+  void pull_groups(int32_t lo, bool lmul, const uint8_t* skip) {
+    for (size_t q = 0; q + 1 < S.pull_group_ptr.size(); ++q) {
+      const int32_t la = std::max(lo, S.pull_group_ptr[q]), lb = S.pull_group_ptr[q + 1];
+      if (la < lb) pull(la, lb, lmul, skip);
+    }
+  }
+
+  // X = V^-1 W on one device: level sweep forward (the chain levels by k_chain), then backward
+  int solve_single() {
+    const int32_t lend = D->chain_T > 0 ? D->chain_l0 : S.nlevels;  // the chain levels are swept by k_chain
+    for (int32_t l = 0; l < lend; ++l) {
+      const int64_t t0 = S.level_tile_ptr[l], t1 = S.level_tile_ptr[l + 1];
+      const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];
+      if (f1 == f0) continue;
+      // deterministic mode: every front of the level first collects the contributions of its (final) descendants
+      if (D->det && l > 0) pull(l, l + 1, false, nullptr);
+      // x_s = invL_s * W[c0:c1] -> X rows c0..c1 (final), then push to the rows below (atomic where fronts may share them)
+      diag_solve(false, D->d_level_fronts + f0, f1 - f0, D->W, D->X);
+      if (!D->det) fwd(0, (f1 - f0) > 1, D->d_level_tiles + t0, t1 - t0, D->X, D->W);
+    }
+    if (D->chain_T > 0) {
+      // (deterministic mode: what the fronts below the chain contribute to the chain blocks arrives through the pull form too)
+      if (D->det) pull_groups(lend, false, D->d_chain_mask);
+      TRY(chain(false));
+    }
+    TRY(mark_mid());
+    if (D->chain_T > 0) {
+      TRY(chain(true));
+      // descendants below the chain: all their chain targets are final now, one read-modify-write each
+      bwd_push(D->d_cg_pairs, D->chain_groups, D->d_cg_ptr, D->d_cg_slot, D->d_push_partial);
+      if (D->chain_groups > 0 && D->n_fold > 0)
+        hipLaunchKernelGGL(k_push_fold, dim3((unsigned)D->n_fold, gy), dim3(256), 0, st, D->v, (const int32_t*)D->d_fold,
+                           (const double*)D->d_push_partial, D->X, rp);
+    }
+    for (int32_t l = lend - 1; l >= 0; --l) {
+      diag_solve(true, D->d_level_fronts + S.level_ptr[l], S.level_ptr[l + 1] - S.level_ptr[l], D->X, D->X);
+      bwd_push(D->d_level_pairs + S.level_pair_ptr[l], S.level_pair_ptr[l + 1] - S.level_pair_ptr[l]);
+    }
+    return SCILMM_OK;
+  }
+
+  // X = L W on one device
+  int lmul_single() {
+    HIPCHK(hipMemsetAsync(D->X, 0, sizeof(double) * (size_t)tot, st));
+    // deterministic mode: every front owns its rows of Z: no dependencies between fronts (the level groups only bound the partial slots)
+    if (D->det) pull_groups(0, true, nullptr);
+    else fwd(1, true, D->d_level_tiles, (int64_t)S.level_tiles.size(), D->W, D->X);
+    return SCILMM_OK;
+  }
+
+  // ---- distributed factor.  The prelude is replicated: every rank sweeps it alike.  A tail panel lives on its owner:
+  //   forward : the owner pushes x_f through its panel into ACC (its private sum of tail contributions); when block f
+  //             is due, the ranks ALL-REDUCE the 128 rows of ACC that belong to it, add them to W (which carries the
+  //             right-hand side and the prelude's contributions, identical everywhere) and every rank solves the block
+  //             with the replicated inverse diagonal block: x_f is known everywhere without a broadcast;
+  //   backward: the owner of panel f has received every push into X[f] (a push (target t, descendant f) needs the
+  //             panel of f): it solves the block and BROADCASTS x_f; then every rank pushes x_f into the descendants
+  //             it holds (the prelude: all ranks; tail panels: their owners).
+  //   L * R   : every panel is multiplied where it lives (the prelude on rank 0), one all-reduce of the product.
+  // One collective per tail block and direction, issued on the communication stream between two event hand-offs.
+  // (buffer 3 = the caller's work buffer, scilmm_dist_set_work: W | X | ACC, nW doubles each)
+  int64_t nW() const { return (int64_t)S.n * RPMAX; }
+  int handoff(int32_t op, int64_t off, int64_t cnt, int32_t root) {
+    HIPCHK(hipEventRecord(D->ev_x0, st));
+    HIPCHK(hipStreamWaitEvent(D->comm, D->ev_x0, 0));
+    if (sym->comm_fn(sym->comm_ctx, op, 3, off, cnt, root) != 0) {
+      sym->err = "multi-GPU: the communication callback failed";
+      return SCILMM_ERR_DEVICE;
+    }
+    HIPCHK(hipEventRecord(D->ev_x1, D->comm));
+    HIPCHK(hipStreamWaitEvent(st, D->ev_x1, 0));
+    return SCILMM_OK;
+  }
+
+  int solve_dist() {
+    HIPCHK(hipMemsetAsync(D->ACC, 0, sizeof(double) * (size_t)tot, st));
+    for (int32_t l = 0; l < S.nlevels; ++l) {
+      const int32_t tf = D->tail_of_level[l];
+      const int64_t t0 = D->lv_tile_ptr[l], tm = D->lv_tile_mid[l], t1 = D->lv_tile_ptr[l + 1];
+      const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];  // ALL fronts of the level (replicated diagonal solves)
+      if (f1 == f0) continue;
+      if (tf >= 0) {
+        const int64_t c0 = S.sn_start[tf], wf = S.sn_start[tf + 1] - c0;
+        TRY(handoff(1, 2 * nW() + c0 * rp, wf * rp, 0));
+        hipLaunchKernelGGL(k_add_rows, dim3((unsigned)((wf * rp + 255) / 256)), dim3(256), 0, st, wf * rp, (const double*)(D->ACC + c0 * rp),
+                           D->W + c0 * rp);
+      }
+      diag_solve(false, D->d_all_fronts + f0, f1 - f0, D->W, D->X);
+      // pushes of the prelude fronts of the level go to W (atomic: they may share rows), of an own tail panel to ACC
+      fwd(0, true, D->d_level_tiles + t0, tm - t0, D->X, D->W);
+      fwd(0, false, D->d_level_tiles + tm, t1 - tm, D->X, D->ACC);
+    }
+    TRY(mark_mid());
+    for (int32_t l = S.nlevels - 1; l >= 0; --l) {
+      const int32_t tf = D->tail_of_level[l];
+      // (the fronts this rank holds)
+      diag_solve(true, D->d_level_fronts + D->lv_ptr[l], D->lv_ptr[l + 1] - D->lv_ptr[l], D->X, D->X);
+      if (tf >= 0) {
+        const int64_t c0 = S.sn_start[tf], wf = S.sn_start[tf + 1] - c0;
+        TRY(handoff(0, nW() + c0 * rp, wf * rp, (tf - D->dist_first) % D->world));
+      }
+      bwd_push(D->d_level_pairs + D->lv_pair_ptr[l], D->lv_pair_ptr[l + 1] - D->lv_pair_ptr[l]);
+    }
+    return SCILMM_OK;
+  }
+
+  int lmul_dist() {
+    HIPCHK(hipMemsetAsync(D->X, 0, sizeof(double) * (size_t)tot, st));
+    fwd(1, true, D->d_lmul_tiles, D->n_lmul_tiles, D->W, D->X);
+    return handoff(1, nW(), tot, 0);
+  }
+};
 
 // dB/dX: device, row-major n x r, ORIGINAL row order.  mode 0: X = V^-1 B.  mode 1: X = P^T L B.
 int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mode) {
@@ -661,283 +836,18 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
     return SCILMM_ERR_DEVICE;
   }
   hipStream_t st = D->stream;
-  const int64_t ntiles_all = (int64_t)S.level_tiles.size();
-  const bool mf = D->use_mfma;
   HIPCHK(hipEventRecord(D->ev[3], st));
-  bool mid_recorded = false;
+  Sweep sw(fac, D);
   for (int32_t cbeg = 0; cbeg < r; cbeg += RPMAX) {
-    const int rc = std::min<int>(RPMAX, r - cbeg);
-    const int rp = rp_of(rc);
-    const unsigned gy = (unsigned)((rp + CW - 1) / CW);
-    // the chain sweeps pick their own window width: 64 columns for long chains (every window streams the whole dense
-    // tail once), 32 for short ones (twice the workgroups on the latency-bound chain)
-    // (read per call: the parity tests force each width on small chains)
-    const Tuning tune = read_tuning();
-    const int chain_wide_T = tune.chain_wide_t, chain_full_T = tune.chain_full_t;
-    auto launch_chain = [&](bool bwd) -> int {
-      const bool wide = D->chain_T >= chain_wide_T;
-      const bool full = D->chain_T >= chain_full_T && rp > 64;  // every column in one 112-wide window
-      const int32_t cwc = full ? 112 : wide ? 64 : 32;
-      const int32_t gyc = (int32_t)((rp + cwc - 1) / cwc);
-      const unsigned grid = (unsigned)D->chain_T * (unsigned)gyc;
-      const int32_t ep = ++D->chain_epoch;
-      HIPCHK(hipMemsetAsync(D->d_chain_err + 2, 0, sizeof(int32_t), st));
-      const int32_t* cptr = bwd ? (const int32_t*)D->d_cb_ptr : (const int32_t*)D->d_cf_ptr;
-      const ChainPair* cpairs = bwd ? (const ChainPair*)D->d_cb : (const ChainPair*)D->d_cf;
-#define SCILMM_CHAIN_LAUNCH(MF, BW, NC)                                                                                                  \
-  hipLaunchKernelGGL((k_chain<MF, BW, NC>), dim3(grid), dim3(512), 0, st, D->v, D->chain_T, (const int32_t*)D->d_chain, cptr, cpairs, \
-                     (const int32_t*)D->d_colmap, (const double*)fac->L, (const double*)fac->invD, (const double*)D->W, D->X, rp, gyc,  \
-                     D->d_chain_flags, ep, D->d_chain_err, D->d_chain_err + 2)
-      if (mf) {
-        if (bwd) { if (full) SCILMM_CHAIN_LAUNCH(true, true, 7); else if (wide) SCILMM_CHAIN_LAUNCH(true, true, 4); else SCILMM_CHAIN_LAUNCH(true, true, 2); }
-        else { if (full) SCILMM_CHAIN_LAUNCH(true, false, 7); else if (wide) SCILMM_CHAIN_LAUNCH(true, false, 4); else SCILMM_CHAIN_LAUNCH(true, false, 2); }
-      } else {
-        if (bwd) SCILMM_CHAIN_LAUNCH(false, true, 2); else SCILMM_CHAIN_LAUNCH(false, false, 2);
-      }
-#undef SCILMM_CHAIN_LAUNCH
-      return SCILMM_OK;
-    };
-    const size_t sm_fwd = sizeof(double) * (size_t)(NB * LDW + KCS * LDA);
-    // deterministic mode: the targets of level l pull their update pairs (k_fwd_pull), long pair lists are folded in slot order
-    // (levels [la, lb): one launch -- the caller keeps them inside one slot group when they are more than one)
-    auto launch_pull = [&](int32_t la, int32_t lb, bool lmul, const uint8_t* skip) {
-      const int64_t g0 = S.pull_level_ptr[(size_t)la], g1 = S.pull_level_ptr[(size_t)lb];
-      const int64_t h0 = S.pull_fold_ptr[(size_t)la], h1 = S.pull_fold_ptr[(size_t)lb];
-      const double* in = lmul ? (const double*)D->W : (const double*)D->X;
-      double* out = lmul ? D->X : D->W;
-      const int64_t mg = (int64_t)(((uint64_t)1 << 32) / 256) - 1;  // launches stay below 2^32 work-items
-      for (int64_t a = g0; a < g1; a += mg) {
-        const unsigned cnt = (unsigned)std::min<int64_t>(mg, g1 - a);
-        const int32_t* segs = D->d_pull_level_segs + a;
-        if (mf && lmul) hipLaunchKernelGGL((k_fwd_pull<true, 1>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
-        else if (mf) hipLaunchKernelGGL((k_fwd_pull<true, 0>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
-        else if (lmul) hipLaunchKernelGGL((k_fwd_pull<false, 1>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
-        else hipLaunchKernelGGL((k_fwd_pull<false, 0>), dim3(cnt, gy), dim3(256), 0, st, D->v, D->pull, segs, skip, (const double*)fac->L, in, out, D->d_pull_partial, rp);
-      }
-      if (h1 > h0) {
-        const int32_t* fold = D->d_pull_fold + 3 * h0;
-        if (lmul) hipLaunchKernelGGL(k_pull_fold<1>, dim3((unsigned)(h1 - h0), gy), dim3(256), 0, st, D->v, fold, (const double*)D->d_pull_partial, out, rp);
-        else hipLaunchKernelGGL(k_pull_fold<0>, dim3((unsigned)(h1 - h0), gy), dim3(256), 0, st, D->v, fold, (const double*)D->d_pull_partial, out, rp);
-      }
-    };
-    // levels from `lo` on, a launch per slot group: for targets that do not depend on each other
-    auto launch_pull_groups = [&](int32_t lo, bool lmul, const uint8_t* skip) {
-      for (size_t q = 0; q + 1 < S.pull_group_ptr.size(); ++q) {
-        const int32_t la = std::max(lo, S.pull_group_ptr[q]), lb = S.pull_group_ptr[q + 1];
-        if (la < lb) launch_pull(la, lb, lmul, skip);
-      }
-    };
-    const int64_t tot = (int64_t)S.n * rp;
-    const unsigned pb = (unsigned)((tot + 255) / 256);
-    if (D->world > 1) {
-      // ---- distributed factor.  The prelude is replicated: every rank sweeps it alike.  A tail panel lives on its owner:
-      //   forward : the owner pushes x_f through its panel into ACC (its private sum of tail contributions); when block f
-      //             is due, the ranks ALL-REDUCE the 128 rows of ACC that belong to it, add them to W (which carries the
-      //             right-hand side and the prelude's contributions, identical everywhere) and every rank solves the block
-      //             with the replicated inverse diagonal block: x_f is known everywhere without a broadcast;
-      //   backward: the owner of panel f has received every push into X[f] (a push (target t, descendant f) needs the
-      //             panel of f): it solves the block and BROADCASTS x_f; then every rank pushes x_f into the descendants
-      //             it holds (the prelude: all ranks; tail panels: their owners).
-      //   L * R   : every panel is multiplied where it lives (the prelude on rank 0), one all-reduce of the product.
-      // One collective per tail block and direction, issued on the communication stream between two event hand-offs.
-      const int64_t nW = (int64_t)S.n * RPMAX;  // W | X | ACC inside the caller's work buffer (scilmm_dist_set_work)
-      auto handoff = [&](int32_t op, int64_t off, int64_t cnt, int32_t root) -> int {
-        HIPCHK(hipEventRecord(D->ev_x0, st));
-        HIPCHK(hipStreamWaitEvent(D->comm, D->ev_x0, 0));
-        if (sym->comm_fn(sym->comm_ctx, op, 3, off, cnt, root) != 0) {
-          sym->err = "multi-GPU: the communication callback failed";
-          return SCILMM_ERR_DEVICE;
-        }
-        HIPCHK(hipEventRecord(D->ev_x1, D->comm));
-        HIPCHK(hipStreamWaitEvent(st, D->ev_x1, 0));
-        return SCILMM_OK;
-      };
-      int rcx;
-      if (mode == 1) {
-        hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, (const int32_t*)nullptr, dB, D->W);
-        HIPCHK(hipMemsetAsync(D->X, 0, sizeof(double) * (size_t)tot, st));
-        if (D->n_lmul_tiles > 0) {
-          D->n_float_atomic++;
-          if (mf)
-            hipLaunchKernelGGL((k_fwd<true, 1, true>), dim3((unsigned)D->n_lmul_tiles, gy), dim3(256), sm_fwd, st, D->v, D->d_lmul_tiles,
-                               fac->L, (const double*)D->W, D->X, rp);
-          else
-            hipLaunchKernelGGL((k_fwd<false, 1, true>), dim3((unsigned)D->n_lmul_tiles, gy), dim3(256), sm_fwd, st, D->v, D->d_lmul_tiles,
-                               fac->L, (const double*)D->W, D->X, rp);
-        }
-        if ((rcx = handoff(1, nW, tot, 0)) != SCILMM_OK) return rcx;
-        hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, D->v.perm, D->X, dX);
-        continue;
-      }
-      hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, D->v.perm, dB, D->W);
-      HIPCHK(hipMemsetAsync(D->ACC, 0, sizeof(double) * (size_t)tot, st));
-      for (int32_t l = 0; l < S.nlevels; ++l) {
-        const int32_t tf = D->tail_of_level[l];
-        const int64_t t0 = D->lv_tile_ptr[l], tm = D->lv_tile_mid[l], t1 = D->lv_tile_ptr[l + 1];
-        const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];  // ALL fronts of the level (replicated diagonal solves)
-        if (f1 == f0) continue;
-        if (tf >= 0) {
-          const int64_t c0 = S.sn_start[tf], wf = S.sn_start[tf + 1] - c0;
-          if ((rcx = handoff(1, 2 * nW + c0 * rp, wf * rp, 0)) != SCILMM_OK) return rcx;
-          hipLaunchKernelGGL(k_add_rows, dim3((unsigned)((wf * rp + 255) / 256)), dim3(256), 0, st, wf * rp, (const double*)(D->ACC + c0 * rp),
-                             D->W + c0 * rp);
-        }
-        if (mf)
-          hipLaunchKernelGGL((k_diag_solve<true, false>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v, D->d_all_fronts + f0,
-                             fac->invD, (const double*)D->W, D->X, rp);
-        else
-          hipLaunchKernelGGL((k_diag_solve<false, false>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v, D->d_all_fronts + f0,
-                             fac->invD, (const double*)D->W, D->X, rp);
-        // pushes of the prelude fronts of the level go to W (atomic: they may share rows), of an own tail panel to ACC
-        if (tm > t0) {
-          D->n_float_atomic++;
-          if (mf)
-            hipLaunchKernelGGL((k_fwd<true, 0, true>), dim3((unsigned)(tm - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
-                               fac->L, (const double*)D->X, D->W, rp);
-          else
-            hipLaunchKernelGGL((k_fwd<false, 0, true>), dim3((unsigned)(tm - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
-                               fac->L, (const double*)D->X, D->W, rp);
-        }
-        if (t1 > tm) {
-          if (mf)
-            hipLaunchKernelGGL((k_fwd<true, 0, false>), dim3((unsigned)(t1 - tm), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + tm,
-                               fac->L, (const double*)D->X, D->ACC, rp);
-          else
-            hipLaunchKernelGGL((k_fwd<false, 0, false>), dim3((unsigned)(t1 - tm), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + tm,
-                               fac->L, (const double*)D->X, D->ACC, rp);
-        }
-      }
-      if (!mid_recorded) {
-        HIPCHK(hipEventRecord(D->ev[4], st));
-        mid_recorded = true;
-      }
-      for (int32_t l = S.nlevels - 1; l >= 0; --l) {
-        const int32_t tf = D->tail_of_level[l];
-        const int32_t f0 = D->lv_ptr[l], f1 = D->lv_ptr[l + 1];  // the fronts this rank holds
-        const int64_t p0 = D->lv_pair_ptr[l], p1 = D->lv_pair_ptr[l + 1];
-        if (f1 > f0) {
-          if (mf)
-            hipLaunchKernelGGL((k_diag_solve<true, true>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v, D->d_level_fronts + f0,
-                               fac->invD, (const double*)D->X, D->X, rp);
-          else
-            hipLaunchKernelGGL((k_diag_solve<false, true>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v, D->d_level_fronts + f0,
-                               fac->invD, (const double*)D->X, D->X, rp);
-        }
-        if (tf >= 0) {
-          const int64_t c0 = S.sn_start[tf], wf = S.sn_start[tf + 1] - c0;
-          if ((rcx = handoff(0, nW + c0 * rp, wf * rp, (tf - D->dist_first) % D->world)) != SCILMM_OK) return rcx;
-        }
-        if (p1 > p0) {
-          if (mf)
-            hipLaunchKernelGGL(k_bwd_push<true>, dim3((unsigned)(p1 - p0), gy), dim3(256), 0, st, D->v, D->d_level_pairs + p0,
-                               (const int64_t*)nullptr, fac->L, D->X, rp, (const int32_t*)nullptr, (double*)nullptr);
-          else
-            hipLaunchKernelGGL(k_bwd_push<false>, dim3((unsigned)(p1 - p0), gy), dim3(256), 0, st, D->v, D->d_level_pairs + p0,
-                               (const int64_t*)nullptr, fac->L, D->X, rp, (const int32_t*)nullptr, (double*)nullptr);
-        }
-      }
-      hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, D->v.perm, D->X, dX);
-      continue;
-    }
-    if (mode == 0) {
-      hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, D->v.perm, dB, D->W);
-      const int32_t lend = D->chain_T > 0 ? D->chain_l0 : S.nlevels;  // the chain levels are swept by k_chain
-      for (int32_t l = 0; l < lend; ++l) {
-        const int64_t t0 = S.level_tile_ptr[l], t1 = S.level_tile_ptr[l + 1];
-        const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];
-        if (f1 == f0) continue;
-        // deterministic mode: every front of the level first collects the contributions of its (final) descendants
-        if (D->det && l > 0) launch_pull(l, l + 1, false, nullptr);
-        // x_s = invL_s * W[c0:c1] -> X rows c0..c1 (final), then push to the rows below
-        if (mf)
-          hipLaunchKernelGGL((k_diag_solve<true, false>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v,
-                             D->d_level_fronts + f0, fac->invD, (const double*)D->W, D->X, rp);
-        else
-          hipLaunchKernelGGL((k_diag_solve<false, false>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v,
-                             D->d_level_fronts + f0, fac->invD, (const double*)D->W, D->X, rp);
-        if (t1 == t0 || D->det) continue;
-        const bool atomic = (f1 - f0) > 1;
-        if (atomic) D->n_float_atomic++;
-        if (mf && atomic)
-          hipLaunchKernelGGL((k_fwd<true, 0, true>), dim3((unsigned)(t1 - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
-                             fac->L, (const double*)D->X, D->W, rp);
-        else if (mf)
-          hipLaunchKernelGGL((k_fwd<true, 0, false>), dim3((unsigned)(t1 - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
-                             fac->L, (const double*)D->X, D->W, rp);
-        else if (atomic)
-          hipLaunchKernelGGL((k_fwd<false, 0, true>), dim3((unsigned)(t1 - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
-                             fac->L, (const double*)D->X, D->W, rp);
-        else
-          hipLaunchKernelGGL((k_fwd<false, 0, false>), dim3((unsigned)(t1 - t0), gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles + t0,
-                             fac->L, (const double*)D->X, D->W, rp);
-      }
-      if (D->chain_T > 0) {
-        // (deterministic mode: what the fronts below the chain contribute to the chain blocks arrives through the pull form too)
-        if (D->det) launch_pull_groups(lend, false, (const uint8_t*)D->d_chain_mask);
-        if (int e = launch_chain(false)) return e;
-      }
-      if (!mid_recorded) {
-        HIPCHK(hipEventRecord(D->ev[4], st));
-        mid_recorded = true;
-      }
-      if (D->chain_T > 0) {
-        if (int e = launch_chain(true)) return e;
-        // descendants below the chain: all their chain targets are final now, one read-modify-write each
-        if (D->chain_groups > 0) {
-          if (mf)
-            hipLaunchKernelGGL(k_bwd_push<true>, dim3((unsigned)D->chain_groups, gy), dim3(256), 0, st, D->v,
-                               (const int32_t*)D->d_cg_pairs, (const int64_t*)D->d_cg_ptr, fac->L, D->X, rp,
-                               (const int32_t*)D->d_cg_slot, D->d_push_partial);
-          else
-            hipLaunchKernelGGL(k_bwd_push<false>, dim3((unsigned)D->chain_groups, gy), dim3(256), 0, st, D->v,
-                               (const int32_t*)D->d_cg_pairs, (const int64_t*)D->d_cg_ptr, fac->L, D->X, rp,
-                               (const int32_t*)D->d_cg_slot, D->d_push_partial);
-          if (D->n_fold > 0)
-            hipLaunchKernelGGL(k_push_fold, dim3((unsigned)D->n_fold, gy), dim3(256), 0, st, D->v, (const int32_t*)D->d_fold,
-                               (const double*)D->d_push_partial, D->X, rp);
-        }
-      }
-      for (int32_t l = lend - 1; l >= 0; --l) {
-        const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];
-        const int64_t p0 = S.level_pair_ptr[l], p1 = S.level_pair_ptr[l + 1];
-        if (f1 > f0) {
-          if (mf)
-            hipLaunchKernelGGL((k_diag_solve<true, true>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v,
-                               D->d_level_fronts + f0, fac->invD, (const double*)D->X, D->X, rp);
-          else
-            hipLaunchKernelGGL((k_diag_solve<false, true>), dim3((unsigned)(f1 - f0), gy), dim3(256), 0, st, D->v,
-                               D->d_level_fronts + f0, fac->invD, (const double*)D->X, D->X, rp);
-        }
-        if (p1 > p0) {
-          if (mf)
-            hipLaunchKernelGGL(k_bwd_push<true>, dim3((unsigned)(p1 - p0), gy), dim3(256), 0, st, D->v, D->d_level_pairs + p0,
-                               (const int64_t*)nullptr, fac->L, D->X, rp, (const int32_t*)nullptr, (double*)nullptr);
-          else
-            hipLaunchKernelGGL(k_bwd_push<false>, dim3((unsigned)(p1 - p0), gy), dim3(256), 0, st, D->v, D->d_level_pairs + p0,
-                               (const int64_t*)nullptr, fac->L, D->X, rp, (const int32_t*)nullptr, (double*)nullptr);
-        }
-      }
-      hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, D->v.perm, D->X, dX);
-    } else {
-      // Z = P^T (L R): R is NOT permuted on the way in (SparseCholesky.py:50-51)
-      hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, (const int32_t*)nullptr, dB, D->W);
-      HIPCHK(hipMemsetAsync(D->X, 0, sizeof(double) * (size_t)tot, st));
-      if (D->det) {
-        // every front owns its rows of Z: no dependencies between fronts (the level groups only bound the partial slots)
-        launch_pull_groups(0, true, nullptr);
-      } else if (ntiles_all > 0) {
-        D->n_float_atomic++;
-        if (mf)
-          hipLaunchKernelGGL((k_fwd<true, 1, true>), dim3((unsigned)ntiles_all, gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles, fac->L,
-                             (const double*)D->W, D->X, rp);
-        else
-          hipLaunchKernelGGL((k_fwd<false, 1, true>), dim3((unsigned)ntiles_all, gy), dim3(256), sm_fwd, st, D->v, D->d_level_tiles, fac->L,
-                             (const double*)D->W, D->X, rp);
-      }
-      hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, rp, cbeg, D->v.perm, D->X, dX);
-    }
+    sw.set_block(std::min<int>(RPMAX, r - cbeg));
+    const unsigned pb = (unsigned)((sw.tot + 255) / 256);
+    // Z = P^T (L R): R is NOT permuted on the way in (SparseCholesky.py:50-51)
+    hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, sw.rp, cbeg, mode == 1 ? (const int32_t*)nullptr : D->v.perm, dB, D->W);
+    if (D->world > 1) TRY(mode == 1 ? sw.lmul_dist() : sw.solve_dist());
+    else TRY(mode == 1 ? sw.lmul_single() : sw.solve_single());
+    hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, sw.rp, cbeg, D->v.perm, D->X, dX);
   }
-  if (!mid_recorded) HIPCHK(hipEventRecord(D->ev[4], st));
+  TRY(sw.mark_mid());
   if (D->h_chain_err && mode == 0) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(D->ev[5], st));
   HIPCHK(hipGetLastError());
@@ -1641,23 +1551,13 @@ int scilmm_selected_inverse(scilmm_factor* fac) {
   // SCILMM_SINV_GENERIC=1: the gather kernel for the dense tail as well (the round's first form)
   const bool tail_kernel = D->use_mfma && !read_tuning().sinv_generic;
   for (int32_t l = S.nlevels - 1; l >= 0; --l) {
-    const int64_t t0 = D->lv_tile_ptr[l], t1 = D->lv_tile_ptr[l + 1];
+    const int64_t t0 = D->lv_tile_ptr[l], nt = D->lv_tile_ptr[l + 1] - t0;
     const int32_t f0 = D->lv_ptr[l], f1 = D->lv_ptr[l + 1];
     if (f1 == f0) continue;
-    const unsigned nt = (unsigned)(t1 - t0);
+    const int32_t* tiles = D->d_level_tiles + t0;
     const int32_t tf = tail_kernel ? D->sinv_tail_front[(size_t)l] : -1;
-    // tiles that go through the gather kernel: all of the level's, or the non-tail fronts' only
-    const int32_t* wt = tf >= 0 ? D->d_sinv_pre_tiles + D->sinv_pre_ptr[(size_t)l] : D->d_level_tiles + t0;
-    const unsigned nwt = tf >= 0 ? (unsigned)(D->sinv_pre_ptr[(size_t)l + 1] - D->sinv_pre_ptr[(size_t)l]) : nt;
     const int32_t ydf = tail_kernel ? S.dense_first : S.nsuper;  // fronts from here on keep Y transposed
-    if (nt > 0) {
-      if (D->use_mfma)
-        hipLaunchKernelGGL(k_sinv_y<true>, dim3(nt), dim3(256), 0, st, D->v, D->d_level_tiles + t0, (const double*)fac->L,
-                           (const double*)fac->invD, D->d_ybuf, (const int64_t*)D->d_yoff, ydf);
-      else
-        hipLaunchKernelGGL(k_sinv_y<false>, dim3(nt), dim3(256), 0, st, D->v, D->d_level_tiles + t0, (const double*)fac->L,
-                           (const double*)fac->invD, D->d_ybuf, (const int64_t*)D->d_yoff, ydf);
-    }
+    sinv_y(D, fac, st, tiles, nt, ydf);
     hipLaunchKernelGGL(k_sinv_cc0, dim3((unsigned)(f1 - f0)), dim3(256), 0, st, D->v, D->d_level_fronts + f0, fac->L,
                        (const double*)fac->invD);
     if (tf >= 0) {
@@ -1671,24 +1571,12 @@ int scilmm_selected_inverse(scilmm_factor* fac) {
                            S.dense_first, (const SinvWork*)(D->d_sinv_work + i0), fac->L, (const double*)D->d_ybuf,
                            (const int64_t*)D->d_yoff, (const int32_t*)D->d_col_front, (const double*)D->d_zeros);
       }
+      // the gather kernel takes the non-tail fronts' tiles only
+      sinv_w(D, fac, st, D->d_sinv_pre_tiles + D->sinv_pre_ptr[(size_t)l], D->sinv_pre_ptr[(size_t)l + 1] - D->sinv_pre_ptr[(size_t)l]);
+    } else {
+      sinv_w(D, fac, st, tiles, nt);  // ... or all of the level's
     }
-    if (nwt > 0) {
-      D->n_float_atomic++;
-      if (D->use_mfma)
-        hipLaunchKernelGGL(k_sinv_w<true>, dim3(nwt), dim3(256), 0, st, D->v, wt, fac->L, (const double*)D->d_ybuf,
-                           (const int64_t*)D->d_yoff, (const int32_t*)D->d_col_front, S.dense_first);
-      else
-        hipLaunchKernelGGL(k_sinv_w<false>, dim3(nwt), dim3(256), 0, st, D->v, wt, fac->L, (const double*)D->d_ybuf,
-                           (const int64_t*)D->d_yoff, (const int32_t*)D->d_col_front, S.dense_first);
-    }
-    if (nt > 0) {
-      if (D->use_mfma)
-        hipLaunchKernelGGL(k_sinv_cc<true>, dim3(nt), dim3(256), 0, st, D->v, D->d_level_tiles + t0, fac->L, (const double*)D->d_ybuf,
-                           (const int64_t*)D->d_yoff, ydf);
-      else
-        hipLaunchKernelGGL(k_sinv_cc<false>, dim3(nt), dim3(256), 0, st, D->v, D->d_level_tiles + t0, fac->L, (const double*)D->d_ybuf,
-                           (const int64_t*)D->d_yoff, ydf);
-    }
+    sinv_cc(D, fac, st, tiles, nt, ydf);
   }
   HIPCHK(hipEventRecord(D->ev[7], st));
   HIPCHK(hipStreamSynchronize(st));

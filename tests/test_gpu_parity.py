@@ -242,6 +242,44 @@ def test_alternative_schedules_agree_with_oracle(monkeypatch, env):
     _check_factor([A, sp.identity(n, format="csr")], [0.35, 0.65], _engine([A, sp.identity(n, format="csr")]), rs=(5, 103))
 
 
+@pytest.mark.parametrize("env", [{}, {"SCILMM_TUNING": "1", "SCILMM_DENSE": "1", "SCILMM_OUTSIDE": "1"}],
+                         ids=["default", "dense_outside"])
+def test_profiled_factorization_reports_consistent_timings(monkeypatch, tmp_path, env):
+    """Profiling (set_profiling(1)) only adds event records: same launches, same factor, and the per-level event brackets
+    add up -- the SCILMM_LEVEL_DUMP rows (printed %.4f from the same event pairs) sum to timing()'s potrf_ms / trsm_ms
+    within the print rounding."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    A, _ = small_pedigree(10000, 0.01, 5)
+    n = A.shape[0]
+    mats, s2 = [A, sp.identity(n, format="csr")], [0.35, 0.65]
+    sym = _engine(mats)
+    f = sym.factorize(s2)
+    n_launches = sym.timing()["n_launches"]
+    assert n_launches > 0
+    dump = tmp_path / "levels.csv"
+    monkeypatch.setenv("SCILMM_LEVEL_DUMP", str(dump))
+    sym.set_profiling(1)
+    f.refactorize(s2)
+    t = sym.timing()
+    rows = [line.split(",") for line in dump.read_text().splitlines()]
+    assert t["n_launches"] == n_launches  # events are not launches
+    for name, v in t.items():
+        if name.endswith("_ms"):
+            assert np.isfinite(v) and v >= 0, (name, v)
+    assert t["n_update_launches"] > 0
+    assert (t["n_dense_launches"] > 0) == ("SCILMM_DENSE" in env)
+    nlevels = sym.info().nlevels
+    assert len(rows) == nlevels + 1 and all(len(r) == 17 for r in rows)
+    for name in ("potrf_ms", "trsm_ms"):
+        col = rows[0].index(name)
+        total = sum(float(r[col]) for r in rows[1:])
+        print(name, "dump sum", total, "timing", t[name], "levels", nlevels)
+        assert abs(total - t[name]) <= nlevels * 1e-4, (name, total, t[name])
+    _check_factor(mats, s2, sym, rs=(5, 103))  # (a profiled factorization of its own)
+    assert sym.timing()["n_launches"] == n_launches
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", [{}, {"SCILMM_DENSE": "1"}, {"SCILMM_DENSE": "1", "SCILMM_OUTSIDE": "1"},
                                  {"SCILMM_OUTSIDE": "1"}])
