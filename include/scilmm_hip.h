@@ -185,6 +185,42 @@ int scilmm_spmm(scilmm_symbolic* sym, int32_t k, const double* X, int32_t r, dou
 /* the same with DEVICE pointers, asynchronous on the engine's stream (the residual of a refinement sweep without a host round trip) */
 int scilmm_spmm_dev(scilmm_symbolic* sym, int32_t k, const double* dX, int32_t r, double* dY);
 
+/* The two halves of factor(b), without the permutation: L X = B (scilmm_solve_L) and L^T X = B (scilmm_solve_Lt), B and X
+ * row-major n x r with rows in the factor's PERMUTED order (row p belongs to individual P[p]).  They replace
+ * sksparse's factor.solve_L(b, use_LDLt_decomposition=False) and factor.solve_Lt(b, use_LDLt_decomposition=False)
+ * (cholmod_solve2 with CHOLMOD_L / CHOLMOD_Lt); factor.apply_P / apply_Pt (CHOLMOD_P / CHOLMOD_Pt) are index operations
+ * on the caller's side (scilmm_symbolic_get "perm").  X = apply_Pt(solve_Lt(solve_L(apply_P(B)))) is scilmm_solve's X: the
+ * same launches in the same order, bit for bit in deterministic mode.  Any r >= 1 (blocks of 128 columns, like
+ * scilmm_solve); r <= 0 or a null pointer: SCILMM_ERR_ARG.  Refused with SCILMM_ERR_STATE and a message, the handle left
+ * as it was: a distributed factor (scilmm_dist_init with world > 1), a handle with scilmm_set_front_precision(32) (a
+ * half-solve cannot be refined against the exact V the way factor(b) is), a factor consumed by scilmm_selected_inverse.
+ * The reference never takes a half-solve; the marker scan below is what they are for. */
+int scilmm_solve_L(scilmm_factor* fac, const double* B, int32_t r, double* X);
+int scilmm_solve_Lt(scilmm_factor* fac, const double* B, int32_t r, double* X);
+
+/* One block of a marker association scan with V held fixed (EMMAX / P3D form), on the device: with w(b) = L^-1 P b,
+ * GLS of y on [C, g] under V is OLS of w(y) on [w(C), w(g)], so a marker costs the FORWARD half of a solve and a column
+ * reduction -- in place of one scilmm_solve_dev (cholmod_solve2 with CHOLMOD_A) and an n x r device-to-host copy per block
+ * of markers.
+ *   d_geno : marker j of the block = d_geno + j * ld_geno, n int8 values, individuals in the ORIGINAL order (the row order
+ *            of the matrices), 0 / 1 / 2 = allele count, any negative value = missing; ld_geno >= n.  Any alignment; the
+ *            rows are read in aligned 16-byte pieces, so the buffer must lie in an allocation that starts and ends on
+ *            16-byte boundaries (every hipMalloc allocation does).
+ *   r      : markers in the block, 1 .. 128.
+ *   d_Q    : n x q row-major, PERMUTED order: the caller's whitened [w(C) | w(y)] as scilmm_solve_L_dev writes it; 1 <= q <= 32.
+ *   d_stats: (q + 4) x r row-major: n_obs | mean over the observed | centred sum of squares over the observed |
+ *            |w(g~)|^2 | the q rows of Q^T w(g~), where g~ = genotype minus the marker's mean, missing = 0 (mean imputation).
+ * Everything is enqueued on the handle's stream without synchronising; the n x r block never leaves the engine's work
+ * buffers.  Every sum is taken in an order that depends on (n, r) alone and without floating-point atomics, so the call
+ * adds to scilmm_timing.n_float_atomic_launches only what its forward sweep adds (nothing in deterministic mode).
+ * Arguments out of range or null: SCILMM_ERR_ARG; refusals as for the half-solves.  No counterpart in the reference. */
+int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
+                          double* d_stats);
+
+/* HIP-event times of the last scilmm_scan_block_dev on the handle, in milliseconds, valid after the scilmm_sync that follows
+ * it: ms[0] moments + dequantise (+ permute), ms[1] forward sweep, ms[2] statistics (tools/assoc_timing.py). */
+int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);
+
 /* SURVEY section 8f rank 4 -- the exact tr(V^-1 A_k) of the gradient instead of the reference's Monte-Carlo estimate
  * (scilmm/SparseCholesky.py:49-52, :65).  scilmm_selected_inverse replaces, IN PLACE, every stored entry of the factor by
  * the entry of Z = (V[P][:,P])^-1 at the same position (Takahashi recursion over the supernodes from the last level
@@ -262,6 +298,8 @@ const char* scilmm_csr_spmm_error(void);
 /* --- device-pointer variants used by bench.py and by callers that keep data resident in HBM */
 int scilmm_solve_dev(scilmm_factor* fac, const double* dB, int32_t r, double* dX);
 int scilmm_lmul_dev(scilmm_factor* fac, const double* dR, int32_t r, double* dZ);
+int scilmm_solve_L_dev(scilmm_factor* fac, const double* dB, int32_t r, double* dX);
+int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double* dX);
 int scilmm_quadforms_dev(scilmm_symbolic* sym, int32_t k, const double* dU, int32_t r, double* d_out);
 int scilmm_sync(scilmm_symbolic* sym);
 

@@ -10,4 +10,5 @@ from .SparseCholesky import (SparseCholesky, REML, HE, run_estimates, run_estima
                              negative_log_likelihood, simulate_vector, matrices_weighted_sum, compute_gradients,
                              compute_hess, compute_varcomp_stderr)
 from .factor import Symbolic, Factor  # noqa: F401
+from .assoc import AssociationScan  # noqa: F401
 from ._lib import ScilmmError, NotPositiveDefiniteError  # noqa: F401

@@ -73,6 +73,8 @@ SYMBOLS = [
     "scilmm_dominance", "scilmm_dominance_dev", "scilmm_dominance_error",
     "scilmm_csr_spmm_dev", "scilmm_csr_spmm_error",
     "scilmm_set_deterministic", "scilmm_get_deterministic",
+    "scilmm_solve_L", "scilmm_solve_Lt", "scilmm_solve_L_dev", "scilmm_solve_Lt_dev", "scilmm_scan_block_dev",
+    "scilmm_scan_timing",
 ]
 
 _lib = None
@@ -159,6 +161,12 @@ def lib():
     L.scilmm_dominance_error.restype = C.c_char_p
     L.scilmm_csr_spmm_dev.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp]
     L.scilmm_csr_spmm_error.restype = C.c_char_p
+    L.scilmm_solve_L.argtypes = [vp, vp, i32, vp]
+    L.scilmm_solve_Lt.argtypes = [vp, vp, i32, vp]
+    L.scilmm_solve_L_dev.argtypes = [vp, vp, i32, vp]
+    L.scilmm_solve_Lt_dev.argtypes = [vp, vp, i32, vp]
+    L.scilmm_scan_block_dev.argtypes = [vp, vp, i64, i32, vp, i32, vp]
+    L.scilmm_scan_timing.argtypes = [vp, P(dbl)]
     L.scilmm_order.argtypes = [i32, vp, vp, i32, vp]
     L.scilmm_fill_count.argtypes = [i32, vp, vp, vp, P(i64), P(dbl), P(i32)]
     _lib = L

@@ -1,0 +1,144 @@
+"""Marker association scan with the variance components held fixed (EMMAX / P3D form) on the resident factor.
+
+With ``w(b) = L^-1 P b`` (``L L^T = V[P][:, P]``), GLS of ``y`` on ``[C, g]`` under ``V`` is OLS of ``w(y)`` on
+``[w(C), w(g)]``::
+
+    g' V^-1 g = |w(g)|^2        g' V^-1 y = w(g)' w(y)        C' V^-1 g = w(C)' w(g)
+
+so a marker costs the forward half of a solve and a column reduction.  ``AssociationScan`` whitens ``[C | y]`` once
+(``Factor.solve_L_dev``) and then streams blocks of int8 markers through ``scilmm_scan_block_dev``: moments, dequantise +
+centre + permute, one forward sweep, column statistics -- the n x r block never leaves HBM and only ``(q + 4)`` numbers per
+marker come back.  The reference stops at the Wald tests of its covariates (scilmm/Estimation/LMM.py:129-133); the p-value
+convention here is the same F(1, n - 1).
+
+    scan = AssociationScan(cholesky_func, mats, sigma2, covariates, y)
+    out = scan(genotypes)          # m x n int8, marker-major; dict of length-m arrays
+
+There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
+"""
+import ctypes as C
+
+import numpy as np
+import scipy.linalg as la
+import scipy.stats as stats
+
+from . import _lib
+
+RPMAX = 128   # markers per device block at most (csrc/plan_types.h)
+QMAX = 32     # columns of [w(C) | w(y)] at most (csrc/scan.hip.h)
+# Width of a device block when the caller does not choose: one full chain window (112) or the sweeps' RPMAX (128),
+# whichever gives more markers per second in profiles/assoc_scan_100k.json (tools/assoc_timing.py).
+DEFAULT_BLOCK = 128
+_CHUNK_BYTES = 64 << 20   # genotypes on the device at a time (whole blocks)
+
+
+def check_genotypes(genotypes, n):
+    """The genotype matrix as the device path takes it: m x n int8, marker-major, C-contiguous (``np.memmap`` included),
+    columns in the row order of ``mats``.  TypeError for another dtype, ValueError for another shape or layout; nothing is
+    converted or copied here."""
+    g = genotypes
+    if not isinstance(g, np.ndarray):
+        raise TypeError("genotypes must be a NumPy int8 array (np.memmap included), got %s" % type(g).__name__)
+    if g.dtype != np.int8:
+        raise TypeError("genotypes must be int8 allele counts (negative = missing), got %s" % g.dtype)
+    if g.ndim != 2:
+        raise ValueError("genotypes must be 2-D, markers x individuals; got %d-D" % g.ndim)
+    if g.shape[1] != n:
+        raise ValueError("genotypes have %d columns, the model has %d individuals" % (g.shape[1], n))
+    if not g.flags.c_contiguous:
+        raise ValueError("genotypes must be C-contiguous (marker-major)")
+    return g
+
+
+class AssociationScan(object):
+    """Tests many candidate fixed effects next to ``covariates`` under V = sum_k sigma2[k] mats[k].
+
+    ``cholesky_func``: a ``SparseCholesky``; ``mats``: every matrix of V (the identity included), as ``_final_factor`` takes
+    them; ``sigma2``: one coefficient per matrix; ``covariates``: n x c (an intercept column is the caller's); ``y``: n.
+    ``block``: markers per device block, 1..128.  The resident factor of ``(mats, sigma2)`` is obtained or re-used; a scan
+    object is tied to it and refuses to run once the factor has been refactorized at other values (build a new one)."""
+
+    def __init__(self, cholesky_func, mats, sigma2, covariates, y, block=None):
+        from .SparseCholesky import SparseCholesky, _device_buffers, _final_factor
+        if block is None:
+            block = DEFAULT_BLOCK
+        if not (isinstance(block, (int, np.integer)) and 1 <= block <= RPMAX):
+            raise ValueError("block must be an integer in 1..%d" % RPMAX)
+        covariates = np.asarray(covariates, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64).ravel()
+        if covariates.ndim != 2 or covariates.shape[0] != y.size:
+            raise ValueError("covariates must be n x c with one row per entry of y")
+        c = covariates.shape[1]
+        if not 1 <= c + 1 <= QMAX:
+            raise ValueError("at most %d covariates" % (QMAX - 1))
+        if not isinstance(cholesky_func, SparseCholesky):
+            raise _lib.ScilmmError("AssociationScan needs the device engine (a scilmm_amd.SparseCholesky): there is no CPU form")
+        _lib.lib()
+        torch = _device_buffers()
+        if torch is None:
+            raise _lib.ScilmmError("AssociationScan needs a GPU that torch can reach (device buffers): there is no CPU form")
+        self.torch, self.block, self.c, self.q = torch, int(block), c, c + 1
+        self.factor = fac = _final_factor(cholesky_func, mats, np.asarray(sigma2, dtype=np.float64))
+        self.sym = sym = fac.sym
+        self.n = n = sym.n
+        if y.size != n:
+            raise ValueError("y has %d entries, the matrices %d rows" % (y.size, n))
+        self._s2 = np.array(sigma2, dtype=np.float64)
+        # Q = L^-1 P [C | y]: one forward sweep, kept in HBM in the permuted order the scan kernels read
+        perm = torch.from_numpy(fac.P()).cuda()
+        dB = torch.from_numpy(np.ascontiguousarray(np.hstack([covariates, y[:, None]]))).cuda()[perm].contiguous()
+        self.dQ = torch.empty_like(dB)
+        torch.cuda.synchronize()
+        fac.solve_L_dev(C.c_void_p(dB.data_ptr()), self.q, C.c_void_p(self.dQ.data_ptr()))
+        sym.sync()
+        G = (self.dQ.T @ self.dQ).cpu().numpy()              # [w(C) | w(y)]' [w(C) | w(y)]: (c + 1) x (c + 1)
+        self.R = la.cholesky(G[:c, :c], lower=False)         # R' R = w(C)' w(C)
+        self.u = la.solve_triangular(self.R, G[:c, c], trans='T', lower=False)   # R^-T w(C)' w(y)
+        self._f = stats.f(1, n - 1)
+
+    def _stats(self, genotypes):
+        """(q + 4) x m statistics of ``scilmm_scan_block_dev`` for every marker, in chunks of whole blocks."""
+        torch, n, q, blk = self.torch, self.n, self.q, self.block
+        m = genotypes.shape[0]
+        out = np.empty((q + 4, m))
+        ld = (n + 15) // 16 * 16      # rows of the device copy start on 16-byte boundaries: every read is an aligned one
+        per = max(blk, min(m, max(1, _CHUNK_BYTES // ld)) // blk * blk)
+        dG = torch.empty((min(per, m), ld), dtype=torch.int8, device="cuda")
+        nblk = (min(per, m) + blk - 1) // blk
+        dS = torch.empty((nblk, (q + 4) * blk), dtype=torch.float64, device="cuda")
+        vp = C.c_void_p
+        for j0 in range(0, m, per):
+            mc = min(per, m - j0)
+            dG[:mc, :n].copy_(torch.from_numpy(np.ascontiguousarray(genotypes[j0:j0 + mc])))
+            torch.cuda.synchronize()
+            for b, k0 in enumerate(range(0, mc, blk)):
+                rb = min(blk, mc - k0)
+                self.factor.scan_block_dev(vp(dG.data_ptr() + k0 * ld), ld, rb, vp(self.dQ.data_ptr()), q,
+                                           vp(dS.data_ptr() + 8 * b * (q + 4) * blk))
+            self.sym.sync()
+            hS = dS.cpu().numpy()
+            for b, k0 in enumerate(range(0, mc, blk)):
+                rb = min(blk, mc - k0)
+                out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
+        return out
+
+    def __call__(self, genotypes):
+        """``genotypes``: m x n int8, marker-major, C-contiguous (0 / 1 / 2 allele counts, negative = missing; missing values
+        are mean-imputed).  Returns a dict of length-m arrays ``beta``, ``se``, ``chi2``, ``p``, ``n_obs``, ``mean``; a
+        marker without an observed value or without variation gets NaN in the first four."""
+        g = check_genotypes(genotypes, self.n)
+        if not self.factor.holds(self._s2):
+            raise _lib.ScilmmError("the resident factor no longer holds the sigma2 this scan was whitened with: build a new "
+                                   "AssociationScan")
+        m, c = g.shape[0], self.c
+        S = self._stats(g) if m else np.empty((self.q + 4, 0))
+        n_obs, mean, css, gg = S[0], S[1].copy(), S[2], S[3]
+        z = la.solve_triangular(self.R, S[4:4 + c], trans='T', lower=False) if m else np.empty((c, 0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = gg - np.sum(z * z, axis=0)
+            b = S[4 + c] - self.u.dot(z)
+            bad = (n_obs == 0) | (css == 0)
+            a = np.where(bad, np.nan, a)
+            beta, se, chi2 = b / a, 1.0 / np.sqrt(a), b * b / a
+        mean[n_obs == 0] = np.nan
+        return {"beta": beta, "se": se, "chi2": chi2, "p": self._f.sf(chi2), "n_obs": n_obs.astype(np.int64), "mean": mean}

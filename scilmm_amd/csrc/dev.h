@@ -270,6 +270,13 @@ struct Dev {
   const int64_t* d_pat_rowslot = nullptr;
   const int32_t* d_pat_rowcol = nullptr;
   int64_t n_float_atomic = 0;           // launches since the handle was created that sum with floating-point atomics
+  // marker scan (scilmm_scan_block_dev): slice partial sums of the statistics, inverse permutation (original -> permuted row)
+  double* scan_partial = nullptr;       // [slices][q + 1][RPMAX]
+  size_t scan_partial_cap = 0;          // doubles
+  const int32_t* d_iperm = nullptr;
+  hipEvent_t scan_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin | W ready | forward sweep done | statistics done
+  bool scan_pending = false;            // a scan block whose events have not been read yet (scilmm_sync)
+  double scan_ms[3] = {0.0, 0.0, 0.0};  // the last block's moments + dequantise | forward sweep | statistics (scilmm_scan_timing)
 };
 
 #define HIPCHK(call)                                                                                   \

@@ -8,8 +8,10 @@
 //   Factorization (run_factorize): prepare_shadow, assemble, prepare_profiling, early(l), late_updates(l), factor_panel(l),
 //     broadcast_tail(l), batch(grp), outside_and_deferred_early(l), exchange_status;
 //     finish_factorize waits for it, ProfRead turns the profiling events (enum ProfEvent) into scilmm_timing;
-//   Sweep (run_rhs): solve_single, solve_dist, lmul_single, lmul_dist per block of RPMAX columns, built from pull /
-//     pull_groups (deterministic mode), chain, handoff (distributed) and mark_mid.
+//   Sweep (run_rhs): solve_single (= forward_single, mark_mid, backward_single: the half-solves run one of the two),
+//     solve_dist, lmul_single, lmul_dist per block of RPMAX columns, built from pull / pull_groups (deterministic mode),
+//     chain, handoff (distributed) and mark_mid;
+//   Scan block (scilmm_scan_block_dev): the kernels of scan.hip.h around Sweep::forward_single.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +30,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "kernels.hip.h"
+#include "scan.hip.h"
 #include "dev.h"
 #include "host_threads.h"
 
@@ -706,9 +709,12 @@ struct Sweep : SweepLaunch {
     }
   }
 
-  // X = V^-1 W on one device: level sweep forward (the chain levels by k_chain), then backward
-  int solve_single() {
-    const int32_t lend = D->chain_T > 0 ? D->chain_l0 : S.nlevels;  // the chain levels are swept by k_chain
+  // the levels below the chain are swept level by level, the chain levels by k_chain
+  int32_t level_end() const { return D->chain_T > 0 ? D->chain_l0 : S.nlevels; }
+
+  // forward half, X = L^-1 W (W permuted; it is consumed): level sweep, then the chain
+  int forward_single() {
+    const int32_t lend = level_end();
     for (int32_t l = 0; l < lend; ++l) {
       const int64_t t0 = S.level_tile_ptr[l], t1 = S.level_tile_ptr[l + 1];
       const int32_t f0 = S.level_ptr[l], f1 = S.level_ptr[l + 1];
@@ -724,7 +730,12 @@ struct Sweep : SweepLaunch {
       if (D->det) pull_groups(lend, false, D->d_chain_mask);
       TRY(chain(false));
     }
-    TRY(mark_mid());
+    return SCILMM_OK;
+  }
+
+  // backward half, X = L^-T X in place: the chain, then the levels below it from the top down
+  int backward_single() {
+    const int32_t lend = level_end();
     if (D->chain_T > 0) {
       TRY(chain(true));
       // descendants below the chain: all their chain targets are final now, one read-modify-write each
@@ -738,6 +749,13 @@ struct Sweep : SweepLaunch {
       bwd_push(D->d_level_pairs + S.level_pair_ptr[l], S.level_pair_ptr[l + 1] - S.level_pair_ptr[l]);
     }
     return SCILMM_OK;
+  }
+
+  // X = V^-1 W on one device: forward, then backward
+  int solve_single() {
+    TRY(forward_single());
+    TRY(mark_mid());
+    return backward_single();
   }
 
   // X = L W on one device
@@ -812,11 +830,11 @@ struct Sweep : SweepLaunch {
   }
 };
 
-// dB/dX: device, row-major n x r, ORIGINAL row order.  mode 0: X = V^-1 B.  mode 1: X = P^T L B.
-int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mode) {
+// What every sweep call does first: complete a queued factorization, refuse a factor that is not valid, make sure the work
+// buffers exist, and report a chain sweep of an earlier call that timed out.
+int begin_rhs(scilmm_factor* fac) {
   scilmm_symbolic* sym = fac->sym;
   Dev* D = (Dev*)sym->device;
-  const Symbolic& S = *sym->S;
   if (fac->pending) {
     int stp = finish_factorize(fac, nullptr);
     if (stp != SCILMM_OK) return stp;
@@ -835,20 +853,55 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
     sym->err = "chain sweep: a workgroup timed out waiting for its predecessor (previous solve)";
     return SCILMM_ERR_DEVICE;
   }
+  return SCILMM_OK;
+}
+
+// The half-solves and the scan stand on the factor alone: refused (handle untouched) where L is not the whole story.
+int check_half(scilmm_factor* fac, const char* who) {
+  scilmm_symbolic* sym = fac->sym;
+  Dev* D = (Dev*)sym->device;
+  if (!D) {
+    sym->err = std::string(who) + ": the handle has no device state";
+    return SCILMM_ERR_STATE;
+  }
+  if (D->world > 1) {
+    sym->err = std::string(who) + ": not available on a distributed factor";
+    return SCILMM_ERR_STATE;
+  }
+  if (D->front_bits == 32) {
+    sym->err = std::string(who) + ": not available with fp32 fronts (a half-solve cannot be refined against the exact V)";
+    return SCILMM_ERR_STATE;
+  }
+  return SCILMM_OK;
+}
+
+enum RhsMode { RHS_SOLVE = 0, RHS_LMUL = 1, RHS_SOLVE_L = 2, RHS_SOLVE_LT = 3 };
+
+// dB/dX: device, row-major n x r.  RHS_SOLVE: X = V^-1 B.  RHS_LMUL: X = P^T L B.  Both in the ORIGINAL row order.
+// RHS_SOLVE_L: X = L^-1 B.  RHS_SOLVE_LT: X = L^-T B.  Both in the factor's PERMUTED row order (single device only).
+int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mode) {
+  scilmm_symbolic* sym = fac->sym;
+  Dev* D = (Dev*)sym->device;
+  const Symbolic& S = *sym->S;
+  TRY(begin_rhs(fac));
   hipStream_t st = D->stream;
   HIPCHK(hipEventRecord(D->ev[3], st));
   Sweep sw(fac, D);
+  const int32_t* perm_in = mode == RHS_SOLVE ? D->v.perm : (const int32_t*)nullptr;
+  const int32_t* perm_out = mode == RHS_SOLVE || mode == RHS_LMUL ? D->v.perm : (const int32_t*)nullptr;
   for (int32_t cbeg = 0; cbeg < r; cbeg += RPMAX) {
     sw.set_block(std::min<int>(RPMAX, r - cbeg));
     const unsigned pb = (unsigned)((sw.tot + 255) / 256);
-    // Z = P^T (L R): R is NOT permuted on the way in (SparseCholesky.py:50-51)
-    hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, sw.rp, cbeg, mode == 1 ? (const int32_t*)nullptr : D->v.perm, dB, D->W);
-    if (D->world > 1) TRY(mode == 1 ? sw.lmul_dist() : sw.solve_dist());
-    else TRY(mode == 1 ? sw.lmul_single() : sw.solve_single());
-    hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, sw.rp, cbeg, D->v.perm, D->X, dX);
+    // Z = P^T (L R): R is NOT permuted on the way in (SparseCholesky.py:50-51); the backward half works in place on X
+    hipLaunchKernelGGL(k_perm_in, dim3(pb), dim3(256), 0, st, S.n, r, sw.rp, cbeg, perm_in, dB, mode == RHS_SOLVE_LT ? D->X : D->W);
+    if (D->world > 1) TRY(mode == RHS_LMUL ? sw.lmul_dist() : sw.solve_dist());
+    else if (mode == RHS_SOLVE_L) TRY(sw.forward_single());
+    else if (mode == RHS_SOLVE_LT) { TRY(sw.mark_mid()); TRY(sw.backward_single()); }
+    else TRY(mode == RHS_LMUL ? sw.lmul_single() : sw.solve_single());
+    hipLaunchKernelGGL(k_perm_out, dim3(pb), dim3(256), 0, st, S.n, r, sw.rp, cbeg, perm_out, D->X, dX);
   }
   TRY(sw.mark_mid());
-  if (D->h_chain_err && mode == 0) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (D->h_chain_err && mode != RHS_LMUL) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(D->ev[5], st));
   HIPCHK(hipGetLastError());
   D->rhs_pending = mode;
@@ -857,7 +910,7 @@ int run_rhs(scilmm_factor* fac, const double* dB, int32_t r, double* dX, int mod
 
 int finish_rhs_timing(scilmm_symbolic* sym, Dev* D, int mode) {
   D->rhs_pending = -1;
-  if (D->chain_T > 0 && mode == 0) {
+  if (D->chain_T > 0 && mode != RHS_LMUL) {
     int32_t cerr = 0;
     HIPCHK(hipMemcpy(&cerr, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (cerr != 0) {
@@ -870,7 +923,7 @@ int finish_rhs_timing(scilmm_symbolic* sym, Dev* D, int mode) {
   float a = 0, b = 0;
   HIPCHK(hipEventElapsedTime(&a, D->ev[3], D->ev[4]));
   HIPCHK(hipEventElapsedTime(&b, D->ev[4], D->ev[5]));
-  if (mode == 0) {
+  if (mode != RHS_LMUL) {  // (a half-solve: the other half's time is that of nothing)
     D->timing.solve_fwd_ms = a;
     D->timing.solve_bwd_ms = b;
   } else {
@@ -1181,6 +1234,85 @@ int scilmm_lmul_dev(scilmm_factor* fac, const double* dR, int32_t r, double* dZ)
   if (!fac || !fac->sym || !dR || !dZ || r <= 0) return SCILMM_ERR_ARG;
   DevGuard guard(fac->sym);
   return run_rhs(fac, dR, r, dZ, 1);
+}
+
+// The half-solves: argument checks before anything is dereferenced, then the refusals, then the sweep.
+static int half_rhs(scilmm_factor* fac, const double* B, int32_t r, double* X, int mode, bool host, const char* who) {
+  if (!fac || !B || !X || r <= 0) return SCILMM_ERR_ARG;
+  if (!fac->sym) return SCILMM_ERR_ARG;
+  DevGuard guard(fac->sym);
+  int st = check_half(fac, who);
+  if (st != SCILMM_OK) return st;
+  return host ? host_rhs(fac, B, r, X, mode) : run_rhs(fac, B, r, X, mode);
+}
+
+int scilmm_solve_L(scilmm_factor* fac, const double* B, int32_t r, double* X) {
+  return half_rhs(fac, B, r, X, RHS_SOLVE_L, true, "scilmm_solve_L");
+}
+int scilmm_solve_Lt(scilmm_factor* fac, const double* B, int32_t r, double* X) {
+  return half_rhs(fac, B, r, X, RHS_SOLVE_LT, true, "scilmm_solve_Lt");
+}
+int scilmm_solve_L_dev(scilmm_factor* fac, const double* dB, int32_t r, double* dX) {
+  return half_rhs(fac, dB, r, dX, RHS_SOLVE_L, false, "scilmm_solve_L_dev");
+}
+int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double* dX) {
+  return half_rhs(fac, dB, r, dX, RHS_SOLVE_LT, false, "scilmm_solve_Lt_dev");
+}
+
+int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
+                          double* d_stats) {
+  if (!fac || !d_geno || !d_Q || !d_stats || r < 1 || r > RPMAX || q < 1 || q > SCAN_QMAX) return SCILMM_ERR_ARG;
+  if (!fac->sym || !fac->sym->S || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
+  DevGuard guard(fac->sym);
+  scilmm_symbolic* sym = fac->sym;
+  int st = check_half(fac, "scilmm_scan_block_dev");
+  if (st != SCILMM_OK) return st;
+  st = begin_rhs(fac);
+  if (st != SCILMM_OK) return st;
+  Dev* D = (Dev*)sym->device;
+  const Symbolic& S = *sym->S;
+  const int32_t n = S.n;
+  hipStream_t s0 = D->stream;
+  const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
+  // (first call on a handle, or a wider q: the one allocation of the scan; nothing is allocated per block afterwards)
+  const size_t need = (size_t)nslice * (size_t)(q + 1) * RPMAX;
+  if (D->scan_partial_cap < need) {
+    HIPCHK(hipStreamSynchronize(s0));
+    if (D->scan_partial) (void)hipFree(D->scan_partial);
+    D->scan_partial = nullptr;
+    D->scan_partial_cap = 0;
+    HIPCHK(hipMalloc((void**)&D->scan_partial, need * sizeof(double)));
+    D->scan_partial_cap = need;
+  }
+  if (!D->scan_ev[0])
+    for (auto& e : D->scan_ev) HIPCHK(hipEventCreate(&e));
+  if (!D->d_iperm) {
+    st = upload(sym, D, S.iperm, &D->d_iperm);
+    if (st != SCILMM_OK) return st;
+  }
+  Sweep sw(fac, D);
+  sw.set_block(r);
+  const int32_t rp = sw.rp;
+  HIPCHK(hipEventRecord(D->scan_ev[0], s0));
+  // rows 0..2 of the statistics: n_obs, mean, centred sum of squares (exact integer sums: no order to fix)
+  hipLaunchKernelGGL(k_scan_moments, dim3((unsigned)r), dim3(256), 0, s0, n, d_geno, ld_geno, r, d_stats);
+  // W = P (g - mean), missing = 0, columns padded to rp: each tile of individuals is written straight to its permuted rows
+  const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
+  hipLaunchKernelGGL(k_scan_dequant, dim3(tiles), dim3(256), 0, s0, n, r, rp, d_geno, ld_geno, (const int32_t*)D->d_iperm,
+                     (const double*)(d_stats + r), D->W);
+  HIPCHK(hipEventRecord(D->scan_ev[1], s0));
+  st = sw.forward_single();
+  if (st != SCILMM_OK) return st;
+  HIPCHK(hipEventRecord(D->scan_ev[2], s0));
+  // rows 3..: |w(g)|^2 and Q^T w(g) from one pass over X, in fixed row slices folded in slice order
+  const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
+  hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, rp, (const double*)D->X, d_Q, q, D->scan_partial);
+  hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_stats + 3 * (int64_t)r);
+  HIPCHK(hipEventRecord(D->scan_ev[3], s0));
+  D->scan_pending = true;
+  if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
 }
 
 int scilmm_quadforms_dev(scilmm_symbolic* sym, int32_t k, const double* dU, int32_t r, double* d_out) {
@@ -1630,6 +1762,22 @@ int scilmm_sync(scilmm_symbolic* sym) {
   DevGuard guard(sym);
   Dev* D = (Dev*)sym->device;
   HIPCHK(hipStreamSynchronize(D->stream));
+  if (D->scan_pending) {
+    D->scan_pending = false;
+    float a = 0, b = 0, c = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->scan_ev[0], D->scan_ev[1]));
+    HIPCHK(hipEventElapsedTime(&b, D->scan_ev[1], D->scan_ev[2]));
+    HIPCHK(hipEventElapsedTime(&c, D->scan_ev[2], D->scan_ev[3]));
+    D->scan_ms[0] = a;
+    D->scan_ms[1] = b;
+    D->scan_ms[2] = c;
+    if (D->h_chain_err && *D->h_chain_err != 0) {  // (the queued copy behind the block's sweep has arrived)
+      HIPCHK(hipMemset(D->d_chain_err, 0, sizeof(int32_t)));
+      *D->h_chain_err = 0;
+      sym->err = "chain sweep: a workgroup timed out waiting for its predecessor (scan block)";
+      return SCILMM_ERR_DEVICE;
+    }
+  }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
 }
@@ -1647,6 +1795,13 @@ int scilmm_last_timing(const scilmm_symbolic* sym, scilmm_timing* out) {
   D->timing.n_late_split = D->n_late_split;
   D->timing.n_float_atomic_launches = D->n_float_atomic;
   *out = D->timing;
+  return SCILMM_OK;
+}
+
+int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const Dev* D = (const Dev*)sym->device;
+  for (int i = 0; i < 3; ++i) ms[i] = D->scan_ms[i];
   return SCILMM_OK;
 }
 

@@ -1681,10 +1681,12 @@ __global__ void k_perm_in(int32_t n, int32_t r, int32_t rp, int32_t cbeg, const 
 
 __global__ void k_perm_out(int32_t n, int32_t r, int32_t rp, int32_t cbeg, const int32_t* __restrict__ perm,
                            const double* __restrict__ Xp, double* __restrict__ X) {
+  // X[perm[p]][cbeg + c] = Xp[p][c]   (perm == nullptr: identity, only drops the padding)
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)n * rp) return;
   int32_t p = (int32_t)(idx / rp), c = (int32_t)(idx - (int64_t)p * rp);
-  if (cbeg + c < r) X[(int64_t)perm[p] * r + cbeg + c] = Xp[idx];
+  const int32_t dst = perm ? perm[p] : p;
+  if (cbeg + c < r) X[(int64_t)dst * r + cbeg + c] = Xp[idx];
 }
 
 // D[M][N=c] accumulate helper for RHS kernels: one M-tile (16 rows) x ncn N-tiles (16 cols each).

@@ -32,6 +32,9 @@ void dev_free(void* p) {
   if (D->X && !D->work_external) (void)hipFree(D->X);
   if (D->IO) (void)hipFree(D->IO);
   if (D->partial) (void)hipFree(D->partial);
+  if (D->scan_partial) (void)hipFree(D->scan_partial);
+  for (auto& e : D->scan_ev)
+    if (e) (void)hipEventDestroy(e);
   if (D->d_out) (void)hipFree(D->d_out);
   for (auto& e : D->ev)
     if (e) (void)hipEventDestroy(e);

@@ -4,7 +4,8 @@ A_k values) and ``Factor`` (numeric factor with the reference's factor protocol)
 Factor protocol mirrored from what the reference touches on an sksparse Factor
 (reference scilmm/SparseCholesky.py:30,32,40,50,52,93,100; scilmm/Estimation/LMM.py:28,30,38,48-50,87,94):
 ``factor(b)``, ``factor.L()``, ``factor.P()``, ``factor.logdet()`` -- plus ``factor.lmul(R)``, the fused
-form of ``factor.L().dot(R)[argsort(P)]`` that never materialises L on the host.
+form of ``factor.L().dot(R)[argsort(P)]`` that never materialises L on the host, and the four pieces of ``factor(b)`` the
+sksparse protocol also offers: ``solve_L``, ``solve_Lt``, ``apply_P``, ``apply_Pt`` (what ``scilmm_amd.assoc`` is built on).
 """
 import ctypes as C
 import os
@@ -250,6 +251,12 @@ class Symbolic(object):
     def quadforms_dev(self, k, dU_ptr, r, dout_ptr):
         check(lib().scilmm_quadforms_dev(self._h, k, dU_ptr, r, dout_ptr), self._h)
 
+    def scan_timing(self):
+        """(moments + dequantise, forward sweep, statistics) of the last scan block in ms, after ``sync()``."""
+        ms = (C.c_double * 3)()
+        check(lib().scilmm_scan_timing(self._h, ms), self._h)
+        return tuple(ms)
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -357,6 +364,51 @@ class Factor(object):
 
     def lmul_dev(self, dR_ptr, r, dZ_ptr):
         check(lib().scilmm_lmul_dev(self._h, dR_ptr, r, dZ_ptr), self.sym._h)
+
+    # ---- the halves of factor(b) (sksparse: solve_L / solve_Lt with use_LDLt_decomposition=False, apply_P, apply_Pt):
+    #      f(b) == f.apply_Pt(f.solve_Lt(f.solve_L(f.apply_P(b)))), bit for bit on a deterministic handle
+
+    def solve_L(self, b):
+        """x with L x = b, for b of shape (n,) or (n, r) whose rows are in the factor's PERMUTED order (``apply_P(b)``); no
+        permutation is applied.  Refused (``ScilmmError``) on a distributed factor, with fp32 fronts, and after
+        ``inverse_traces`` until the next ``refactorize``."""
+        if getattr(self, "_pending", None) is not None:
+            self.wait()
+        return self._rhs(lib().scilmm_solve_L, b)
+
+    def solve_Lt(self, b):
+        """x with L^T x = b (rows in permuted order in, permuted order out); refusals as for ``solve_L``."""
+        if getattr(self, "_pending", None) is not None:
+            self.wait()
+        return self._rhs(lib().scilmm_solve_Lt, b)
+
+    def _rows(self, b):
+        b = np.asarray(b)
+        if b.ndim not in (1, 2) or b.shape[0] != self.n:
+            raise ValueError("expected %d rows" % self.n)
+        return b
+
+    def apply_P(self, b):
+        """b[P]: rows from the original order into the factor's permuted order."""
+        return self._rows(b)[self.P()]
+
+    def apply_Pt(self, b):
+        """The inverse of ``apply_P``: out[P] = b."""
+        b = self._rows(b)
+        out = np.empty_like(b)
+        out[self.P()] = b
+        return out
+
+    def solve_L_dev(self, dB_ptr, r, dX_ptr):
+        """Device-pointer ``solve_L`` (row-major n x r, PERMUTED row order); enqueues without synchronising."""
+        check(lib().scilmm_solve_L_dev(self._h, dB_ptr, r, dX_ptr), self.sym._h)
+
+    def solve_Lt_dev(self, dB_ptr, r, dX_ptr):
+        check(lib().scilmm_solve_Lt_dev(self._h, dB_ptr, r, dX_ptr), self.sym._h)
+
+    def scan_block_dev(self, dG_ptr, ld, r, dQ_ptr, q, dstats_ptr):
+        """One block of the marker scan (``scilmm_scan_block_dev``; ``scilmm_amd.assoc.AssociationScan`` is the interface)."""
+        check(lib().scilmm_scan_block_dev(self._h, dG_ptr, ld, r, dQ_ptr, q, dstats_ptr), self.sym._h)
 
     def inverse_traces(self):
         """tr(V^-1 A_k) for every matrix of the analysis, exactly: the selected inverse on the supernodal factor (Takahashi
