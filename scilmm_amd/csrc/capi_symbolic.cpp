@@ -1,6 +1,8 @@
 // C-ABI entry points for the host-side symbolic phase (no GPU needed). Declared in include/scilmm_hip.h.
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -35,16 +37,24 @@ int scilmm_symbolic_create(int32_t n, int32_t K, const int64_t* const* indptr, c
     if (opts->nd_oksep > 0) o.nd_oksep = opts->nd_oksep;
     if (opts->dense_relax != 0) o.dense_relax = o.dense_relax_wide = opts->dense_relax < 0 ? 0.0 : opts->dense_relax;  // explicit: one budget
   }
-  if (const char* t = getenv("SCILMM_TUNING"))
-    if (t[0] == '1')
-      if (const char* e = getenv("SCILMM_TAIL_WIDE")) o.dense_relax_wide = atof(e);  // flop budget of a wide tail
   if (perm_in && !opts) o.ordering = 2;
-  scilmm_symbolic* h = new scilmm_symbolic();
-  h->S = scilmm::symbolic_analyze(n, K, indptr, indices, perm_in, o);
+  // (the analysis reads its environment switches itself: scilmm::read_analysis_switches)
+  std::unique_ptr<scilmm_symbolic> h;
+  try {
+    h.reset(new scilmm_symbolic());
+    h->S = scilmm::symbolic_analyze(n, K, indptr, indices, perm_in, o);
+  } catch (const std::exception& e) {
+    // no C++ exception crosses the C boundary: the host ran out of memory or threads.  The caller gets a handle that
+    // holds the message and no analysis (every other call refuses it; scilmm_symbolic_free releases it)
+    if (!h) return SCILMM_ERR_STATE;
+    h->err = e.what();
+    *out = h.release();
+    return SCILMM_ERR_STATE;
+  }
   h->deterministic = env_deterministic();
-  *out = h;
-  if (!h->S->error.empty()) {
-    h->err = h->S->error;
+  *out = h.release();
+  if (!(*out)->S->error.empty()) {
+    (*out)->err = (*out)->S->error;
     return SCILMM_ERR_ARG;
   }
   return SCILMM_OK;
@@ -58,13 +68,17 @@ int scilmm_symbolic_save(const scilmm_symbolic* h, const char* path, uint64_t ke
 int scilmm_symbolic_load(const char* path, uint64_t key, scilmm_symbolic** out) {
   scilmm::use_host_threads();
   if (!path || !out) return SCILMM_ERR_ARG;
-  scilmm::Symbolic* S = scilmm::symbolic_load(path, key);
-  if (!S) return SCILMM_ERR_STATE;  // no file, another key / build, or a damaged image: the caller analyses afresh
-  scilmm_symbolic* h = new scilmm_symbolic();
-  h->S = S;
-  h->deterministic = env_deterministic();
-  *out = h;
-  return SCILMM_OK;
+  try {
+    std::unique_ptr<scilmm::Symbolic> S(scilmm::symbolic_load(path, key));
+    if (!S) return SCILMM_ERR_STATE;  // no file, another key / build, or a damaged image: the caller analyses afresh
+    scilmm_symbolic* h = new scilmm_symbolic();
+    h->S = S.release();
+    h->deterministic = env_deterministic();
+    *out = h;
+    return SCILMM_OK;
+  } catch (const std::exception&) {
+    return SCILMM_ERR_STATE;  // out of memory while the image was read: like a miss, nothing is kept
+  }
 }
 
 int scilmm_set_deterministic(scilmm_symbolic* h, int32_t on) {
@@ -131,10 +145,15 @@ int scilmm_symbolic_info(const scilmm_symbolic* h, scilmm_info* info) {
 int scilmm_symbolic_get(const scilmm_symbolic* h, const char* what, void* out, int64_t* count) {
   scilmm::use_host_threads();
   if (!h || !h->S || !what || !count) return SCILMM_ERR_ARG;
-  if (!h->S->combos_built && !std::strncmp(what, "combo_", 6)) scilmm::build_tile_combos(h->S, nullptr);
-  if (!std::strncmp(what, "pull_", 5)) scilmm::build_pull_schedule(h->S);
-  if (!std::strcmp(what, "pat_rowptr") || !std::strcmp(what, "pat_rowslot") || !std::strcmp(what, "pat_rowcol"))
-    if (!scilmm::build_row_index(h->S)) return SCILMM_ERR_STATE;  // (the host maps were released before the index was built)
+  try {  // the lists that are built on demand
+    if (!h->S->combos_built && !std::strncmp(what, "combo_", 6)) scilmm::build_tile_combos(h->S, nullptr);
+    if (!std::strncmp(what, "pull_", 5)) scilmm::build_pull_schedule(h->S);
+    if (!std::strcmp(what, "pat_rowptr") || !std::strcmp(what, "pat_rowslot") || !std::strcmp(what, "pat_rowcol"))
+      if (!scilmm::build_row_index(h->S)) return SCILMM_ERR_STATE;  // (the host maps were released before the index was built)
+  } catch (const std::exception& e) {
+    const_cast<scilmm_symbolic*>(h)->err = e.what();  // (the handle is const for its ANALYSIS; its message is not part of it)
+    return SCILMM_ERR_STATE;
+  }
   const Symbolic& S = *h->S;
   if (!std::strcmp(what, "dense_first")) {
     if (out) *(int32_t*)out = S.dense_first;

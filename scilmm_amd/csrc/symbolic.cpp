@@ -2,6 +2,7 @@
 // column counts, (relaxed) supernodes, supernode row structures, left-looking update schedule,
 // value-assembly maps.  See symbolic.h.  Replaces cholmod_analyze as reached from the reference at
 // scilmm/SparseCholesky.py:22-26 / scilmm/Estimation/LMM.py:20-24, but runs once per pattern.
+// (The image of an analysis on disk: symbolic_image.cpp.)
 //
 // All algorithms are written from their published descriptions (Liu 1990 elimination tree with
 // path compression; Gilbert, Ng & Peyton 1994 skeleton column counts; Ashcraft & Grimes 1989 relaxed
@@ -18,8 +19,9 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
+#include <memory>
 #include <thread>
-#include <unistd.h>
 
 namespace scilmm {
 
@@ -189,91 +191,289 @@ void fill_count(int32_t n, const int64_t* g_ptr, const int32_t* g_idx, const int
   if (colcount_out) std::memcpy(colcount_out, cc.data(), sizeof(int32_t) * (size_t)n);
 }
 
-Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, const int32_t* const* indices,
-                           const int32_t* perm_in, const SymbolicOptions& opts) {
-  use_host_threads();
-  Symbolic* S = new Symbolic();
-  S->n = n;
-  S->K = K;
-  const bool verbose = getenv("SCILMM_VERBOSE") != nullptr;
-  auto tlast = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    auto now = std::chrono::steady_clock::now();
-    if (verbose) fprintf(stderr, "[scilmm symbolic] %-28s %8.3f s\n", what, std::chrono::duration<double>(now - tlast).count());
-    tlast = now;
+// ------------------------------------------------------------------------------------------------
+// The analysis: symbolic_analyze (at the end of this section) is the list of its stages.
+
+AnalysisSwitches read_analysis_switches() {
+  AnalysisSwitches sw;
+  const char* gate = getenv("SCILMM_TUNING");
+  if (gate && gate[0] == '1') {
+    if (const char* e = getenv("SCILMM_TAIL_ELIG")) sw.tail_elig = atof(e);
+    if (const char* e = getenv("SCILMM_TAIL_DELAY")) sw.tail_delay = atoi(e);
+    if (const char* e = getenv("SCILMM_TAIL_WIDE")) sw.tail_wide = atof(e);
+  }
+  sw.verbose = getenv("SCILMM_VERBOSE") != nullptr;
+  sw.tail_dump = getenv("SCILMM_TAIL_DUMP");
+  return sw;
+}
+
+namespace {
+
+// (the order-independent hash sums that verify structural symmetry add this over the entries)
+inline uint64_t mix64(uint64_t x) {
+  x += 0x9e3779b97f4a7c15ull;
+  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+
+// Elimination tree of the permuted matrix straight from G.
+// Liu's algorithm walks the rows of the permuted matrix in order; row i' is vertex perm[i'] and its entries left of
+// the diagonal are the neighbours with a smaller new label -- no permuted copy of the pattern is needed for it.
+// The neighbour lists are filtered (smaller new label only) and relabelled on all cores, a block of rows at a time;
+// the sequential part reads the result as a stream.  nlarger[v] = neighbours with a larger label: the size of v's
+// column in the permuted pattern (unchanged by a postorder -- adjacent vertices are ancestor and descendant).
+void etree_from_g(int32_t n, const std::vector<int64_t>& gptr, const std::vector<int32_t>& gidx, const std::vector<int32_t>& perm,
+                  const std::vector<int32_t>& iperm, std::vector<int32_t>& parent, std::vector<int32_t>& nlarger) {
+  parent.assign(n, -1);
+  nlarger.assign(n, 0);
+  std::vector<int32_t> anc(n, -1);
+  constexpr int32_t BLK = 32768;
+  const int32_t nblk = (n + BLK - 1) / BLK;
+  std::vector<int32_t> buf[2], bcnt[2];
+  std::vector<int64_t> boff[2];
+  for (int h = 0; h < 2; ++h) { bcnt[h].resize(BLK); boff[h].resize(BLK + 1); }
+  auto filter_row = [&](int h, int32_t i0, int32_t i) {
+    const int32_t v = perm[i];
+    int32_t* o = buf[h].data() + boff[h][i - i0];
+    int32_t m = 0;
+    for (int64_t e = gptr[v]; e < gptr[v + 1]; ++e) {
+      const int32_t k = iperm[gidx[e]];
+      if (k < i) o[m++] = k;
+    }
+    bcnt[h][i - i0] = m;
+    nlarger[v] = (int32_t)(gptr[v + 1] - gptr[v]) - m;
   };
-  // ---------------------------------------------------------------- 1. symmetric adjacency of the union pattern
-  // G = the union pattern without its diagonal, both halves, lists ascending: every later step of the analysis (the
-  // ordering, the elimination tree, the permuted pattern) reads it by vertex, with no scatter pass of its own.
-  S->is_diag.assign(K, 1);
-  for (int32_t k = 0; k < K; ++k) {
-    bool diag = true;
-    for (int32_t i = 0; i < n && diag; ++i)
-      for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e)
-        if (indices[k][e] != i) { diag = false; break; }
-    S->is_diag[k] = diag ? 1 : 0;
-  }
-  std::vector<int64_t> gptr(n + 1, 0);
-  std::vector<int32_t> gidx;
-  // Fast path, inputs stored with both halves (what SciPy hands over): row i of G is the merged row i of the inputs,
-  // one pass over the rows on all cores.  Structural symmetry is verified by comparing an order-independent 64-bit
-  // hash sum of the lower entries (i, j) with that of the mirrored upper entries; inputs that store one half only, or
-  // unsymmetric ones, take the scatter path below, which reads the lower half alone.
-  bool have_g = false;
-  {
-    std::vector<int64_t> ub(n + 1, 0);
-    for (int32_t i = 0; i < n; ++i) {
-      int64_t len = 0;
-      for (int32_t k = 0; k < K; ++k) len += indptr[k][i + 1] - indptr[k][i];
-      ub[i + 1] = ub[i] + len;
-    }
-    std::vector<int32_t> stage(ub[n]);
-    std::vector<int32_t> cnt(n), low(n);
-    uint64_t hlo = 0, hup = 0;
-    auto mix = [](uint64_t x) {
-      x += 0x9e3779b97f4a7c15ull;
-      x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-      x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-      return x ^ (x >> 31);
-    };
-#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : hlo, hup)
-    for (int32_t i = 0; i < n; ++i) {
-      int32_t* r = stage.data() + ub[i];
-      int64_t m = 0;
-      for (int32_t k = 0; k < K; ++k)
-        for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
-          const int32_t j = indices[k][e];
-          if (j >= 0 && j < n && j != i) r[m++] = j;
+  auto consume = [&](int h, int32_t i0, int32_t i1) {
+    for (int32_t i = i0; i < i1; ++i) {
+      const int32_t* o = buf[h].data() + boff[h][i - i0];
+      for (int32_t t = 0; t < bcnt[h][i - i0]; ++t) {
+        int32_t k = o[t];
+        while (k != -1 && k < i) {
+          const int32_t nx = anc[k];
+          anc[k] = i;
+          if (nx == -1) parent[k] = i;
+          k = nx;
         }
-      bool sorted = true;
-      for (int64_t t = 1; t < m; ++t)
-        if (r[t - 1] >= r[t]) { sorted = false; break; }
-      if (!sorted) {
-        std::sort(r, r + m);
-        m = std::unique(r, r + m) - r;
       }
-      int32_t lo = 0;
-      for (int64_t t = 0; t < m; ++t) {
-        const uint32_t j = (uint32_t)r[t];
-        if (r[t] < i) { hlo += mix(((uint64_t)(uint32_t)i << 32) | j); ++lo; }
-        else hup += mix(((uint64_t)j << 32) | (uint32_t)i);
+    }
+  };
+  // block b is consumed by one thread while the others filter block b + 1
+  for (int32_t b = -1; b < nblk; ++b) {
+    const int hn = (b + 1) & 1;
+    const int32_t n0 = (b + 1) * BLK, n1 = std::min<int64_t>(n, (int64_t)(b + 2) * BLK);
+    if (b + 1 < nblk) {
+      boff[hn][0] = 0;
+      for (int32_t i = n0; i < n1; ++i) boff[hn][i - n0 + 1] = boff[hn][i - n0] + (gptr[perm[i] + 1] - gptr[perm[i]]);
+      if ((int64_t)buf[hn].size() < boff[hn][n1 - n0]) buf[hn].resize(boff[hn][n1 - n0]);
+    }
+    std::atomic<int32_t> next{n0};
+    bool consumed = false;
+#pragma omp parallel
+    {
+#ifdef _OPENMP
+      const bool consumer = omp_get_thread_num() == 0 && omp_get_num_threads() > 1;
+#else
+      const bool consumer = false;
+#endif
+      if (consumer) {
+        if (b >= 0) consume(b & 1, b * BLK, std::min<int64_t>(n, (int64_t)(b + 1) * BLK));
+        consumed = true;
+      } else if (b + 1 < nblk) {
+        for (;;) {
+          const int32_t i = next.fetch_add(64, std::memory_order_relaxed);
+          if (i >= n1) break;
+          for (int32_t q = i; q < std::min(n1, i + 64); ++q) filter_row(hn, n0, q);
+        }
       }
-      cnt[i] = (int32_t)m;
-      low[i] = lo;
     }
-    int64_t nlow = 0, nall = 0;
-    for (int32_t i = 0; i < n; ++i) { nlow += low[i]; nall += cnt[i]; }
-    if (hlo == hup && nall == 2 * nlow) {
-      for (int32_t i = 0; i < n; ++i) gptr[i + 1] = gptr[i] + cnt[i];
-      gidx.resize(gptr[n]);
-#pragma omp parallel for schedule(dynamic, 4096)
-      for (int32_t i = 0; i < n; ++i) std::copy(stage.data() + ub[i], stage.data() + ub[i] + cnt[i], gidx.begin() + gptr[i]);
-      S->nnz_pattern = nlow + n;
-      have_g = true;
-    }
+    if (!consumed && b >= 0) consume(b & 1, b * BLK, std::min<int64_t>(n, (int64_t)(b + 1) * BLK));  // team of one
   }
-  if (verbose) fprintf(stderr, "[scilmm symbolic] inputs %s\n", have_g ? "store both halves: adjacency read row by row" : "do not store both halves symmetrically: lower half scattered");
-  if (!have_g) {
+}
+
+// The true column counts (nnz(L), flops) of the FINAL order, taken again when the dense tail was moved: elimination tree
+// + postorder + skeleton counts.  Nothing in the analysis reads them (they are reported numbers), so the recount runs
+// BESIDE the rest of the analysis on a quarter of the host threads: 0.4 of the 1.7 s analysis of the 100k config, 2 of
+// 20 s at 1M.  The worker reads G, perm, iperm and the permuted pattern of the Analysis that owns it -- none of them is
+// modified or released once it runs: every stage after the start takes the Analysis const -- and writes a vector of
+// its own, which join() hands over.  The destructor joins, so that no way out of symbolic_analyze, an exception
+// included, leaves the worker behind or destroys a joinable thread.
+class Recount {
+ public:
+  ~Recount() {
+    if (worker.joinable()) worker.join();
+  }
+  bool running() const { return worker.joinable(); }
+  void start(int32_t n, const std::vector<int64_t>& gptr, const std::vector<int32_t>& gidx, const std::vector<int32_t>& perm,
+             const std::vector<int32_t>& iperm, const std::vector<int64_t>& cptr, const std::vector<int32_t>& cidx) {
+    worker = std::thread([this, n, &gptr, &gidx, &perm, &iperm, &cptr, &cidx]() {
+      try {
+#ifdef _OPENMP
+        omp_set_num_threads(std::max(1, host_threads() / 4));
+#endif
+        std::vector<int32_t> tpar, tnl, tpost;
+        etree_from_g(n, gptr, gidx, perm, iperm, tpar, tnl);
+        postorder(n, tpar, tpost);
+        column_counts(n, tpar, tpost, cptr, cidx, cc);
+      } catch (...) {
+        failed = std::current_exception();  // rethrown by join() on the main thread
+      }
+    });
+  }
+  std::vector<int32_t> join() {
+    worker.join();
+    if (failed) std::rethrow_exception(failed);
+    return std::move(cc);
+  }
+
+ private:
+  std::thread worker;
+  std::vector<int32_t> cc;
+  std::exception_ptr failed;
+};
+
+struct SN { int32_t start, end, m; int64_t zeros; };  // supernode: columns [start, end), m rows, relaxation zeros so far
+
+// Between the stages of symbolic_analyze: the inputs of one call and what a stage leaves for a later one and is not part
+// of the result.  Everything a single stage needs stays a local of that stage.
+struct Analysis {
+  const int32_t n, K;
+  const int64_t* const* const indptr;
+  const int32_t* const* const indices;
+  const int32_t* const perm_in;
+  const SymbolicOptions opts;  // (dense_relax_wide: SCILMM_TAIL_WIDE already applied)
+  const AnalysisSwitches sw;
+  Symbolic& S;
+  std::chrono::steady_clock::time_point lap_start = std::chrono::steady_clock::now();
+  void lap(const char* what) {
+    auto now = std::chrono::steady_clock::now();
+    if (sw.verbose) fprintf(stderr, "[scilmm symbolic] %-28s %8.3f s\n", what, std::chrono::duration<double>(now - lap_start).count());
+    lap_start = now;
+  }
+  // build_adjacency -> every stage that reads the pattern.  G = the union pattern without its diagonal, both halves, lists
+  // ascending: the ordering, the elimination tree and the permuted pattern read it by vertex, with no scatter pass of their own.
+  std::vector<int64_t> gptr;
+  std::vector<int32_t> gidx;
+  // order_vertices, etree_and_postorder (postorder composed), move_tail_to_end (tail relabelled): final from there on
+  std::vector<int32_t> perm, iperm;
+  std::vector<int32_t> parent, post;  // column etree and its postorder under perm
+  std::vector<int32_t> nlarger;       // per VERTEX: neighbours with a larger label under perm
+  // permuted_pattern: strict lower pattern by column under perm, rows ascending
+  std::vector<int64_t> cptr;
+  std::vector<int32_t> cidx;
+  std::vector<int32_t> cc;            // count_columns; replaced by the recount's at the join
+  // find_supernodes (relabelled by move_tail_to_end)
+  std::vector<SN> out;
+  std::vector<int32_t> snode_of;      // front of every column
+  int32_t best = 0;                   // select_dense_tail: first front of the tail-to-be (nsuper: none)
+  Recount recount;                    // (last member: joined before anything it reads is destroyed)
+};
+
+// The rows of front d below its own columns, cut into the runs that fall into the columns of ONE later front s (each run
+// is one update pair of the left-looking schedule): fn(s, t, t2) for rows [t, t2) of sn_rows, runs in ascending order.
+template <class F>
+void for_each_target_run(const Analysis& a, int32_t d, F fn) {
+  const Symbolic& S = a.S;
+  const int64_t re = S.sn_rowptr[d + 1];
+  int64_t t = S.sn_rowptr[d] + (a.out[d].end - a.out[d].start);
+  while (t < re) {
+    const int32_t s = a.snode_of[S.sn_rows[t]];
+    int64_t t2 = t;
+    while (t2 < re && a.snode_of[S.sn_rows[t2]] == s) ++t2;
+    fn(s, t, t2);
+    t = t2;
+  }
+}
+// flops of the update that a run of nq rows of a front of width w, with `below` rows after the run, sends to its target
+inline double run_flops(int32_t w, int64_t nq, int64_t below) {
+  return (double)w * ((double)nq * ((double)nq + 1.0) + 2.0 * (double)nq * (double)below);
+}
+
+// ---------------------------------------------------------------- 1. symmetric adjacency of the union pattern
+void detect_diagonal_inputs(Analysis& a) {
+  a.S.is_diag.assign(a.K, 1);
+  for (int32_t k = 0; k < a.K; ++k) {
+    bool diag = true;
+    for (int32_t i = 0; i < a.n && diag; ++i)
+      for (int64_t e = a.indptr[k][i]; e < a.indptr[k][i + 1]; ++e)
+        if (a.indices[k][e] != i) { diag = false; break; }
+    a.S.is_diag[k] = diag ? 1 : 0;
+  }
+}
+
+// Fast path, inputs stored with both halves (what SciPy hands over): row i of G is the merged row i of the inputs,
+// one pass over the rows on all cores.  Structural symmetry is verified by comparing an order-independent 64-bit
+// hash sum of the lower entries (i, j) with that of the mirrored upper entries; false (G untouched): the inputs store
+// one half only, or are unsymmetric, and take the scatter path below, which reads the lower half alone.
+bool adjacency_from_rows(Analysis& a) {
+  const int32_t n = a.n, K = a.K;
+  const int64_t* const* indptr = a.indptr;
+  const int32_t* const* indices = a.indices;
+  std::vector<int64_t> ub(n + 1, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t len = 0;
+    for (int32_t k = 0; k < K; ++k) len += indptr[k][i + 1] - indptr[k][i];
+    ub[i + 1] = ub[i] + len;
+  }
+  std::vector<int32_t> stage(ub[n]);
+  std::vector<int32_t> cnt(n), low(n);
+  uint64_t hlo = 0, hup = 0;
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : hlo, hup)
+  for (int32_t i = 0; i < n; ++i) {
+    int32_t* r = stage.data() + ub[i];
+    int64_t m = 0;
+    for (int32_t k = 0; k < K; ++k)
+      for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
+        const int32_t j = indices[k][e];
+        if (j >= 0 && j < n && j != i) r[m++] = j;
+      }
+    bool sorted = true;
+    for (int64_t t = 1; t < m; ++t)
+      if (r[t - 1] >= r[t]) { sorted = false; break; }
+    if (!sorted) {
+      std::sort(r, r + m);
+      m = std::unique(r, r + m) - r;
+    }
+    int32_t lo = 0;
+    for (int64_t t = 0; t < m; ++t) {
+      const uint32_t j = (uint32_t)r[t];
+      if (r[t] < i) { hlo += mix64(((uint64_t)(uint32_t)i << 32) | j); ++lo; }
+      else hup += mix64(((uint64_t)j << 32) | (uint32_t)i);
+    }
+    cnt[i] = (int32_t)m;
+    low[i] = lo;
+  }
+  int64_t nlow = 0, nall = 0;
+  for (int32_t i = 0; i < n; ++i) { nlow += low[i]; nall += cnt[i]; }
+  if (hlo != hup || nall != 2 * nlow) return false;
+  for (int32_t i = 0; i < n; ++i) a.gptr[i + 1] = a.gptr[i] + cnt[i];
+  a.gidx.resize(a.gptr[n]);
+#pragma omp parallel for schedule(dynamic, 4096)
+  for (int32_t i = 0; i < n; ++i) std::copy(stage.data() + ub[i], stage.data() + ub[i] + cnt[i], a.gidx.begin() + a.gptr[i]);
+  a.S.nnz_pattern = nlow + n;
+  return true;
+}
+
+// row i of the union pattern's lower half, diagonal included: ascending, without duplicates
+void merged_lower_row(const Analysis& a, int32_t i, std::vector<int32_t>& row) {
+  row.assign(1, i);
+  for (int32_t k = 0; k < a.K; ++k)
+    for (int64_t e = a.indptr[k][i]; e < a.indptr[k][i + 1]; ++e) {
+      const int32_t j = a.indices[k][e];
+      if (j < 0 || j >= a.n) continue;
+      if (j <= i) row.push_back(j);
+    }
+  std::sort(row.begin(), row.end());
+  row.erase(std::unique(row.begin(), row.end()), row.end());
+}
+
+// Scatter path: the merged lower half U first (counted, then filled), G from it on all cores: the lower half of a vertex
+// is its own row; the upper half is counted and filled with relaxed atomics and then sorted, so the result does not
+// depend on the thread schedule.
+void adjacency_from_lower_half(Analysis& a) {
+  const int32_t n = a.n;
+  std::vector<int64_t>& gptr = a.gptr;
+  std::vector<int32_t>& gidx = a.gidx;
   std::vector<int64_t> uptr(n + 1, 0);
   std::vector<int32_t> uidx;
   {
@@ -281,76 +481,66 @@ Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, c
 #pragma omp parallel for schedule(dynamic, 1024)
     for (int32_t i = 0; i < n; ++i) {
       std::vector<int32_t> tmp;
-      tmp.push_back(i);
-      for (int32_t k = 0; k < K; ++k)
-        for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
-          int32_t j = indices[k][e];
-          if (j < 0 || j >= n) continue;
-          if (j <= i) tmp.push_back(j);
-        }
-      std::sort(tmp.begin(), tmp.end());
-      cnt[i] = std::unique(tmp.begin(), tmp.end()) - tmp.begin();
+      merged_lower_row(a, i, tmp);
+      cnt[i] = (int64_t)tmp.size();
     }
     for (int32_t i = 0; i < n; ++i) uptr[i + 1] = uptr[i] + cnt[i];
     uidx.resize(uptr[n]);
 #pragma omp parallel for schedule(dynamic, 1024)
     for (int32_t i = 0; i < n; ++i) {
       std::vector<int32_t> tmp;
-      tmp.push_back(i);
-      for (int32_t k = 0; k < K; ++k)
-        for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
-          int32_t j = indices[k][e];
-          if (j < 0 || j >= n) continue;
-          if (j <= i) tmp.push_back(j);
-        }
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+      merged_lower_row(a, i, tmp);
       std::copy(tmp.begin(), tmp.end(), uidx.begin() + uptr[i]);
     }
   }
-  S->nnz_pattern = uptr[n];
-
-  // G = the union pattern without its diagonal, both halves, lists ascending: every later step of the analysis (the
-  // ordering, the elimination tree, the permuted pattern) reads it by vertex, with no scatter pass of its own.
-  // Built on all cores: the lower half of a vertex is its own row; the upper half is counted and filled with relaxed
-  // atomics and then sorted, so the result does not depend on the thread schedule.
-  {
-    std::vector<int64_t> up(n, 0);
+  a.S.nnz_pattern = uptr[n];
+  std::vector<int64_t> up(n, 0);
 #pragma omp parallel for schedule(dynamic, 4096) num_threads(BUCKET_THREADS)
-    for (int32_t i = 0; i < n; ++i)
-      for (int64_t e = uptr[i]; e < uptr[i + 1]; ++e) {
-        const int32_t j = uidx[e];
-        if (j != i) __atomic_fetch_add(&up[j], 1, __ATOMIC_RELAXED);
-      }
-    for (int32_t i = 0; i < n; ++i) gptr[i + 1] = gptr[i] + (uptr[i + 1] - uptr[i] - 1) + up[i];
-    gidx.resize(gptr[n]);
-    std::vector<int64_t> fill(n);
-#pragma omp parallel for schedule(dynamic, 4096)
-    for (int32_t i = 0; i < n; ++i) {
-      int64_t f = gptr[i];
-      for (int64_t e = uptr[i]; e < uptr[i + 1]; ++e)
-        if (uidx[e] != i) gidx[f++] = uidx[e];
-      fill[i] = f;
+  for (int32_t i = 0; i < n; ++i)
+    for (int64_t e = uptr[i]; e < uptr[i + 1]; ++e) {
+      const int32_t j = uidx[e];
+      if (j != i) __atomic_fetch_add(&up[j], 1, __ATOMIC_RELAXED);
     }
+  for (int32_t i = 0; i < n; ++i) gptr[i + 1] = gptr[i] + (uptr[i + 1] - uptr[i] - 1) + up[i];
+  gidx.resize(gptr[n]);
+  std::vector<int64_t> fill(n);
+#pragma omp parallel for schedule(dynamic, 4096)
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t f = gptr[i];
+    for (int64_t e = uptr[i]; e < uptr[i + 1]; ++e)
+      if (uidx[e] != i) gidx[f++] = uidx[e];
+    fill[i] = f;
+  }
 #pragma omp parallel for schedule(dynamic, 4096) num_threads(BUCKET_THREADS)
-    for (int32_t i = 0; i < n; ++i)
-      for (int64_t e = uptr[i]; e < uptr[i + 1]; ++e) {
-        const int32_t j = uidx[e];
-        if (j != i) gidx[__atomic_fetch_add(&fill[j], 1, __ATOMIC_RELAXED)] = i;
-      }
+  for (int32_t i = 0; i < n; ++i)
+    for (int64_t e = uptr[i]; e < uptr[i + 1]; ++e) {
+      const int32_t j = uidx[e];
+      if (j != i) gidx[__atomic_fetch_add(&fill[j], 1, __ATOMIC_RELAXED)] = i;
+    }
 #pragma omp parallel for schedule(dynamic, 1024)
-    for (int32_t i = 0; i < n; ++i) std::sort(gidx.begin() + (gptr[i + 1] - up[i]), gidx.begin() + gptr[i + 1]);
-    std::vector<int32_t>().swap(uidx);
-  }
-  }
-  lap("symmetric adjacency");
-  std::vector<int32_t> perm(n);
+  for (int32_t i = 0; i < n; ++i) std::sort(gidx.begin() + (gptr[i + 1] - up[i]), gidx.begin() + gptr[i + 1]);
+}
+
+void build_adjacency(Analysis& a) {
+  a.gptr.assign((size_t)a.n + 1, 0);
+  const bool have_g = adjacency_from_rows(a);
+  if (a.sw.verbose) fprintf(stderr, "[scilmm symbolic] inputs %s\n", have_g ? "store both halves: adjacency read row by row" : "do not store both halves symmetrically: lower half scattered");
+  if (!have_g) adjacency_from_lower_half(a);
+}
+
+// ---------------------------------------------------------------- 2. ordering
+// false: the user's permutation is refused, S.error says why
+bool order_vertices(Analysis& a) {
+  const int32_t n = a.n;
+  const SymbolicOptions& opts = a.opts;
+  std::vector<int32_t>& perm = a.perm;
+  perm.resize(n);
   if (opts.ordering == 2) {
-    if (!perm_in) { S->error = "user ordering requested but no permutation given"; return S; }
+    if (!a.perm_in) { a.S.error = "user ordering requested but no permutation given"; return false; }
     std::vector<uint8_t> seen(n, 0);
     for (int32_t i = 0; i < n; ++i) {
-      int32_t p = perm_in[i];
-      if (p < 0 || p >= n || seen[p]) { S->error = "invalid user permutation"; return S; }
+      int32_t p = a.perm_in[i];
+      if (p < 0 || p >= n || seen[p]) { a.S.error = "invalid user permutation"; return false; }
       seen[p] = 1;
       perm[i] = p;
     }
@@ -360,108 +550,37 @@ Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, c
     NdOptions ndo;
     ndo.oksep = opts.nd_oksep;
     NdStats nds;
-    nd_order(n, gptr.data(), gidx.data(), perm.data(), ndo, &nds);
-    if (verbose)
+    nd_order(n, a.gptr.data(), a.gidx.data(), perm.data(), ndo, &nds);
+    if (a.sw.verbose)
       fprintf(stderr, "[scilmm symbolic] nested dissection: %d -> %d compressed vertices, %lld separators, largest %lld\n", n,
               nds.n_compressed, (long long)nds.n_separators, (long long)nds.top_separator);
     if (opts.ordering == 4) {
       // keep whichever ordering gives fewer factor flops (elimination tree + column counts only: cheap)
       std::vector<int32_t> p2(n);
-      amd_order(n, gptr.data(), gidx.data(), p2.data(), opts.amd_dense);
+      amd_order(n, a.gptr.data(), a.gidx.data(), p2.data(), opts.amd_dense);
       double f_nd = 0, f_amd = 0;
-      fill_count(n, gptr.data(), gidx.data(), perm.data(), nullptr, &f_nd, nullptr, nullptr);
-      fill_count(n, gptr.data(), gidx.data(), p2.data(), nullptr, &f_amd, nullptr, nullptr);
-      if (verbose) fprintf(stderr, "[scilmm symbolic] factor flops: nested dissection %.4g, minimum degree %.4g\n", f_nd, f_amd);
+      fill_count(n, a.gptr.data(), a.gidx.data(), perm.data(), nullptr, &f_nd, nullptr, nullptr);
+      fill_count(n, a.gptr.data(), a.gidx.data(), p2.data(), nullptr, &f_amd, nullptr, nullptr);
+      if (a.sw.verbose) fprintf(stderr, "[scilmm symbolic] factor flops: nested dissection %.4g, minimum degree %.4g\n", f_nd, f_amd);
       if (f_amd < f_nd) perm.swap(p2);
     }
   } else {
-    amd_order(n, gptr.data(), gidx.data(), perm.data(), opts.amd_dense);
+    amd_order(n, a.gptr.data(), a.gidx.data(), perm.data(), opts.amd_dense);
   }
-  std::vector<int32_t> iperm(n);
-  for (int32_t i = 0; i < n; ++i) iperm[perm[i]] = i;
+  a.iperm.resize(n);
+  for (int32_t i = 0; i < n; ++i) a.iperm[perm[i]] = i;
+  return true;
+}
 
-  lap("ordering");
-  // ---------------------------------------------------------------- 3. etree + postorder straight from G
-  // Liu's algorithm walks the rows of the permuted matrix in order; row i' is vertex perm[i'] and its entries left of
-  // the diagonal are the neighbours with a smaller new label -- no permuted copy of the pattern is needed for it.
-  // The neighbour lists are filtered (smaller new label only) and relabelled on all cores, a block of rows at a time;
-  // the sequential part reads the result as a stream.  nlarger[v] = neighbours with a larger label: the size of v's
-  // column in the permuted pattern (unchanged by the postorder below -- adjacent vertices are ancestor and descendant).
-  std::vector<int32_t> parent(n, -1);
-  std::vector<int32_t> nlarger(n);
-  auto etree_from_g = [&](const std::vector<int32_t>& perm, const std::vector<int32_t>& iperm, std::vector<int32_t>& parent,
-                          std::vector<int32_t>& nlarger) {
-    parent.assign(n, -1);
-    nlarger.assign(n, 0);
-    std::vector<int32_t> anc(n, -1);
-    constexpr int32_t BLK = 32768;
-    const int32_t nblk = (n + BLK - 1) / BLK;
-    std::vector<int32_t> buf[2], bcnt[2];
-    std::vector<int64_t> boff[2];
-    for (int h = 0; h < 2; ++h) { bcnt[h].resize(BLK); boff[h].resize(BLK + 1); }
-    auto filter_row = [&](int h, int32_t i0, int32_t i) {
-      const int32_t v = perm[i];
-      int32_t* o = buf[h].data() + boff[h][i - i0];
-      int32_t m = 0;
-      for (int64_t e = gptr[v]; e < gptr[v + 1]; ++e) {
-        const int32_t k = iperm[gidx[e]];
-        if (k < i) o[m++] = k;
-      }
-      bcnt[h][i - i0] = m;
-      nlarger[v] = (int32_t)(gptr[v + 1] - gptr[v]) - m;
-    };
-    auto consume = [&](int h, int32_t i0, int32_t i1) {
-      for (int32_t i = i0; i < i1; ++i) {
-        const int32_t* o = buf[h].data() + boff[h][i - i0];
-        for (int32_t t = 0; t < bcnt[h][i - i0]; ++t) {
-          int32_t k = o[t];
-          while (k != -1 && k < i) {
-            const int32_t nx = anc[k];
-            anc[k] = i;
-            if (nx == -1) parent[k] = i;
-            k = nx;
-          }
-        }
-      }
-    };
-    // block b is consumed by one thread while the others filter block b + 1
-    for (int32_t b = -1; b < nblk; ++b) {
-      const int hn = (b + 1) & 1;
-      const int32_t n0 = (b + 1) * BLK, n1 = std::min<int64_t>(n, (int64_t)(b + 2) * BLK);
-      if (b + 1 < nblk) {
-        boff[hn][0] = 0;
-        for (int32_t i = n0; i < n1; ++i) boff[hn][i - n0 + 1] = boff[hn][i - n0] + (gptr[perm[i] + 1] - gptr[perm[i]]);
-        if ((int64_t)buf[hn].size() < boff[hn][n1 - n0]) buf[hn].resize(boff[hn][n1 - n0]);
-      }
-      std::atomic<int32_t> next{n0};
-      bool consumed = false;
-#pragma omp parallel
-      {
-#ifdef _OPENMP
-        const bool consumer = omp_get_thread_num() == 0 && omp_get_num_threads() > 1;
-#else
-        const bool consumer = false;
-#endif
-        if (consumer) {
-          if (b >= 0) consume(b & 1, b * BLK, std::min<int64_t>(n, (int64_t)(b + 1) * BLK));
-          consumed = true;
-        } else if (b + 1 < nblk) {
-          for (;;) {
-            const int32_t i = next.fetch_add(64, std::memory_order_relaxed);
-            if (i >= n1) break;
-            for (int32_t q = i; q < std::min(n1, i + 64); ++q) filter_row(hn, n0, q);
-          }
-        }
-      }
-      if (!consumed && b >= 0) consume(b & 1, b * BLK, std::min<int64_t>(n, (int64_t)(b + 1) * BLK));  // team of one
-    }
-  };
-  etree_from_g(perm, iperm, parent, nlarger);
-  std::vector<int32_t> post;
+// ---------------------------------------------------------------- 3. etree + postorder straight from G
+void etree_and_postorder(Analysis& a) {
+  const int32_t n = a.n;
+  std::vector<int32_t>&perm = a.perm, &iperm = a.iperm, &parent = a.parent, &post = a.post;
+  etree_from_g(n, a.gptr, a.gidx, perm, iperm, parent, a.nlarger);
   postorder(n, parent, post);
   // A user-supplied permutation is honoured exactly (parity with an oracle factor of the same P);
   // otherwise the ordering is composed with the etree postorder (same fill, contiguous supernodes).
-  if (opts.ordering != 2) {
+  if (a.opts.ordering != 2) {
     std::vector<int32_t> perm2(n), pinv(n);
     for (int32_t k = 0; k < n; ++k) {
       perm2[k] = perm[post[k]];
@@ -474,40 +593,51 @@ Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, c
     for (int32_t i = 0; i < n; ++i) iperm[perm[i]] = i;
     std::iota(post.begin(), post.end(), 0);
   }
-  lap("etree+postorder");
-  // ---------------------------------------------------------------- 4. permuted strict-lower pattern by column
-  // column c = vertex perm[c]; its rows are the neighbours with a larger new label, sorted (column by column, no scatter)
-  std::vector<int64_t> cptr(n + 1, 0);
-  std::vector<int32_t> cidx;
-  {
-    for (int32_t c = 0; c < n; ++c) cptr[c + 1] = cptr[c] + nlarger[perm[c]];
-    cidx.resize(cptr[n]);
-#pragma omp parallel for schedule(dynamic, 1024)
-    for (int32_t c = 0; c < n; ++c) {
-      const int32_t v = perm[c];
-      int64_t f = cptr[c];
-      for (int64_t e = gptr[v]; e < gptr[v + 1]; ++e) {
-        const int32_t r = iperm[gidx[e]];
-        if (r > c) cidx[f++] = r;
-      }
-      std::sort(cidx.begin() + cptr[c], cidx.begin() + cptr[c + 1]);
-    }
-  }
-  lap("permuted pattern");
-  // ---------------------------------------------------------------- 5. column counts
-  std::vector<int32_t> cc;
-  column_counts(n, parent, post, cptr, cidx, cc);
-  S->nnzL = 0;
-  S->flops = 0;
-  for (int32_t j = 0; j < n; ++j) {
-    S->nnzL += cc[j];
-    S->flops += (double)cc[j] * (double)cc[j];
-  }
+}
 
-  lap("column counts");
-  // ---------------------------------------------------------------- 6. supernodes (fundamental, then relaxed)
-  struct SN { int32_t start, end, m; int64_t zeros; };
-  std::vector<SN> out;
+// ---------------------------------------------------------------- 4. permuted strict-lower pattern by column
+// column c = vertex perm[c]; its rows are the neighbours with a larger new label (nlarger[perm[c]] of them), sorted
+// (column by column, straight from G, no scatter)
+void permuted_pattern(Analysis& a) {
+  const int32_t n = a.n;
+  std::vector<int64_t>& cptr = a.cptr;
+  std::vector<int32_t>& cidx = a.cidx;
+  cptr.assign((size_t)n + 1, 0);
+  for (int32_t c = 0; c < n; ++c) cptr[c + 1] = cptr[c] + a.nlarger[a.perm[c]];
+  cidx.resize(cptr[n]);
+#pragma omp parallel for schedule(dynamic, 1024)
+  for (int32_t c = 0; c < n; ++c) {
+    const int32_t v = a.perm[c];
+    int64_t f = cptr[c];
+    for (int64_t e = a.gptr[v]; e < a.gptr[v + 1]; ++e) {
+      const int32_t r = a.iperm[a.gidx[e]];
+      if (r > c) cidx[f++] = r;
+    }
+    std::sort(cidx.begin() + cptr[c], cidx.begin() + cptr[c + 1]);
+  }
+}
+
+// ---------------------------------------------------------------- 5. column counts
+void report_column_counts(const std::vector<int32_t>& cc, Symbolic& S) {
+  S.nnzL = 0;
+  S.flops = 0;
+  for (int32_t c : cc) {
+    S.nnzL += c;
+    S.flops += (double)c * (double)c;
+  }
+}
+
+void count_columns(Analysis& a) {
+  column_counts(a.n, a.parent, a.post, a.cptr, a.cidx, a.cc);
+  report_column_counts(a.cc, a.S);
+}
+
+// ---------------------------------------------------------------- 6. supernodes (fundamental, then relaxed)
+void find_supernodes(Analysis& a) {
+  const int32_t n = a.n;
+  const SymbolicOptions& opts = a.opts;
+  const std::vector<int32_t>&parent = a.parent, &cc = a.cc;
+  std::vector<SN>& out = a.out;
   {
     int32_t j = 0;
     std::vector<int32_t> nchild(n, 0);
@@ -555,648 +685,686 @@ Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, c
     }
     out.swap(sp);
   }
-  int32_t ns = (int32_t)out.size();
-  S->nsuper = ns;
-  S->sn_start.resize(ns + 1);
-  for (int32_t s = 0; s < ns; ++s) S->sn_start[s] = out[s].start;
-  S->sn_start[ns] = n;
-  std::vector<int32_t> snode_of(n);
+  const int32_t ns = (int32_t)out.size();
+  a.S.nsuper = ns;
+  a.S.sn_start.resize(ns + 1);
+  for (int32_t s = 0; s < ns; ++s) a.S.sn_start[s] = out[s].start;
+  a.S.sn_start[ns] = n;
+  a.snode_of.resize(n);
   for (int32_t s = 0; s < ns; ++s)
-    for (int32_t j = out[s].start; j < out[s].end; ++j) snode_of[j] = s;
+    for (int32_t j = out[s].start; j < out[s].end; ++j) a.snode_of[j] = s;
+}
 
-  lap("supernodes");
-  // ---------------------------------------------------------------- 7. row structure of every supernode
-  S->sn_rowptr.assign(ns + 1, 0);
-  S->sn_parent.assign(ns, -1);
-  {
-    // rows contributed by the input pattern itself (the columns of A inside the front), on all cores; what is left
-    // for the sequential sweep below is the merge of the children's row lists (a child always precedes its parent)
-    std::vector<std::vector<int32_t>> arows(ns);
+// ---------------------------------------------------------------- 7. row structure of every supernode
+void front_row_structures(Analysis& a) {
+  const int32_t n = a.n, ns = a.S.nsuper;
+  Symbolic& S = a.S;
+  const std::vector<SN>& out = a.out;
+  const std::vector<int64_t>& cptr = a.cptr;
+  const std::vector<int32_t>& cidx = a.cidx;
+  S.sn_rowptr.assign(ns + 1, 0);
+  S.sn_parent.assign(ns, -1);
+  // rows contributed by the input pattern itself (the columns of A inside the front), on all cores; what is left
+  // for the sequential sweep below is the merge of the children's row lists (a child always precedes its parent)
+  std::vector<std::vector<int32_t>> arows(ns);
 #pragma omp parallel
-    {
-      std::vector<int32_t> mk(n, -1);
+  {
+    std::vector<int32_t> mk(n, -1);
 #pragma omp for schedule(dynamic, 64)
-      for (int32_t s = 0; s < ns; ++s) {
-        const int32_t c0 = out[s].start, c1 = out[s].end;
-        std::vector<int32_t>& a = arows[s];
-        for (int32_t j = c0; j < c1; ++j)
-          for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) {
-            const int32_t i = cidx[e];
-            if (i >= c1 && mk[i] != s) { mk[i] = s; a.push_back(i); }
-          }
-      }
-    }
-    std::vector<int32_t> chead(ns, -1), cnext(ns, -1);
-    std::vector<int32_t> mark(n, -1);
-    std::vector<int32_t> tmp;
-    S->sn_rows.reserve((size_t)(S->nnzL / 4 + n));
     for (int32_t s = 0; s < ns; ++s) {
-      int32_t c0 = out[s].start, c1 = out[s].end;
-      tmp.swap(arows[s]);
-      std::vector<int32_t>().swap(arows[s]);
-      for (int32_t i : tmp) mark[i] = s;
-      for (int32_t c = chead[s]; c != -1; c = cnext[c]) {
-        int64_t b = S->sn_rowptr[c], e2 = S->sn_rowptr[c + 1];
-        int32_t wc = out[c].end - out[c].start;
-        for (int64_t e = b + wc; e < e2; ++e) {
-          int32_t i = S->sn_rows[e];
-          if (i >= c1 && mark[i] != s) { mark[i] = s; tmp.push_back(i); }
+      const int32_t c0 = out[s].start, c1 = out[s].end;
+      std::vector<int32_t>& ar = arows[s];
+      for (int32_t j = c0; j < c1; ++j)
+        for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) {
+          const int32_t i = cidx[e];
+          if (i >= c1 && mk[i] != s) { mk[i] = s; ar.push_back(i); }
         }
-      }
-      for (int32_t j = c0; j < c1; ++j) S->sn_rows.push_back(j);
-      const size_t first = S->sn_rows.size();
-      if ((int64_t)tmp.size() * 16 > (int64_t)(n - c1)) {
-        // long list (the fronts of the trailing clique hold most of the later columns): read it off the marks
-        for (int32_t i = c1; i < n; ++i)
-          if (mark[i] == s) S->sn_rows.push_back(i);
-      } else {
-        std::sort(tmp.begin(), tmp.end());
-        S->sn_rows.insert(S->sn_rows.end(), tmp.begin(), tmp.end());
-      }
-      S->sn_rowptr[s + 1] = (int64_t)S->sn_rows.size();
-      if (!tmp.empty()) {
-        int32_t p = snode_of[S->sn_rows[first]];
-        S->sn_parent[s] = p;
-        cnext[s] = chead[p];
-        chead[p] = s;
-      }
-      tmp.clear();
     }
   }
-  lap("row structures");
-  // ---------------------------------------------------------------- 7a. dense tail: which fronts
-  // The top of a pedigree factor (16.6k columns at the 100k config, 170k at 1M; > 75 % / > 99 % of the flops) consists
-  // of fronts whose row lists are "almost every later column".  Padding those lists to EVERY later column (explicit
-  // zeros, like relaxed amalgamation) turns that part into one dense lower-triangular matrix cut into block columns:
-  // updates inside it need no index lists, no descriptors and no gather.
-  // The tail T is an ancestor-closed set of fronts, grown from the roots of the supernodal tree downwards: among the
-  // fronts whose parent is already in T the one with the longest true row list is taken next, as long as its own list
-  // fills at least half of its padded one and the padded flop count of the whole tail stays within dense_relax of the
-  // true one.  T need not be a chain of the tree: at the 1M config two chains of near-dense fronts (45 x 128 columns
-  // with 126k rows each beside the main one) merge 46 levels above the tail's start; as a side branch their updates
-  // of the tail went through the gather path at 11 TFLOP/s (a fifth of the factorization time), inside T they are
-  // k_dense work.  The fronts of T are moved to the end of the elimination order (children still precede parents, so
-  // the fill is unchanged) in the reverse order in which they were taken.
-  // A user-supplied permutation is never changed: then T is the trailing chain (parent = next front) only.
-  S->dense_first = ns;
-  int32_t best = ns;
-  std::thread recount;  // (column counts of the final order, when the tail is moved: joined before the return)
-  if (opts.dense_relax > 0.0 && opts.ordering == 2) {
-    double fl_dense = 0.0, fl_true = 0.0;
-    for (int32_t q = ns - 1; q >= 0; --q) {
-      if (q < ns - 1 && S->sn_parent[q] != q + 1) break;
-      const double w = out[q].end - out[q].start, mt = (double)(S->sn_rowptr[q + 1] - S->sn_rowptr[q]), md = (double)(n - out[q].start);
-      fl_dense += w * md * md;
-      fl_true += w * mt * mt;
-      if (fl_dense <= opts.dense_relax * fl_true) best = q;
-      else if (fl_dense > 1.5 * fl_true) break;
-    }
-  } else if (opts.dense_relax > 0.0) {
-    std::vector<int32_t> chead(ns, -1), cnext(ns, -1);
-    for (int32_t q = 0; q < ns; ++q)
-      if (S->sn_parent[q] != -1) { cnext[q] = chead[S->sn_parent[q]]; chead[S->sn_parent[q]] = q; }
-    std::priority_queue<std::pair<int64_t, int32_t>> heap;  // (true rows, front): longest list first, then the later front
-    for (int32_t q = 0; q < ns; ++q)
-      if (S->sn_parent[q] == -1) heap.push({S->sn_rowptr[q + 1] - S->sn_rowptr[q], q});
-    std::vector<int32_t> taken;
-    double fl_dense = 0.0, fl_true = 0.0;
-    int64_t cols_after = 0, best_cols = 0, wide_cols = 0;
-    double best_ratio = 0.0, wide_ratio = 0.0;
-    size_t nbest = 0, nwide = 0;
-    const char* tun = getenv("SCILMM_TUNING");
-    const char* eel = (tun && tun[0] == '1') ? getenv("SCILMM_TAIL_ELIG") : nullptr;
-    const double tail_elig = eel ? atof(eel) : 0.5;
-    FILE* tail_dump = getenv("SCILMM_TAIL_DUMP") ? fopen(getenv("SCILMM_TAIL_DUMP"), "w") : nullptr;  // diagnostic: every candidate
-    if (tail_dump) fprintf(tail_dump, "taken,front,w,true_rows,padded_rows,fl_dense_before,fl_true_before\n");
-    while (!heap.empty()) {
-      const int32_t q = heap.top().second;
-      heap.pop();
-      const double w = out[q].end - out[q].start, mt = (double)(S->sn_rowptr[q + 1] - S->sn_rowptr[q]), md = (double)cols_after + w;
-      if (tail_dump) fprintf(tail_dump, "%d,%d,%.0f,%.0f,%.0f,%.6g,%.6g\n", (int)taken.size(), q, w, mt, md, fl_dense, fl_true);
-      // (0.5: padding such a front costs at most 4 x its true flops, the ratio between the dense and the gather kernel.
-      // SCILMM_TUNING=1 SCILMM_TAIL_ELIG=x: at 1M 0.3 takes 27 more fronts, starts the tail 4 levels earlier -- fewer
-      // fronts behind k_outside, 7 x the cells -- and is slower, 30.2 vs 29.6 s.)
-      if (mt < tail_elig * md) continue;  // its list only gets relatively shorter as T grows: never eligible again
-      fl_dense += w * md * md;
-      fl_true += w * mt * mt;
-      taken.push_back(q);
-      cols_after += (int64_t)w;
-      if (fl_dense <= opts.dense_relax * fl_true) { nbest = taken.size(); best_cols = cols_after; best_ratio = fl_dense / fl_true; }
-      if (fl_dense <= opts.dense_relax_wide * fl_true) { nwide = taken.size(); wide_cols = cols_after; wide_ratio = fl_dense / fl_true; }
-      if (fl_dense > std::max(1.5, opts.dense_relax_wide) * fl_true) break;
-      for (int32_t c = chead[q]; c != -1; c = cnext[c]) heap.push({S->sn_rowptr[c + 1] - S->sn_rowptr[c], c});
-    }
-    if (tail_dump) fclose(tail_dump);
-    if (best_cols >= opts.dense_wide_cols && nwide > nbest) { nbest = nwide; best_cols = wide_cols; best_ratio = wide_ratio; }
-    if (nbest >= 4) {
-      taken.resize(nbest);
-      std::reverse(taken.begin(), taken.end());
-      best = ns - (int32_t)nbest;
-      // The top of T is (all but) a clique: every front's list holds >= 99 % of the later columns (1200 of the 1393
-      // fronts at the 1M config, fill 0.997 - 1.000) and is padded to all of them anyway.  The structure of every
-      // column BELOW that region depends only on which columns precede it, not on the order inside the region, so the
-      // region's columns may be sorted freely: by the number of lower tail fronts that have them as a row.  What a lower
-      // front does NOT reach (12 - 50 % of the region for the fronts below it at 1M) then sits together at the region's
-      // start, as whole 128-column blocks that the dense update can skip (tail_blk below), instead of being spread over
-      // every block as padding.  (The true fill inside the region changes by a fraction of a percent with its order:
-      // the column counts are taken again for the final order.)
-      size_t ncl = 0;
-      {
-        int64_t cols = 0;
-        for (size_t t = nbest; t-- > 0;) {
-          const int32_t q = taken[t];
-          const int64_t w = out[q].end - out[q].start;
-          if ((double)(S->sn_rowptr[q + 1] - S->sn_rowptr[q]) < 0.99 * (double)(cols + w)) break;
-          cols += w;
-          ++ncl;
-        }
-      }
-      const size_t nlow = nbest - ncl;
-      std::vector<int32_t> clique_cols;  // old labels in their new order
-      if (ncl >= 2) {
-        std::vector<uint8_t> in_cl(ns, 0);
-        for (size_t t = nlow; t < nbest; ++t) in_cl[taken[t]] = 1;
-        std::vector<int32_t> cnt(n, 0);
-        for (size_t t = 0; t < nlow; ++t) {
-          const int32_t q = taken[t];
-          for (int64_t e = S->sn_rowptr[q] + (out[q].end - out[q].start); e < S->sn_rowptr[q + 1]; ++e)
-            if (in_cl[snode_of[S->sn_rows[e]]]) cnt[S->sn_rows[e]]++;
-        }
-        for (size_t t = nlow; t < nbest; ++t)
-          for (int32_t j = out[taken[t]].start; j < out[taken[t]].end; ++j) clique_cols.push_back(j);
-        if (nlow > 0) std::stable_sort(clique_cols.begin(), clique_cols.end(), [&](int32_t x, int32_t y) { return cnt[x] < cnt[y]; });
-      }
-      // new front order = the others as they are, then T; new labels front by front (clique: column by column)
-      std::vector<uint8_t> inT(ns, 0);
-      for (int32_t q : taken) inT[q] = 1;
-      std::vector<int32_t> order;
-      order.reserve(ns);
-      for (int32_t q = 0; q < ns; ++q)
-        if (!inT[q]) order.push_back(q);
-      order.insert(order.end(), taken.begin(), taken.end());
-      std::vector<int32_t> newlab(n), newsn(ns);
-      std::vector<SN> out2(ns);
-      const int32_t k_cl = ncl >= 2 ? ns - (int32_t)ncl : ns;  // first clique front (new index)
-      {
-        int32_t c = 0;
-        size_t ci = 0;
-        for (int32_t k = 0; k < ns; ++k) {
-          const int32_t q = order[k];
-          newsn[q] = k;
-          out2[k] = out[q];
-          out2[k].start = c;
-          const int32_t w = out[q].end - out[q].start;
-          if (k >= k_cl) {
-            for (int32_t t = 0; t < w; ++t) newlab[clique_cols[ci++]] = c++;
-          } else {
-            for (int32_t j = out[q].start; j < out[q].end; ++j) newlab[j] = c++;
-          }
-          out2[k].end = c;
-        }
-      }
-      bool in_place = true;
-      for (int32_t j = 0; j < n && in_place; ++j) in_place = newlab[j] == j;
-      if (verbose)
-        fprintf(stderr, "[scilmm symbolic] dense tail: %zu fronts (%zu of them a clique), %lld columns, padded / true flops %.3f%s\n", nbest, ncl,
-                (long long)best_cols, best_ratio, in_place ? "" : " (moved to the end of the order)");
-      if (!in_place) {
-        std::vector<int32_t> perm2(n);
-        for (int32_t j = 0; j < n; ++j) perm2[newlab[j]] = perm[j];
-        perm.swap(perm2);
-        for (int32_t i = 0; i < n; ++i) iperm[perm[i]] = i;
-        // row lists: relabel, sort, store in the new front order (a clique front: every later column)
-        std::vector<int64_t> rp2(ns + 1, 0);
-        for (int32_t k = 0; k < ns; ++k)
-          rp2[k + 1] = rp2[k] + (k >= k_cl ? (int64_t)(n - out2[k].start) : S->sn_rowptr[order[k] + 1] - S->sn_rowptr[order[k]]);
-        std::vector<int32_t> rows2(rp2[ns]);
-#pragma omp parallel for schedule(dynamic, 64)
-        for (int32_t k = 0; k < ns; ++k) {
-          int32_t* o = rows2.data() + rp2[k];
-          if (k >= k_cl) {
-            for (int32_t r = out2[k].start; r < n; ++r) o[r - out2[k].start] = r;
-            continue;
-          }
-          const int32_t q = order[k];
-          const int64_t b = S->sn_rowptr[q], e = S->sn_rowptr[q + 1];
-          for (int64_t t = b; t < e; ++t) o[t - b] = newlab[S->sn_rows[t]];
-          std::sort(o + (out[q].end - out[q].start), o + (e - b));  // (own columns stay first and ascending)
-        }
-        S->sn_rows.swap(rows2);
-        S->sn_rowptr.swap(rp2);
-        out.swap(out2);
-        for (int32_t k = 0; k < ns; ++k) {
-          S->sn_start[k] = out[k].start;
-          for (int32_t j = out[k].start; j < out[k].end; ++j) snode_of[j] = k;
-        }
-        // parents (of fronts and of columns) and column counts follow from the row lists
-        for (int32_t k = 0; k < ns; ++k) {
-          const int64_t b = S->sn_rowptr[k], e = S->sn_rowptr[k + 1];
-          const int32_t w = out[k].end - out[k].start;
-          S->sn_parent[k] = e - b > w ? snode_of[S->sn_rows[b + w]] : -1;
-          for (int32_t j = out[k].start; j + 1 < out[k].end; ++j) parent[j] = j + 1;
-          parent[out[k].end - 1] = e - b > w ? S->sn_rows[b + w] : -1;
-        }
-        // the permuted pattern under the new labels, again straight from G
-#pragma omp parallel for schedule(dynamic, 1024)
-        for (int32_t c = 0; c < n; ++c) {
-          const int32_t v = perm[c];
-          int64_t m = 0;
-          for (int64_t e = gptr[v]; e < gptr[v + 1]; ++e) m += iperm[gidx[e]] > c;
-          cptr[c + 1] = m;
-        }
-        cptr[0] = 0;
-        for (int32_t c = 0; c < n; ++c) cptr[c + 1] += cptr[c];
-#pragma omp parallel for schedule(dynamic, 1024)
-        for (int32_t c = 0; c < n; ++c) {
-          const int32_t v = perm[c];
-          int64_t f = cptr[c];
-          for (int64_t e = gptr[v]; e < gptr[v + 1]; ++e) {
-            const int32_t r = iperm[gidx[e]];
-            if (r > c) cidx[f++] = r;
-          }
-          std::sort(cidx.begin() + cptr[c], cidx.begin() + cptr[c + 1]);
-        }
-        // true column counts (nnz(L), flops) of the final order: elimination tree + postorder + skeleton counts again.
-        // Nothing below reads them (they are reported numbers), so the recount runs BESIDE the rest of the analysis on a
-        // quarter of the host threads and is joined before the function returns: 0.4 of the 1.7 s analysis of the 100k
-        // config, 2 of 20 s at 1M.  It only reads perm / iperm / G / the permuted pattern, none of which changes any more.
-        recount = std::thread([&]() {
-#ifdef _OPENMP
-          omp_set_num_threads(std::max(1, host_threads() / 4));
-#endif
-          std::vector<int32_t> tpar, tnl, tpost;
-          etree_from_g(perm, iperm, tpar, tnl);
-          postorder(n, tpar, tpost);
-          column_counts(n, tpar, tpost, cptr, cidx, cc);
-        });
-      }
-    }
-  }
-  S->perm = perm;
-  S->iperm = iperm;
-  S->parent = parent;
-  lap("dense tail selection");
-  // ---------------------------------------------------------------- 7b. dense tail: padding
-  if (opts.dense_relax > 0.0) {
-    if (ns - best >= 4) {
-      // algorithmic update flops of the fronts about to be padded, on their TRUE row lists (same formula as step 10)
-      double true_tail = 0.0;
-      for (int32_t d = 0; d < ns; ++d) {
-        const int64_t rb = S->sn_rowptr[d], re = S->sn_rowptr[d + 1];
-        const int32_t w = out[d].end - out[d].start;
-        int64_t t = rb + w;
-        while (t < re) {
-          const int32_t sq = snode_of[S->sn_rows[t]];
-          int64_t t2 = t;
-          while (t2 < re && snode_of[S->sn_rows[t2]] == sq) ++t2;
-          if (d >= best) {
-            const double nq = (double)(t2 - t), below = (double)(re - t2);
-            true_tail += (double)w * (nq * (nq + 1.0) + 2.0 * nq * below);
-          }
-          t = t2;
-        }
-      }
-      // block pattern of the true structure (which later tail fronts does a tail front reach at all)
-      S->tail_blk_ptr.assign((size_t)(ns - best) + 1, 0);
-      for (int32_t q = best; q < ns; ++q) {
-        const int64_t rb = S->sn_rowptr[q] + (out[q].end - out[q].start), re = S->sn_rowptr[q + 1];
-        int32_t last = -1;
-        for (int64_t t = rb; t < re; ++t) {
-          const int32_t f = snode_of[S->sn_rows[t]];  // rows ascending => fronts ascending
-          if (f != last) { S->tail_blk.push_back(f - best); last = f; }
-        }
-        S->tail_blk_ptr[(size_t)(q - best) + 1] = (int64_t)S->tail_blk.size();
-      }
-      S->update_flops_pad = -true_tail;  // completed in step 10: executed(tail) - true(tail)
-      S->dense_flops = true_tail;
-      S->dense_first = best;
-      S->sn_rows.resize((size_t)S->sn_rowptr[best]);
-      for (int32_t q = best; q < ns; ++q) {
-        for (int32_t r = out[q].start; r < n; ++r) S->sn_rows.push_back(r);
-        S->sn_rowptr[q + 1] = (int64_t)S->sn_rows.size();
-        S->sn_parent[q] = q + 1 < ns ? q + 1 : -1;  // padded: the tail is a chain in index order
-      }
-    }
-  }
-  lap("dense tail padding");
-  // ---------------------------------------------------------------- 8. panel offsets, levels
-  S->sn_loff.assign(ns + 1, 0);
+  std::vector<int32_t> chead(ns, -1), cnext(ns, -1);
+  std::vector<int32_t> mark(n, -1);
+  std::vector<int32_t> tmp;
+  S.sn_rows.reserve((size_t)(S.nnzL / 4 + n));
   for (int32_t s = 0; s < ns; ++s) {
-    int64_t m = S->sn_rowptr[s + 1] - S->sn_rowptr[s];
-    int64_t w = out[s].end - out[s].start;
+    int32_t c0 = out[s].start, c1 = out[s].end;
+    tmp.swap(arows[s]);
+    std::vector<int32_t>().swap(arows[s]);
+    for (int32_t i : tmp) mark[i] = s;
+    for (int32_t c = chead[s]; c != -1; c = cnext[c]) {
+      int64_t b = S.sn_rowptr[c], e2 = S.sn_rowptr[c + 1];
+      int32_t wc = out[c].end - out[c].start;
+      for (int64_t e = b + wc; e < e2; ++e) {
+        int32_t i = S.sn_rows[e];
+        if (i >= c1 && mark[i] != s) { mark[i] = s; tmp.push_back(i); }
+      }
+    }
+    for (int32_t j = c0; j < c1; ++j) S.sn_rows.push_back(j);
+    const size_t first = S.sn_rows.size();
+    if ((int64_t)tmp.size() * 16 > (int64_t)(n - c1)) {
+      // long list (the fronts of the trailing clique hold most of the later columns): read it off the marks
+      for (int32_t i = c1; i < n; ++i)
+        if (mark[i] == s) S.sn_rows.push_back(i);
+    } else {
+      std::sort(tmp.begin(), tmp.end());
+      S.sn_rows.insert(S.sn_rows.end(), tmp.begin(), tmp.end());
+    }
+    S.sn_rowptr[s + 1] = (int64_t)S.sn_rows.size();
+    if (!tmp.empty()) {
+      int32_t p = a.snode_of[S.sn_rows[first]];
+      S.sn_parent[s] = p;
+      cnext[s] = chead[p];
+      chead[p] = s;
+    }
+    tmp.clear();
+  }
+}
+
+// ---------------------------------------------------------------- 7a. dense tail: which fronts
+// The top of a pedigree factor (16.6k columns at the 100k config, 170k at 1M; > 75 % / > 99 % of the flops) consists
+// of fronts whose row lists are "almost every later column".  Padding those lists to EVERY later column (explicit
+// zeros, like relaxed amalgamation) turns that part into one dense lower-triangular matrix cut into block columns:
+// updates inside it need no index lists, no descriptors and no gather.
+// The tail T is an ancestor-closed set of fronts, grown from the roots of the supernodal tree downwards: among the
+// fronts whose parent is already in T the one with the longest true row list is taken next, as long as its own list
+// fills at least half of its padded one and the padded flop count of the whole tail stays within dense_relax of the
+// true one.  T need not be a chain of the tree: at the 1M config two chains of near-dense fronts (45 x 128 columns
+// with 126k rows each beside the main one) merge 46 levels above the tail's start; as a side branch their updates
+// of the tail went through the gather path at 11 TFLOP/s (a fifth of the factorization time), inside T they are
+// k_dense work.  The fronts of T are moved to the end of the elimination order (children still precede parents, so
+// the fill is unchanged) in the reverse order in which they were taken.
+// A user-supplied permutation is never changed: then T is the trailing chain (parent = next front) only.
+void select_tail_chain(Analysis& a) {
+  const Symbolic& S = a.S;
+  const int32_t ns = S.nsuper;
+  double fl_dense = 0.0, fl_true = 0.0;
+  for (int32_t q = ns - 1; q >= 0; --q) {
+    if (q < ns - 1 && S.sn_parent[q] != q + 1) break;
+    const double w = a.out[q].end - a.out[q].start, mt = (double)(S.sn_rowptr[q + 1] - S.sn_rowptr[q]), md = (double)(a.n - a.out[q].start);
+    fl_dense += w * md * md;
+    fl_true += w * mt * mt;
+    if (fl_dense <= a.opts.dense_relax * fl_true) a.best = q;
+    else if (fl_dense > 1.5 * fl_true) break;
+  }
+}
+
+struct Tail {
+  std::vector<int32_t> taken;        // the fronts of T in their new order: the reverse of the order in which they were taken
+  int64_t cols = 0;                  // columns of T
+  double ratio = 0.0;                // padded / true flops of T
+  size_t ncl = 0;                    // the last ncl fronts of `taken` are (all but) a clique
+  std::vector<int32_t> clique_cols;  // ncl >= 2: the clique's columns (old labels) in their new order
+};
+
+Tail grow_tail_from_roots(const Analysis& a) {
+  const Symbolic& S = a.S;
+  const SymbolicOptions& opts = a.opts;
+  const std::vector<SN>& out = a.out;
+  const int32_t ns = S.nsuper;
+  std::vector<int32_t> chead(ns, -1), cnext(ns, -1);
+  for (int32_t q = 0; q < ns; ++q)
+    if (S.sn_parent[q] != -1) { cnext[q] = chead[S.sn_parent[q]]; chead[S.sn_parent[q]] = q; }
+  std::priority_queue<std::pair<int64_t, int32_t>> heap;  // (true rows, front): longest list first, then the later front
+  for (int32_t q = 0; q < ns; ++q)
+    if (S.sn_parent[q] == -1) heap.push({S.sn_rowptr[q + 1] - S.sn_rowptr[q], q});
+  Tail T;
+  std::vector<int32_t>& taken = T.taken;
+  double fl_dense = 0.0, fl_true = 0.0;
+  int64_t cols_after = 0, wide_cols = 0;
+  double wide_ratio = 0.0;
+  size_t nbest = 0, nwide = 0;
+  FilePtr tail_dump(a.sw.tail_dump ? fopen(a.sw.tail_dump, "w") : nullptr);  // diagnostic: every candidate
+  if (tail_dump) fprintf(tail_dump.get(), "taken,front,w,true_rows,padded_rows,fl_dense_before,fl_true_before\n");
+  while (!heap.empty()) {
+    const int32_t q = heap.top().second;
+    heap.pop();
+    const double w = out[q].end - out[q].start, mt = (double)(S.sn_rowptr[q + 1] - S.sn_rowptr[q]), md = (double)cols_after + w;
+    if (tail_dump) fprintf(tail_dump.get(), "%d,%d,%.0f,%.0f,%.0f,%.6g,%.6g\n", (int)taken.size(), q, w, mt, md, fl_dense, fl_true);
+    // (0.5: padding such a front costs at most 4 x its true flops, the ratio between the dense and the gather kernel.
+    // SCILMM_TUNING=1 SCILMM_TAIL_ELIG=x: at 1M 0.3 takes 27 more fronts, starts the tail 4 levels earlier -- fewer
+    // fronts behind k_outside, 7 x the cells -- and is slower, 30.2 vs 29.6 s.)
+    if (mt < a.sw.tail_elig * md) continue;  // its list only gets relatively shorter as T grows: never eligible again
+    fl_dense += w * md * md;
+    fl_true += w * mt * mt;
+    taken.push_back(q);
+    cols_after += (int64_t)w;
+    if (fl_dense <= opts.dense_relax * fl_true) { nbest = taken.size(); T.cols = cols_after; T.ratio = fl_dense / fl_true; }
+    if (fl_dense <= opts.dense_relax_wide * fl_true) { nwide = taken.size(); wide_cols = cols_after; wide_ratio = fl_dense / fl_true; }
+    if (fl_dense > std::max(1.5, opts.dense_relax_wide) * fl_true) break;
+    for (int32_t c = chead[q]; c != -1; c = cnext[c]) heap.push({S.sn_rowptr[c + 1] - S.sn_rowptr[c], c});
+  }
+  if (T.cols >= opts.dense_wide_cols && nwide > nbest) { nbest = nwide; T.cols = wide_cols; T.ratio = wide_ratio; }
+  taken.resize(nbest);
+  std::reverse(taken.begin(), taken.end());
+  return T;
+}
+
+// The top of T is (all but) a clique: every front's list holds >= 99 % of the later columns (1200 of the 1393
+// fronts at the 1M config, fill 0.997 - 1.000) and is padded to all of them anyway.  The structure of every
+// column BELOW that region depends only on which columns precede it, not on the order inside the region, so the
+// region's columns may be sorted freely: by the number of lower tail fronts that have them as a row.  What a lower
+// front does NOT reach (12 - 50 % of the region for the fronts below it at 1M) then sits together at the region's
+// start, as whole 128-column blocks that the dense update can skip (tail_blk below), instead of being spread over
+// every block as padding.  (The true fill inside the region changes by a fraction of a percent with its order:
+// the column counts are taken again for the final order.)
+void order_tail_clique(const Analysis& a, Tail& T) {
+  const Symbolic& S = a.S;
+  const std::vector<SN>& out = a.out;
+  const std::vector<int32_t>& taken = T.taken;
+  const size_t nbest = taken.size();
+  int64_t cols = 0;
+  for (size_t t = nbest; t-- > 0;) {
+    const int32_t q = taken[t];
+    const int64_t w = out[q].end - out[q].start;
+    if ((double)(S.sn_rowptr[q + 1] - S.sn_rowptr[q]) < 0.99 * (double)(cols + w)) break;
+    cols += w;
+    ++T.ncl;
+  }
+  if (T.ncl < 2) return;
+  const size_t nlow = nbest - T.ncl;
+  std::vector<uint8_t> in_cl(S.nsuper, 0);
+  for (size_t t = nlow; t < nbest; ++t) in_cl[taken[t]] = 1;
+  std::vector<int32_t> cnt(a.n, 0);
+  for (size_t t = 0; t < nlow; ++t) {
+    const int32_t q = taken[t];
+    for (int64_t e = S.sn_rowptr[q] + (out[q].end - out[q].start); e < S.sn_rowptr[q + 1]; ++e)
+      if (in_cl[a.snode_of[S.sn_rows[e]]]) cnt[S.sn_rows[e]]++;
+  }
+  for (size_t t = nlow; t < nbest; ++t)
+    for (int32_t j = out[taken[t]].start; j < out[taken[t]].end; ++j) T.clique_cols.push_back(j);
+  if (nlow > 0) std::stable_sort(T.clique_cols.begin(), T.clique_cols.end(), [&](int32_t x, int32_t y) { return cnt[x] < cnt[y]; });
+}
+
+// New front order = the others as they are, then T; new labels front by front (clique: column by column).  Unless every
+// column keeps its label: the order, the row lists, the parents (of fronts and of columns) and the permuted pattern under
+// the new labels, and the recount of the column counts started beside the rest of the analysis.
+void move_tail_to_end(Analysis& a, const Tail& T) {
+  const int32_t n = a.n, ns = a.S.nsuper;
+  Symbolic& S = a.S;
+  std::vector<SN>& out = a.out;
+  std::vector<uint8_t> inT(ns, 0);
+  for (int32_t q : T.taken) inT[q] = 1;
+  std::vector<int32_t> order;
+  order.reserve(ns);
+  for (int32_t q = 0; q < ns; ++q)
+    if (!inT[q]) order.push_back(q);
+  order.insert(order.end(), T.taken.begin(), T.taken.end());
+  std::vector<int32_t> newlab(n);
+  std::vector<SN> out2(ns);
+  const int32_t k_cl = T.ncl >= 2 ? ns - (int32_t)T.ncl : ns;  // first clique front (new index)
+  {
+    int32_t c = 0;
+    size_t ci = 0;
+    for (int32_t k = 0; k < ns; ++k) {
+      const int32_t q = order[k];
+      out2[k] = out[q];
+      out2[k].start = c;
+      const int32_t w = out[q].end - out[q].start;
+      if (k >= k_cl) {
+        for (int32_t t = 0; t < w; ++t) newlab[T.clique_cols[ci++]] = c++;
+      } else {
+        for (int32_t j = out[q].start; j < out[q].end; ++j) newlab[j] = c++;
+      }
+      out2[k].end = c;
+    }
+  }
+  bool in_place = true;
+  for (int32_t j = 0; j < n && in_place; ++j) in_place = newlab[j] == j;
+  if (a.sw.verbose)
+    fprintf(stderr, "[scilmm symbolic] dense tail: %zu fronts (%zu of them a clique), %lld columns, padded / true flops %.3f%s\n", T.taken.size(),
+            T.ncl, (long long)T.cols, T.ratio, in_place ? "" : " (moved to the end of the order)");
+  if (in_place) return;
+  {
+    std::vector<int32_t> perm2(n);
+    for (int32_t j = 0; j < n; ++j) perm2[newlab[j]] = a.perm[j];
+    a.perm.swap(perm2);
+    for (int32_t i = 0; i < n; ++i) a.iperm[a.perm[i]] = i;
+  }
+  // row lists: relabel, sort, store in the new front order (a clique front: every later column)
+  std::vector<int64_t> rp2(ns + 1, 0);
+  for (int32_t k = 0; k < ns; ++k)
+    rp2[k + 1] = rp2[k] + (k >= k_cl ? (int64_t)(n - out2[k].start) : S.sn_rowptr[order[k] + 1] - S.sn_rowptr[order[k]]);
+  std::vector<int32_t> rows2(rp2[ns]);
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int32_t k = 0; k < ns; ++k) {
+    int32_t* o = rows2.data() + rp2[k];
+    if (k >= k_cl) {
+      for (int32_t r = out2[k].start; r < n; ++r) o[r - out2[k].start] = r;
+      continue;
+    }
+    const int32_t q = order[k];
+    const int64_t b = S.sn_rowptr[q], e = S.sn_rowptr[q + 1];
+    for (int64_t t = b; t < e; ++t) o[t - b] = newlab[S.sn_rows[t]];
+    std::sort(o + (out[q].end - out[q].start), o + (e - b));  // (own columns stay first and ascending)
+  }
+  S.sn_rows.swap(rows2);
+  S.sn_rowptr.swap(rp2);
+  out.swap(out2);
+  for (int32_t k = 0; k < ns; ++k) {
+    S.sn_start[k] = out[k].start;
+    for (int32_t j = out[k].start; j < out[k].end; ++j) a.snode_of[j] = k;
+  }
+  // parents (of fronts and of columns) follow from the row lists
+  for (int32_t k = 0; k < ns; ++k) {
+    const int64_t b = S.sn_rowptr[k], e = S.sn_rowptr[k + 1];
+    const int32_t w = out[k].end - out[k].start;
+    S.sn_parent[k] = e - b > w ? a.snode_of[S.sn_rows[b + w]] : -1;
+    for (int32_t j = out[k].start; j + 1 < out[k].end; ++j) a.parent[j] = j + 1;
+    a.parent[out[k].end - 1] = e - b > w ? S.sn_rows[b + w] : -1;
+  }
+  // the permuted pattern under the new labels, again straight from G
+#pragma omp parallel for schedule(dynamic, 1024)
+  for (int32_t c = 0; c < n; ++c) {
+    const int32_t v = a.perm[c];
+    int32_t m = 0;
+    for (int64_t e = a.gptr[v]; e < a.gptr[v + 1]; ++e) m += a.iperm[a.gidx[e]] > c;
+    a.nlarger[v] = m;
+  }
+  permuted_pattern(a);
+  a.recount.start(n, a.gptr, a.gidx, a.perm, a.iperm, a.cptr, a.cidx);
+}
+
+void select_dense_tail(Analysis& a) {
+  const int32_t ns = a.S.nsuper;
+  a.S.dense_first = a.best = ns;
+  if (a.opts.dense_relax > 0.0 && a.opts.ordering == 2) {
+    select_tail_chain(a);
+  } else if (a.opts.dense_relax > 0.0) {
+    Tail T = grow_tail_from_roots(a);
+    if (T.taken.size() >= 4) {
+      a.best = ns - (int32_t)T.taken.size();
+      order_tail_clique(a, T);
+      move_tail_to_end(a, T);
+    }
+  }
+  // the order is final (and the recount may be running: the stages below take the Analysis const)
+  a.S.perm = a.perm;
+  a.S.iperm = a.iperm;
+  a.S.parent = a.parent;
+}
+
+// ---------------------------------------------------------------- 7b. dense tail: padding
+void pad_dense_tail(const Analysis& a) {
+  Symbolic& S = a.S;
+  const std::vector<SN>& out = a.out;
+  const int32_t n = a.n, ns = S.nsuper, best = a.best;
+  if (!(a.opts.dense_relax > 0.0) || ns - best < 4) return;
+  // on the TRUE row lists of the fronts about to be padded: their algorithmic update flops (as in step 10) and the block
+  // pattern of the true structure (which later tail fronts does a tail front reach at all; rows ascending => fronts ascending)
+  double true_tail = 0.0;
+  S.tail_blk_ptr.assign((size_t)(ns - best) + 1, 0);
+  for (int32_t d = best; d < ns; ++d) {
+    for_each_target_run(a, d, [&](int32_t s, int64_t t, int64_t t2) {
+      true_tail += run_flops(out[d].end - out[d].start, t2 - t, S.sn_rowptr[d + 1] - t2);
+      S.tail_blk.push_back(s - best);
+    });
+    S.tail_blk_ptr[(size_t)(d - best) + 1] = (int64_t)S.tail_blk.size();
+  }
+  S.update_flops_pad = -true_tail;  // completed in step 10: executed(tail) - true(tail)
+  S.dense_flops = true_tail;
+  S.dense_first = best;
+  S.sn_rows.resize((size_t)S.sn_rowptr[best]);
+  for (int32_t q = best; q < ns; ++q) {
+    for (int32_t r = out[q].start; r < n; ++r) S.sn_rows.push_back(r);
+    S.sn_rowptr[q + 1] = (int64_t)S.sn_rows.size();
+    S.sn_parent[q] = q + 1 < ns ? q + 1 : -1;  // padded: the tail is a chain in index order
+  }
+}
+
+// ---------------------------------------------------------------- 8. panel offsets, levels, children
+void panel_offsets_levels_children(const Analysis& a) {
+  Symbolic& S = a.S;
+  const int32_t ns = S.nsuper;
+  S.sn_loff.assign(ns + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) {
+    int64_t m = S.sn_rowptr[s + 1] - S.sn_rowptr[s];
+    int64_t w = a.out[s].end - a.out[s].start;
     int64_t sz = m * w;
     sz = (sz + 1) & ~(int64_t)1;  // keep every panel 16-byte aligned
-    S->sn_loff[s + 1] = S->sn_loff[s] + sz;
+    S.sn_loff[s + 1] = S.sn_loff[s] + sz;
   }
-  S->nnzL_stored = S->sn_loff[ns];
-  S->sn_level.assign(ns, 0);
+  S.nnzL_stored = S.sn_loff[ns];
+  S.sn_level.assign(ns, 0);
   for (int32_t s = 0; s < ns; ++s) {
-    int32_t p = S->sn_parent[s];
-    if (p != -1) S->sn_level[p] = std::max(S->sn_level[p], S->sn_level[s] + 1);
+    int32_t p = S.sn_parent[s];
+    if (p != -1) S.sn_level[p] = std::max(S.sn_level[p], S.sn_level[s] + 1);
   }
   // (SCILMM_TUNING=1 SCILMM_TAIL_DELAY=k starts the tail chain k levels later, so that more of the prelude lies below
   // it and goes through k_outside instead of the gather path: at 1M k = 24 moves 96 % of the remaining gather combos
   // there, 2.8M -> 6.5M outside items, and the factorization takes the same 29.6 s -- the two paths cost the same.)
-  if (const char* e = (getenv("SCILMM_TUNING") && getenv("SCILMM_TUNING")[0] == '1') ? getenv("SCILMM_TAIL_DELAY") : nullptr) {
-    if (S->dense_first < ns) {
-      S->sn_level[S->dense_first] += atoi(e);
-      for (int32_t q = S->dense_first + 1; q < ns; ++q) S->sn_level[q] = std::max(S->sn_level[q], S->sn_level[q - 1] + 1);
-    }
+  if (a.sw.tail_delay != 0 && S.dense_first < ns) {
+    S.sn_level[S.dense_first] += a.sw.tail_delay;
+    for (int32_t q = S.dense_first + 1; q < ns; ++q) S.sn_level[q] = std::max(S.sn_level[q], S.sn_level[q - 1] + 1);
   }
-  S->nlevels = 0;
-  for (int32_t s = 0; s < ns; ++s) S->nlevels = std::max(S->nlevels, S->sn_level[s] + 1);
+  S.nlevels = 0;
+  for (int32_t s = 0; s < ns; ++s) S.nlevels = std::max(S.nlevels, S.sn_level[s] + 1);
 
   // children lists (increasing order)
-  S->child_ptr.assign(ns + 1, 0);
+  S.child_ptr.assign(ns + 1, 0);
   for (int32_t s = 0; s < ns; ++s)
-    if (S->sn_parent[s] != -1) S->child_ptr[S->sn_parent[s] + 1]++;
-  for (int32_t s = 0; s < ns; ++s) S->child_ptr[s + 1] += S->child_ptr[s];
-  S->child_idx.resize(S->child_ptr[ns]);
-  {
-    std::vector<int64_t> fill(S->child_ptr.begin(), S->child_ptr.end() - 1);
-    for (int32_t s = 0; s < ns; ++s)
-      if (S->sn_parent[s] != -1) S->child_idx[fill[S->sn_parent[s]]++] = s;
-  }
+    if (S.sn_parent[s] != -1) S.child_ptr[S.sn_parent[s] + 1]++;
+  for (int32_t s = 0; s < ns; ++s) S.child_ptr[s + 1] += S.child_ptr[s];
+  S.child_idx.resize(S.child_ptr[ns]);
+  std::vector<int64_t> fill(S.child_ptr.begin(), S.child_ptr.end() - 1);
+  for (int32_t s = 0; s < ns; ++s)
+    if (S.sn_parent[s] != -1) S.child_idx[fill[S.sn_parent[s]]++] = s;
+}
 
-  lap("offsets/levels/children");
-  // ---------------------------------------------------------------- 9. value-assembly maps
-  // pattern slots are numbered in permuted CSC order with the diagonal first in each column.
-  {
-    std::vector<int64_t> slot_ptr(n + 1, 0);
-    for (int32_t j = 0; j < n; ++j) slot_ptr[j + 1] = slot_ptr[j] + 1 + (cptr[j + 1] - cptr[j]);
-    S->asm_dst.resize(slot_ptr[n]);
-    S->diag_dst.resize(n);
-    S->pat_colptr = slot_ptr;
-    S->pat_row.resize(slot_ptr[n]);
+// ---------------------------------------------------------------- 9. value-assembly maps
+// pattern slots are numbered in permuted CSC order with the diagonal first in each column (S.pat_colptr).
+void pattern_slot_maps(const Analysis& a) {
+  Symbolic& S = a.S;
+  const int32_t n = a.n, ns = S.nsuper;
+  const std::vector<SN>& out = a.out;
+  const std::vector<int64_t>& cptr = a.cptr;
+  const std::vector<int32_t>& cidx = a.cidx;
+  std::vector<int64_t>& slot_ptr = S.pat_colptr;
+  slot_ptr.assign((size_t)n + 1, 0);
+  for (int32_t j = 0; j < n; ++j) slot_ptr[j + 1] = slot_ptr[j] + 1 + (cptr[j + 1] - cptr[j]);
+  S.asm_dst.resize(slot_ptr[n]);
+  S.diag_dst.resize(n);
+  S.pat_row.resize(slot_ptr[n]);
+  S.nnz_pattern = slot_ptr[n];
 #pragma omp parallel for schedule(dynamic, 4096)
-    for (int32_t j = 0; j < n; ++j) {
-      int64_t sl = slot_ptr[j];
-      S->pat_row[sl++] = j;
-      for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) S->pat_row[sl++] = cidx[e];
-    }
-    S->inv_off.assign(ns + 1, 0);
-    for (int32_t s = 0; s < ns; ++s) {
-      int64_t w = out[s].end - out[s].start;
-      S->inv_off[s + 1] = S->inv_off[s] + ((w * w + 1) & ~(int64_t)1);
-    }
+  for (int32_t j = 0; j < n; ++j) {
+    int64_t sl = slot_ptr[j];
+    S.pat_row[sl++] = j;
+    for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) S.pat_row[sl++] = cidx[e];
+  }
+  S.inv_off.assign(ns + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) {
+    int64_t w = out[s].end - out[s].start;
+    S.inv_off[s + 1] = S.inv_off[s] + ((w * w + 1) & ~(int64_t)1);
+  }
 #pragma omp parallel
-    {
-      std::vector<int32_t> pos(n, -1);
+  {
+    std::vector<int32_t> pos(n, -1);
 #pragma omp for schedule(dynamic, 16)
-      for (int32_t s = 0; s < ns; ++s) {
-        int64_t rb = S->sn_rowptr[s], re = S->sn_rowptr[s + 1];
-        int64_t m = re - rb;
-        const bool tail = s >= S->dense_first;  // rows = every column from the front's first on
-        const int32_t c0 = out[s].start;
-        if (!tail)
-          for (int64_t t = rb; t < re; ++t) pos[S->sn_rows[t]] = (int32_t)(t - rb);
-        for (int32_t j = c0; j < out[s].end; ++j) {
-          int64_t colbase = S->sn_loff[s] + (int64_t)(j - c0) * m;
-          int64_t sl = slot_ptr[j];
-          S->asm_dst[sl] = colbase + (j - c0);
-          S->diag_dst[j] = S->asm_dst[sl];
-          ++sl;
-          if (tail)
-            for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) S->asm_dst[sl++] = colbase + (cidx[e] - c0);
-          else
-            for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) S->asm_dst[sl++] = colbase + pos[cidx[e]];
-        }
-      }
-    }
-    lap("  pattern slots -> panels");
-    // per input matrix: where does each stored lower entry go
-    S->val_slot.resize(K);
-    S->val_src.resize(K);
-    for (int32_t k = 0; k < K; ++k) {
-      if (S->is_diag[k]) {
-        for (int32_t i = 0; i < n; ++i)
-          for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
-            S->val_slot[k].push_back(iperm[i]);
-            S->val_src[k].push_back(e);
-          }
-        continue;
-      }
-      // Fast path -- matrix k stores both halves, rows strictly ascending (canonical CSR).  Vertex v's pattern column
-      // c = new(v) is walked once: positions of its rows go to a thread-local table, and every entry (v, u) of row v
-      // with new(u) >= c finds its slot there -- the column is warm, nothing is searched.  The value is read from the
-      // stored LOWER entry: (v, u) itself if u <= v, else its mirror (u, v), whose index inside row u is the number of
-      // smaller columns in that row = the running count of mirrors seen while the rows are swept in ascending order
-      // (done per range of target rows, one range per thread, so the counts need no atomics).
-      bool fast = true;
-      {
-        uint64_t hlo = 0, hup = 0;
-        int64_t bad = 0;
-        auto mix = [](uint64_t x) {
-          x += 0x9e3779b97f4a7c15ull;
-          x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-          x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-          return x ^ (x >> 31);
-        };
-#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : hlo, hup, bad)
-        for (int32_t i = 0; i < n; ++i)
-          for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
-            const int32_t j = indices[k][e];
-            if (j < 0 || j >= n || (e > indptr[k][i] && indices[k][e - 1] >= j)) { ++bad; continue; }
-            if (j < i) hlo += mix(((uint64_t)(uint32_t)i << 32) | (uint32_t)j);
-            else if (j > i) hup += mix(((uint64_t)(uint32_t)j << 32) | (uint32_t)i);
-          }
-        fast = bad == 0 && hlo == hup;
-      }
-      if (fast) {
-        const int64_t* ip = indptr[k];
-        const int32_t* ix = indices[k];
-        const int64_t nzk = ip[n];
-        // mirror positions of the upper entries
-        std::vector<int32_t> mir(nzk);
-        {
-          const int R = std::max(1, host_threads());
-          std::vector<int64_t> lowcum(n + 1, 0);
-#pragma omp parallel for schedule(static)
-          for (int32_t i = 0; i < n; ++i) lowcum[i + 1] = std::lower_bound(ix + ip[i], ix + ip[i + 1], i) - (ix + ip[i]);
-          for (int32_t i = 0; i < n; ++i) lowcum[i + 1] += lowcum[i];
-          std::vector<int32_t> cut(R + 1, n);
-          cut[0] = 0;
-          for (int q = 1; q < R; ++q)
-            cut[q] = (int32_t)(std::lower_bound(lowcum.begin(), lowcum.end(), lowcum[n] * q / R) - lowcum.begin());
-          for (int q = 1; q <= R; ++q) cut[q] = std::max(cut[q], cut[q - 1]);
-#pragma omp parallel for schedule(dynamic, 1)
-          for (int q = 0; q < R; ++q) {
-            const int32_t i0 = cut[q], i1 = cut[q + 1];
-            if (i1 <= i0) continue;
-            std::vector<int32_t> cur(i1 - i0, 0);
-            for (int32_t j = 0; j < i1; ++j) {  // rows j >= i1 have no upper entry below i1
-              const int32_t* b = ix + ip[j];
-              const int32_t* e = ix + ip[j + 1];
-              const int32_t* lo = std::lower_bound(b, e, std::max(i0, j + 1));
-              for (const int32_t* t = lo; t < e && *t < i1; ++t) mir[t - ix] = cur[*t - i0]++;
-            }
-          }
-        }
-        std::vector<int64_t> optr(n + 1, 0);
-#pragma omp parallel for schedule(dynamic, 1024)
-        for (int32_t v = 0; v < n; ++v) {
-          const int32_t c = iperm[v];
-          int64_t m = 0;
-          for (int64_t e = ip[v]; e < ip[v + 1]; ++e) m += iperm[ix[e]] >= c;
-          optr[v + 1] = m;
-        }
-        for (int32_t v = 0; v < n; ++v) optr[v + 1] += optr[v];
-        S->val_slot[k].resize(optr[n]);
-        S->val_src[k].resize(optr[n]);
-#pragma omp parallel
-        {
-          std::vector<int32_t> pos(n, -1);
-#pragma omp for schedule(dynamic, 256)
-          for (int32_t v = 0; v < n; ++v) {
-            const int32_t c = iperm[v];
-            for (int64_t e = cptr[c]; e < cptr[c + 1]; ++e) pos[cidx[e]] = (int32_t)(e - cptr[c]);
-            int64_t t = optr[v];
-            for (int64_t e = ip[v]; e < ip[v + 1]; ++e) {
-              const int32_t u = ix[e], r = iperm[u];
-              if (r < c) continue;
-              S->val_slot[k][t] = r == c ? slot_ptr[c] : slot_ptr[c] + 1 + pos[r];
-              S->val_src[k][t] = u <= v ? e : ip[u] + mir[e];
-              ++t;
-            }
-          }
-        }
-        continue;
-      }
-      // General inputs (one half stored, unsorted rows, duplicates):
-      // every stored lower entry (i, j) looks its pattern slot up: column min(new i, new j), row max, found by bisection
-      // in the sorted column -- independent per entry, all cores, no scatter.  (A duplicate of an entry inside one
-      // matrix maps to the same slot; the value upload keeps one of them.)
-      std::vector<int64_t> lptr(n + 1, 0);
-#pragma omp parallel for schedule(static)
-      for (int32_t i = 0; i < n; ++i) {
-        int64_t c = 0;
-        for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) c += indices[k][e] >= 0 && indices[k][e] <= i;
-        lptr[i + 1] = c;
-      }
-      for (int32_t i = 0; i < n; ++i) lptr[i + 1] += lptr[i];
-      S->val_slot[k].resize(lptr[n]);
-      S->val_src[k].resize(lptr[n]);
-#pragma omp parallel for schedule(dynamic, 256)
-      for (int32_t i = 0; i < n; ++i) {
-        int64_t t = lptr[i];
-        const int32_t a = iperm[i];
-        for (int64_t e = indptr[k][i]; e < indptr[k][i + 1]; ++e) {
-          const int32_t j = indices[k][e];
-          if (j < 0 || j > i) continue;
-          const int32_t bq = iperm[j];
-          const int32_t c = std::min(a, bq), r = std::max(a, bq);
-          int64_t sl = slot_ptr[c];
-          if (r != c) {
-            const int32_t* lo = cidx.data() + cptr[c];
-            const int32_t* hi = cidx.data() + cptr[c + 1];
-            sl += 1 + (std::lower_bound(lo, hi, r) - lo);
-          }
-          S->val_slot[k][t] = sl;
-          S->val_src[k][t] = e;
-          ++t;
-        }
-      }
-    }
-    S->nnz_pattern = slot_ptr[n];
-  }
-  lap("  entries -> pattern slots");
-  // ---------------------------------------------------------------- 10. left-looking update schedule
-  {
-    S->upd_ptr.assign(ns + 1, 0);
-    for (int32_t d = 0; d < ns; ++d) {
-      int64_t rb = S->sn_rowptr[d], re = S->sn_rowptr[d + 1];
-      int32_t w = out[d].end - out[d].start;
-      int32_t prev = -1;
-      for (int64_t t = rb + w; t < re; ++t) {
-        int32_t s = snode_of[S->sn_rows[t]];
-        if (s != prev) { S->upd_ptr[s + 1]++; prev = s; }
-      }
-    }
-    for (int32_t s = 0; s < ns; ++s) S->upd_ptr[s + 1] += S->upd_ptr[s];
-    int64_t nu = S->upd_ptr[ns];
-    S->upd_src.resize(nu);
-    S->upd_p0.resize(nu);
-    S->upd_p1.resize(nu);
-    S->upd_jp0.resize(nu);
-    std::vector<int64_t> fill(S->upd_ptr.begin(), S->upd_ptr.end() - 1);
-    for (int32_t d = 0; d < ns; ++d) {  // increasing d => each target's list is in increasing descendant order
-      int64_t rb = S->sn_rowptr[d], re = S->sn_rowptr[d + 1];
-      int32_t w = out[d].end - out[d].start;
-      int64_t t = rb + w;
-      while (t < re) {
-        int32_t s = snode_of[S->sn_rows[t]];
-        int64_t t2 = t;
-        while (t2 < re && snode_of[S->sn_rows[t2]] == s) ++t2;
-        int64_t f = fill[s]++;
-        S->upd_src[f] = d;
-        S->upd_p0[f] = (int32_t)(t - rb);
-        S->upd_p1[f] = (int32_t)(t2 - rb);
-        S->upd_jp0[f] = (S->sn_rows[t2 - 1] - S->sn_rows[t] == (int32_t)(t2 - 1 - t)) ? S->sn_rows[t] - out[s].start : -1;
-        {
-          const double nq = (double)(t2 - t), below = (double)(re - t2);
-          S->update_flops += (double)w * (nq * (nq + 1.0) + 2.0 * nq * below);
-          if (d >= S->dense_first) S->update_flops_pad += (double)w * (nq * (nq + 1.0) + 2.0 * nq * below);
-        }
-        t = t2;
-      }
-    }
-  }
-  // level lists, big fronts first inside a level
-  S->level_ptr.assign(S->nlevels + 1, 0);
-  for (int32_t s = 0; s < ns; ++s) S->level_ptr[S->sn_level[s] + 1]++;
-  for (int32_t l = 0; l < S->nlevels; ++l) S->level_ptr[l + 1] += S->level_ptr[l];
-  S->level_fronts.resize(ns);
-  {
-    std::vector<int32_t> fill(S->level_ptr.begin(), S->level_ptr.end() - 1);
-    for (int32_t s = 0; s < ns; ++s) S->level_fronts[fill[S->sn_level[s]]++] = s;
-  }
-  lap("update schedule");
-  // ---------------------------------------------------------------- 11. target tiles (their combos are built lazily)
-  {
-    const int32_t TM = opts.tile_rows;
-    S->tile_rows = TM;
-    S->tile_base.assign(ns + 1, 0);
     for (int32_t s = 0; s < ns; ++s) {
-      int64_t m = S->sn_rowptr[s + 1] - S->sn_rowptr[s];
-      S->tile_base[s + 1] = S->tile_base[s] + (m + TM - 1) / TM;
-    }
-    int64_t nt = S->tile_base[ns];
-    S->tile_front.resize(nt);
-    for (int32_t s = 0; s < ns; ++s)
-      for (int64_t g = S->tile_base[s]; g < S->tile_base[s + 1]; ++g) S->tile_front[g] = s;
-    // per-level tile lists in tile order (the update plan balances its own work items; trsm / L*R tiles cost the same)
-    S->level_tile_ptr.assign(S->nlevels + 1, 0);
-    for (int64_t g = 0; g < nt; ++g) S->level_tile_ptr[S->sn_level[S->tile_front[g]] + 1]++;
-    for (int32_t l = 0; l < S->nlevels; ++l) S->level_tile_ptr[l + 1] += S->level_tile_ptr[l];
-    S->level_tiles.resize(nt);
-    {
-      std::vector<int64_t> fill(S->level_tile_ptr.begin(), S->level_tile_ptr.end() - 1);
-      for (int64_t g = 0; g < nt; ++g) S->level_tiles[fill[S->sn_level[S->tile_front[g]]]++] = (int32_t)g;
-    }
-    // per-level update-pair lists (by target level)
-    S->level_pair_ptr.assign(S->nlevels + 1, 0);
-    for (int32_t s = 0; s < ns; ++s) S->level_pair_ptr[S->sn_level[s] + 1] += S->upd_ptr[s + 1] - S->upd_ptr[s];
-    for (int32_t l = 0; l < S->nlevels; ++l) S->level_pair_ptr[l + 1] += S->level_pair_ptr[l];
-    S->level_pairs.resize(S->upd_src.size());
-    {
-      std::vector<int64_t> fill(S->level_pair_ptr.begin(), S->level_pair_ptr.end() - 1);
-      for (int32_t s = 0; s < ns; ++s)
-        for (int64_t e = S->upd_ptr[s]; e < S->upd_ptr[s + 1]; ++e) S->level_pairs[fill[S->sn_level[s]]++] = (int32_t)e;
+      int64_t rb = S.sn_rowptr[s], re = S.sn_rowptr[s + 1];
+      int64_t m = re - rb;
+      const bool tail = s >= S.dense_first;  // rows = every column from the front's first on
+      const int32_t c0 = out[s].start;
+      if (!tail)
+        for (int64_t t = rb; t < re; ++t) pos[S.sn_rows[t]] = (int32_t)(t - rb);
+      for (int32_t j = c0; j < out[s].end; ++j) {
+        int64_t colbase = S.sn_loff[s] + (int64_t)(j - c0) * m;
+        int64_t sl = slot_ptr[j];
+        S.asm_dst[sl] = colbase + (j - c0);
+        S.diag_dst[j] = S.asm_dst[sl];
+        ++sl;
+        if (tail)
+          for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) S.asm_dst[sl++] = colbase + (cidx[e] - c0);
+        else
+          for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) S.asm_dst[sl++] = colbase + pos[cidx[e]];
+      }
     }
   }
-  if (recount.joinable()) {
-    recount.join();
-    S->nnzL = 0;
-    S->flops = 0;
-    for (int32_t j = 0; j < n; ++j) {
-      S->nnzL += cc[j];
-      S->flops += (double)cc[j] * (double)cc[j];
+}
+
+// per input matrix: where does each stored lower entry go
+void value_map_diagonal(const Analysis& a, int32_t k) {
+  for (int32_t i = 0; i < a.n; ++i)
+    for (int64_t e = a.indptr[k][i]; e < a.indptr[k][i + 1]; ++e) {
+      a.S.val_slot[k].push_back(a.iperm[i]);
+      a.S.val_src[k].push_back(e);
     }
-    lap("column counts of the final order (joined)");
+}
+
+// Fast path -- matrix k stores both halves, rows strictly ascending (canonical CSR); false: it does not, nothing written.
+// Vertex v's pattern column c = new(v) is walked once: positions of its rows go to a thread-local table, and every entry
+// (v, u) of row v with new(u) >= c finds its slot there -- the column is warm, nothing is searched.  The value is read
+// from the stored LOWER entry: (v, u) itself if u <= v, else its mirror (u, v), whose index inside row u is the number of
+// smaller columns in that row = the running count of mirrors seen while the rows are swept in ascending order
+// (done per range of target rows, one range per thread, so the counts need no atomics).
+bool value_map_canonical(const Analysis& a, int32_t k) {
+  Symbolic& S = a.S;
+  const int32_t n = a.n;
+  const int64_t* ip = a.indptr[k];
+  const int32_t* ix = a.indices[k];
+  const std::vector<int32_t>& iperm = a.iperm;
+  {
+    uint64_t hlo = 0, hup = 0;
+    int64_t bad = 0;
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : hlo, hup, bad)
+    for (int32_t i = 0; i < n; ++i)
+      for (int64_t e = ip[i]; e < ip[i + 1]; ++e) {
+        const int32_t j = ix[e];
+        if (j < 0 || j >= n || (e > ip[i] && ix[e - 1] >= j)) { ++bad; continue; }
+        if (j < i) hlo += mix64(((uint64_t)(uint32_t)i << 32) | (uint32_t)j);
+        else if (j > i) hup += mix64(((uint64_t)(uint32_t)j << 32) | (uint32_t)i);
+      }
+    if (bad != 0 || hlo != hup) return false;
   }
-  std::vector<int32_t>().swap(gidx);
-  S->colcount = cc;
-  return S;
+  const int64_t nzk = ip[n];
+  // mirror positions of the upper entries
+  std::vector<int32_t> mir(nzk);
+  {
+    const int R = std::max(1, host_threads());
+    std::vector<int64_t> lowcum(n + 1, 0);
+#pragma omp parallel for schedule(static)
+    for (int32_t i = 0; i < n; ++i) lowcum[i + 1] = std::lower_bound(ix + ip[i], ix + ip[i + 1], i) - (ix + ip[i]);
+    for (int32_t i = 0; i < n; ++i) lowcum[i + 1] += lowcum[i];
+    std::vector<int32_t> cut(R + 1, n);
+    cut[0] = 0;
+    for (int q = 1; q < R; ++q)
+      cut[q] = (int32_t)(std::lower_bound(lowcum.begin(), lowcum.end(), lowcum[n] * q / R) - lowcum.begin());
+    for (int q = 1; q <= R; ++q) cut[q] = std::max(cut[q], cut[q - 1]);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int q = 0; q < R; ++q) {
+      const int32_t i0 = cut[q], i1 = cut[q + 1];
+      if (i1 <= i0) continue;
+      std::vector<int32_t> cur(i1 - i0, 0);
+      for (int32_t j = 0; j < i1; ++j) {  // rows j >= i1 have no upper entry below i1
+        const int32_t* b = ix + ip[j];
+        const int32_t* e = ix + ip[j + 1];
+        const int32_t* lo = std::lower_bound(b, e, std::max(i0, j + 1));
+        for (const int32_t* t = lo; t < e && *t < i1; ++t) mir[t - ix] = cur[*t - i0]++;
+      }
+    }
+  }
+  std::vector<int64_t> optr(n + 1, 0);
+#pragma omp parallel for schedule(dynamic, 1024)
+  for (int32_t v = 0; v < n; ++v) {
+    const int32_t c = iperm[v];
+    int64_t m = 0;
+    for (int64_t e = ip[v]; e < ip[v + 1]; ++e) m += iperm[ix[e]] >= c;
+    optr[v + 1] = m;
+  }
+  for (int32_t v = 0; v < n; ++v) optr[v + 1] += optr[v];
+  S.val_slot[k].resize(optr[n]);
+  S.val_src[k].resize(optr[n]);
+#pragma omp parallel
+  {
+    std::vector<int32_t> pos(n, -1);
+#pragma omp for schedule(dynamic, 256)
+    for (int32_t v = 0; v < n; ++v) {
+      const int32_t c = iperm[v];
+      for (int64_t e = a.cptr[c]; e < a.cptr[c + 1]; ++e) pos[a.cidx[e]] = (int32_t)(e - a.cptr[c]);
+      int64_t t = optr[v];
+      for (int64_t e = ip[v]; e < ip[v + 1]; ++e) {
+        const int32_t u = ix[e], r = iperm[u];
+        if (r < c) continue;
+        S.val_slot[k][t] = r == c ? S.pat_colptr[c] : S.pat_colptr[c] + 1 + pos[r];
+        S.val_src[k][t] = u <= v ? e : ip[u] + mir[e];
+        ++t;
+      }
+    }
+  }
+  return true;
+}
+
+// General inputs (one half stored, unsorted rows, duplicates):
+// every stored lower entry (i, j) looks its pattern slot up: column min(new i, new j), row max, found by bisection
+// in the sorted column -- independent per entry, all cores, no scatter.  (A duplicate of an entry inside one
+// matrix maps to the same slot; the value upload keeps one of them.)
+void value_map_general(const Analysis& a, int32_t k) {
+  Symbolic& S = a.S;
+  const int32_t n = a.n;
+  const int64_t* ip = a.indptr[k];
+  const int32_t* ix = a.indices[k];
+  std::vector<int64_t> lptr(n + 1, 0);
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t c = 0;
+    for (int64_t e = ip[i]; e < ip[i + 1]; ++e) c += ix[e] >= 0 && ix[e] <= i;
+    lptr[i + 1] = c;
+  }
+  for (int32_t i = 0; i < n; ++i) lptr[i + 1] += lptr[i];
+  S.val_slot[k].resize(lptr[n]);
+  S.val_src[k].resize(lptr[n]);
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t t = lptr[i];
+    const int32_t ai = a.iperm[i];
+    for (int64_t e = ip[i]; e < ip[i + 1]; ++e) {
+      const int32_t j = ix[e];
+      if (j < 0 || j > i) continue;
+      const int32_t bq = a.iperm[j];
+      const int32_t c = std::min(ai, bq), r = std::max(ai, bq);
+      int64_t sl = S.pat_colptr[c];
+      if (r != c) {
+        const int32_t* lo = a.cidx.data() + a.cptr[c];
+        const int32_t* hi = a.cidx.data() + a.cptr[c + 1];
+        sl += 1 + (std::lower_bound(lo, hi, r) - lo);
+      }
+      S.val_slot[k][t] = sl;
+      S.val_src[k][t] = e;
+      ++t;
+    }
+  }
+}
+
+void value_maps(const Analysis& a) {
+  a.S.val_slot.resize(a.K);
+  a.S.val_src.resize(a.K);
+  for (int32_t k = 0; k < a.K; ++k) {
+    if (a.S.is_diag[k]) value_map_diagonal(a, k);
+    else if (!value_map_canonical(a, k)) value_map_general(a, k);
+  }
+}
+
+// ---------------------------------------------------------------- 10. left-looking update schedule
+void update_schedule(const Analysis& a) {
+  Symbolic& S = a.S;
+  const int32_t ns = S.nsuper;
+  S.upd_ptr.assign(ns + 1, 0);
+  for (int32_t d = 0; d < ns; ++d) for_each_target_run(a, d, [&](int32_t s, int64_t, int64_t) { S.upd_ptr[s + 1]++; });
+  for (int32_t s = 0; s < ns; ++s) S.upd_ptr[s + 1] += S.upd_ptr[s];
+  int64_t nu = S.upd_ptr[ns];
+  S.upd_src.resize(nu);
+  S.upd_p0.resize(nu);
+  S.upd_p1.resize(nu);
+  S.upd_jp0.resize(nu);
+  std::vector<int64_t> fill(S.upd_ptr.begin(), S.upd_ptr.end() - 1);
+  for (int32_t d = 0; d < ns; ++d) {  // increasing d => each target's list is in increasing descendant order
+    const int64_t rb = S.sn_rowptr[d], re = S.sn_rowptr[d + 1];
+    for_each_target_run(a, d, [&](int32_t s, int64_t t, int64_t t2) {
+      const int64_t f = fill[s]++;
+      S.upd_src[f] = d;
+      S.upd_p0[f] = (int32_t)(t - rb);
+      S.upd_p1[f] = (int32_t)(t2 - rb);
+      S.upd_jp0[f] = (S.sn_rows[t2 - 1] - S.sn_rows[t] == (int32_t)(t2 - 1 - t)) ? S.sn_rows[t] - a.out[s].start : -1;
+      const double fl = run_flops(a.out[d].end - a.out[d].start, t2 - t, re - t2);
+      S.update_flops += fl;
+      if (d >= S.dense_first) S.update_flops_pad += fl;
+    });
+  }
+}
+
+// level lists, big fronts first inside a level
+void level_lists(const Analysis& a) {
+  Symbolic& S = a.S;
+  const int32_t ns = S.nsuper;
+  S.level_ptr.assign(S.nlevels + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) S.level_ptr[S.sn_level[s] + 1]++;
+  for (int32_t l = 0; l < S.nlevels; ++l) S.level_ptr[l + 1] += S.level_ptr[l];
+  S.level_fronts.resize(ns);
+  std::vector<int32_t> fill(S.level_ptr.begin(), S.level_ptr.end() - 1);
+  for (int32_t s = 0; s < ns; ++s) S.level_fronts[fill[S.sn_level[s]]++] = s;
+}
+
+// ---------------------------------------------------------------- 11. target tiles (their combos are built lazily)
+void target_tiles(const Analysis& a) {
+  Symbolic& S = a.S;
+  const int32_t ns = S.nsuper;
+  const int32_t TM = a.opts.tile_rows;
+  S.tile_rows = TM;
+  S.tile_base.assign(ns + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) {
+    int64_t m = S.sn_rowptr[s + 1] - S.sn_rowptr[s];
+    S.tile_base[s + 1] = S.tile_base[s] + (m + TM - 1) / TM;
+  }
+  int64_t nt = S.tile_base[ns];
+  S.tile_front.resize(nt);
+  for (int32_t s = 0; s < ns; ++s)
+    for (int64_t g = S.tile_base[s]; g < S.tile_base[s + 1]; ++g) S.tile_front[g] = s;
+  // per-level tile lists in tile order (the update plan balances its own work items; trsm / L*R tiles cost the same)
+  S.level_tile_ptr.assign(S.nlevels + 1, 0);
+  for (int64_t g = 0; g < nt; ++g) S.level_tile_ptr[S.sn_level[S.tile_front[g]] + 1]++;
+  for (int32_t l = 0; l < S.nlevels; ++l) S.level_tile_ptr[l + 1] += S.level_tile_ptr[l];
+  S.level_tiles.resize(nt);
+  {
+    std::vector<int64_t> fill(S.level_tile_ptr.begin(), S.level_tile_ptr.end() - 1);
+    for (int64_t g = 0; g < nt; ++g) S.level_tiles[fill[S.sn_level[S.tile_front[g]]]++] = (int32_t)g;
+  }
+  // per-level update-pair lists (by target level)
+  S.level_pair_ptr.assign(S.nlevels + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) S.level_pair_ptr[S.sn_level[s] + 1] += S.upd_ptr[s + 1] - S.upd_ptr[s];
+  for (int32_t l = 0; l < S.nlevels; ++l) S.level_pair_ptr[l + 1] += S.level_pair_ptr[l];
+  S.level_pairs.resize(S.upd_src.size());
+  std::vector<int64_t> fill(S.level_pair_ptr.begin(), S.level_pair_ptr.end() - 1);
+  for (int32_t s = 0; s < ns; ++s)
+    for (int64_t e = S.upd_ptr[s]; e < S.upd_ptr[s + 1]; ++e) S.level_pairs[fill[S.sn_level[s]]++] = (int32_t)e;
+}
+
+}  // namespace
+
+Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, const int32_t* const* indices,
+                           const int32_t* perm_in, const SymbolicOptions& opts_in) {
+  use_host_threads();
+  const AnalysisSwitches sw = read_analysis_switches();
+  SymbolicOptions opts = opts_in;
+  if (sw.tail_wide) opts.dense_relax_wide = *sw.tail_wide;  // flop budget of a wide tail
+  std::unique_ptr<Symbolic> result(new Symbolic());
+  result->n = n;
+  result->K = K;
+  Analysis a{n, K, indptr, indices, perm_in, opts, sw, *result};
+  detect_diagonal_inputs(a);
+  build_adjacency(a);
+  a.lap("symmetric adjacency");
+  if (!order_vertices(a)) return result.release();  // (with its `error` set)
+  a.lap("ordering");
+  etree_and_postorder(a);
+  a.lap("etree+postorder");
+  permuted_pattern(a);
+  a.lap("permuted pattern");
+  count_columns(a);
+  a.lap("column counts");
+  find_supernodes(a);
+  a.lap("supernodes");
+  front_row_structures(a);
+  a.lap("row structures");
+  select_dense_tail(a);  // may start a.recount: from here on the stages read the Analysis and write the result only
+  a.lap("dense tail selection");
+  pad_dense_tail(a);
+  a.lap("dense tail padding");
+  panel_offsets_levels_children(a);
+  a.lap("offsets/levels/children");
+  pattern_slot_maps(a);
+  a.lap("  pattern slots -> panels");
+  value_maps(a);
+  a.lap("  entries -> pattern slots");
+  update_schedule(a);
+  level_lists(a);
+  a.lap("update schedule");
+  target_tiles(a);
+  if (a.recount.running()) {
+    a.cc = a.recount.join();
+    report_column_counts(a.cc, a.S);
+    a.lap("column counts of the final order (joined)");
+  }
+  result->colcount = std::move(a.cc);
+  return result.release();
 }
 
 // Step 11b, on demand: for every 128-row tile of every target panel the list of descendant row ranges ("combos")
@@ -1262,89 +1430,7 @@ void build_tile_combos(Symbolic* S, const uint8_t* keep_front, bool skip_dense, 
   S->combos_built = true;
 }
 
-// ------------------------------------------------------------------------------------------------
-// On-disk / shared-memory image of an analysis (the reference keeps its stage artefacts on disk,
-// scilmm/IBDCompute.py:82-84; here the 20 s analysis of the 1M config need not be redone by every process of a node).
-// Plain binary: a header, then every member of Symbolic in the order of the list below -- which is the single place that
-// names them, for writing and for reading.  The tile combos (built lazily per rank) are not part of the image.
-namespace {
-constexpr uint64_t kImageMagic = 0x53434c4d53594d34ull;  // "SCLMSYM4" (4: length + checksum trailer)
-
-// Every byte that passes through pod() / vec() is counted and folded into a 64-bit checksum (four interleaved
-// multiply-xorshift lanes over 8-byte words: memory speed); the writer appends (bytes, checksum) as a trailer and the
-// reader refuses an image whose trailer does not match what it read -- a truncated or torn file (two writers on one
-// name, a copy cut short) is then a cache miss, never a wrong analysis.
-struct ImageIO {
-  FILE* fp;
-  bool write;
-  bool ok = true;
-  uint64_t bytes = 0;
-  uint64_t lane[4] = {0x9e3779b97f4a7c15ull, 0xc2b2ae3d27d4eb4full, 0x165667b19e3779f9ull, 0x27d4eb2f165667c5ull};
-  void fold(const void* p, size_t nbytes) {
-    const unsigned char* b = (const unsigned char*)p;
-    size_t i = 0;
-    uint64_t l0 = lane[0], l1 = lane[1], l2 = lane[2], l3 = lane[3];
-    for (; i + 32 <= nbytes; i += 32) {
-      uint64_t w[4];
-      std::memcpy(w, b + i, 32);
-      l0 = (l0 ^ w[0]) * 0x9e3779b97f4a7c15ull; l0 ^= l0 >> 29;
-      l1 = (l1 ^ w[1]) * 0xc2b2ae3d27d4eb4full; l1 ^= l1 >> 31;
-      l2 = (l2 ^ w[2]) * 0x165667b19e3779f9ull; l2 ^= l2 >> 30;
-      l3 = (l3 ^ w[3]) * 0x27d4eb2f165667c5ull; l3 ^= l3 >> 28;
-    }
-    for (; i < nbytes; ++i) { l0 = (l0 ^ b[i]) * 0x100000001b3ull; l0 ^= l0 >> 32; }
-    lane[0] = l0; lane[1] = l1; lane[2] = l2; lane[3] = l3;
-    bytes += nbytes;
-  }
-  uint64_t checksum() const {
-    uint64_t h = bytes;
-    for (int q = 0; q < 4; ++q) { h = (h ^ lane[q]) * 0x9e3779b97f4a7c15ull; h ^= h >> 32; }
-    return h;
-  }
-  template <typename T>
-  void pod(T& v) {
-    if (!ok) return;
-    ok = write ? fwrite(&v, sizeof(T), 1, fp) == 1 : fread(&v, sizeof(T), 1, fp) == 1;
-    if (ok) fold(&v, sizeof(T));
-  }
-  template <typename T>
-  void vec(std::vector<T>& v) {
-    uint64_t cnt = (uint64_t)v.size();
-    pod(cnt);
-    if (!ok) return;
-    if (!write) {
-      if (cnt > ((uint64_t)1 << 40) / sizeof(T)) { ok = false; return; }
-      v.resize((size_t)cnt);
-    }
-    if (cnt) ok = write ? fwrite(v.data(), sizeof(T), (size_t)cnt, fp) == cnt : fread(v.data(), sizeof(T), (size_t)cnt, fp) == cnt;
-    if (ok && cnt) fold(v.data(), sizeof(T) * (size_t)cnt);
-  }
-  template <typename T>
-  void vecvec(std::vector<std::vector<T>>& v) {
-    uint64_t cnt = (uint64_t)v.size();
-    pod(cnt);
-    if (!ok) return;
-    if (!write) v.resize((size_t)cnt);
-    for (auto& x : v) vec(x);
-  }
-};
-
-void image_fields(ImageIO& io, Symbolic& S) {
-  io.pod(S.n); io.pod(S.K); io.pod(S.nsuper); io.pod(S.dense_first); io.pod(S.tile_rows); io.pod(S.nlevels);
-  io.pod(S.nnz_pattern); io.pod(S.nnzL); io.pod(S.nnzL_stored); io.pod(S.flops); io.pod(S.update_flops);
-  io.pod(S.dense_flops); io.pod(S.update_flops_pad);
-  io.vec(S.perm); io.vec(S.iperm); io.vec(S.parent); io.vec(S.colcount); io.vec(S.sn_start); io.vec(S.sn_parent);
-  io.vec(S.sn_rowptr); io.vec(S.sn_rows); io.vec(S.sn_loff); io.vec(S.sn_level); io.vec(S.child_ptr); io.vec(S.child_idx);
-  io.vec(S.upd_ptr); io.vec(S.upd_src); io.vec(S.upd_p0); io.vec(S.upd_p1); io.vec(S.upd_jp0);
-  io.vec(S.tile_base); io.vec(S.tile_front);
-  io.vec(S.level_tile_ptr); io.vec(S.level_tiles); io.vec(S.level_pair_ptr); io.vec(S.level_pairs);
-  io.vec(S.level_ptr); io.vec(S.level_fronts);
-  io.vec(S.asm_dst); io.vec(S.diag_dst); io.vec(S.pat_colptr); io.vec(S.pat_row); io.vec(S.inv_off);
-  io.vec(S.tail_blk_ptr); io.vec(S.tail_blk);
-  io.vecvec(S.val_slot); io.vecvec(S.val_src); io.vec(S.is_diag);
-}
-}  // namespace
-
+// Deterministic mode, on demand: the pull schedule of the sweeps and the transposed pattern index (symbolic.h).
 void build_pull_schedule(Symbolic* Sp) {
   Symbolic& S = *Sp;
   if (S.pull_built) return;
@@ -1432,70 +1518,6 @@ bool build_row_index(Symbolic* Sp) {
     }
   S.rowidx_built = true;
   return true;
-}
-
-bool symbolic_save(const Symbolic& S, const char* path, uint64_t key) {
-  // a name of this writer's own (pid + clock + address entropy): ranks that miss the cache at the same time each write a
-  // complete image and the LAST rename wins -- none truncates a file another one is still writing
-  char suffix[96];
-  const uint64_t salt = (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() ^ (uint64_t)(uintptr_t)&S;
-  snprintf(suffix, sizeof suffix, ".tmp.%ld.%016llx", (long)getpid(), (unsigned long long)salt);
-  const std::string tmp = std::string(path) + suffix;
-  FILE* fp = fopen(tmp.c_str(), "wbx");  // (x: fail rather than share a name)
-  if (!fp) return false;
-  ImageIO io{fp, true};
-  uint64_t magic = kImageMagic, k = key, nb = (uint64_t)SCILMM_NB;
-  io.pod(magic); io.pod(k); io.pod(nb);
-  image_fields(io, const_cast<Symbolic&>(S));
-  uint64_t trailer[2] = {io.bytes, io.checksum()};
-  const bool wrote = io.ok && fwrite(trailer, sizeof(uint64_t), 2, fp) == 2;
-  const bool ok = (fclose(fp) == 0) && wrote;
-  if (!ok) { remove(tmp.c_str()); return false; }
-  if (rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return false; }  // readers never see a half-written image
-  return true;
-}
-
-Symbolic* symbolic_load(const char* path, uint64_t key) {
-  FILE* fp = fopen(path, "rb");
-  if (!fp) return nullptr;
-  ImageIO io{fp, false};
-  uint64_t magic = 0, k = 0, nb = 0;
-  io.pod(magic); io.pod(k); io.pod(nb);
-  if (!io.ok || magic != kImageMagic || k != key || nb != (uint64_t)SCILMM_NB) { fclose(fp); return nullptr; }
-  Symbolic* S = new Symbolic();
-  image_fields(io, *S);
-  uint64_t trailer[2] = {0, 0};
-  const bool trailer_ok = io.ok && fread(trailer, sizeof(uint64_t), 2, fp) == 2 && trailer[0] == io.bytes && trailer[1] == io.checksum() &&
-                          fgetc(fp) == EOF;
-  fclose(fp);
-  // structural sanity: sizes must agree with the header fields, indices must stay inside what they index
-  bool sane = trailer_ok && S->n >= 0 && S->nsuper >= 0 && (int64_t)S->perm.size() == S->n && (int64_t)S->iperm.size() == S->n &&
-              (int64_t)S->sn_start.size() == (int64_t)S->nsuper + 1 && (int64_t)S->sn_rowptr.size() == (int64_t)S->nsuper + 1 &&
-              (int64_t)S->sn_loff.size() >= S->nsuper && (int64_t)S->asm_dst.size() == S->nnz_pattern &&
-              (int64_t)S->diag_dst.size() == S->n && (int64_t)S->pat_colptr.size() == (int64_t)S->n + 1 &&
-              (int64_t)S->val_slot.size() == S->K && (int64_t)S->val_src.size() == S->K &&
-              (int64_t)S->level_ptr.size() == (int64_t)S->nlevels + 1;
-  if (sane) {
-    const int64_t n = S->n, nst = S->nnzL_stored;
-    bool ok_perm = true, ok_rows = true, ok_asm = true;
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t p = S->perm[(size_t)i];
-      if (p < 0 || p >= n || S->iperm[(size_t)p] != (int32_t)i) { ok_perm = false; break; }
-    }
-    const int64_t nrows = (int64_t)S->sn_rows.size();
-    if (nrows != S->sn_rowptr[(size_t)S->nsuper]) ok_rows = false;
-#pragma omp parallel for reduction(&& : ok_rows) num_threads(host_threads()) if (nrows > (1 << 20))
-    for (int64_t t = 0; t < nrows; ++t) ok_rows = ok_rows && S->sn_rows[(size_t)t] >= 0 && S->sn_rows[(size_t)t] < n;
-    const int64_t nasm = (int64_t)S->asm_dst.size();
-#pragma omp parallel for reduction(&& : ok_asm) num_threads(host_threads()) if (nasm > (1 << 20))
-    for (int64_t t = 0; t < nasm; ++t) ok_asm = ok_asm && S->asm_dst[(size_t)t] >= 0 && S->asm_dst[(size_t)t] < nst;
-    for (int64_t j = 0; j < n && ok_asm; ++j) ok_asm = S->diag_dst[(size_t)j] >= 0 && S->diag_dst[(size_t)j] < nst;
-    sane = ok_perm && ok_rows && ok_asm;
-  }
-  if (!sane) { delete S; return nullptr; }
-  S->combos_built = false;
-  // (tile combo arrays of a fresh analysis are sized by build_tile_combos on demand)
-  return S;
 }
 
 }  // namespace scilmm

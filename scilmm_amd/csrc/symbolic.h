@@ -6,6 +6,9 @@
 #define SCILMM_NB 128
 #endif
 #include <cstdint>
+#include <cstdio>
+#include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -46,6 +49,24 @@ struct SymbolicOptions {
   double dense_relax_wide = 1.25;
   int32_t dense_wide_cols = 32768;
 };
+
+// The environment switches of the analysis, read once per call by read_analysis_switches() (symbolic.cpp): the only place
+// of the host analysis that reads the environment.  The tail_* switches are honoured only with SCILMM_TUNING=1, like the
+// schedule switches of dev.h, and change the result: scilmm_amd/factor.py lists their names in the key of the analysis
+// cache (tests/test_symbolic.py holds the two lists together).  The diagnostics are not gated and change nothing.
+struct AnalysisSwitches {
+  double tail_elig = 0.5;           // SCILMM_TAIL_ELIG: a front joins the dense tail when its true rows fill this share of its padded list
+  int32_t tail_delay = 0;           // SCILMM_TAIL_DELAY: start the tail chain this many levels later
+  std::optional<double> tail_wide;  // SCILMM_TAIL_WIDE: replaces SymbolicOptions::dense_relax_wide
+  bool verbose = false;             // SCILMM_VERBOSE: the [scilmm symbolic] lines
+  const char* tail_dump = nullptr;  // SCILMM_TAIL_DUMP: file that receives every candidate of the dense-tail selection
+};
+AnalysisSwitches read_analysis_switches();
+
+struct FileCloser {
+  void operator()(FILE* f) const { if (f) fclose(f); }
+};
+using FilePtr = std::unique_ptr<FILE, FileCloser>;
 
 // Everything the numeric phase needs.  "Front" s owns columns [sn_start[s], sn_start[s+1]) of the
 // permuted matrix, has m = rows.size() rows (the first w are its own columns), stores its
@@ -157,6 +178,8 @@ struct Symbolic {
 
 // indptr[k]/indices[k]: CSR of matrix k (both triangles or lower only; only j<=i is read).
 // perm_in: optional user permutation (perm_in[new] = old), required when opts.ordering == 2.
+// Returns an analysis whose `error` is set when the permutation is refused; throws (std::bad_alloc, std::system_error)
+// when the host runs out of memory or threads -- nothing is leaked and no thread is left behind then.
 Symbolic* symbolic_analyze(int32_t n, int32_t K, const int64_t* const* indptr, const int32_t* const* indices,
                            const int32_t* perm_in, const SymbolicOptions& opts);
 
@@ -174,6 +197,7 @@ bool build_row_index(Symbolic* S);
 
 // Binary image of an analysis (everything but the lazily built tile combos); `key` = the caller's hash of the inputs the
 // analysis depends on (patterns, permutation, options): symbolic_load returns NULL unless it matches.
+// (symbolic_image.cpp)
 bool symbolic_save(const Symbolic& S, const char* path, uint64_t key);
 Symbolic* symbolic_load(const char* path, uint64_t key);
 

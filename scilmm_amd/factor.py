@@ -95,7 +95,8 @@ class Symbolic(object):
         if upload:
             self.upload_values()
 
-    # every environment variable the host analysis reads (csrc/symbolic.cpp, csrc/capi_symbolic.cpp): part of the cache key
+    # every environment variable that changes what the host analysis computes (read_analysis_switches in csrc/symbolic.cpp,
+    # its only reader of the environment; tests/test_symbolic.py compares the two lists): part of the cache key
     _ANALYSIS_ENV = ("SCILMM_TUNING", "SCILMM_TAIL_WIDE", "SCILMM_TAIL_ELIG", "SCILMM_TAIL_DELAY")
     # bumped whenever the analysis changes what it produces for the same input (the library's magic number guards the FORMAT of
     # the image, this constant and scilmm_version() its CONTENT)

@@ -285,7 +285,7 @@ def test_profiled_factorization_reports_consistent_timings(monkeypatch, tmp_path
                                  {"SCILMM_OUTSIDE": "1"}])
 def test_moved_dense_tail_matches_oracle(monkeypatch, env):
     """A pedigree whose dense tail is NOT a chain of the elimination tree (a side branch of near-dense fronts joins it
-    and the tail is moved to the end of the order; symbolic.cpp step 7a): every schedule must match the oracle."""
+    and the tail is moved to the end of the order; symbolic.cpp move_tail_to_end): every schedule must match the oracle."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     monkeypatch.setenv("SCILMM_TUNING", "1")

@@ -333,3 +333,43 @@ def test_symbolic_image_round_trip(tmp_path):
         fh.truncate(os.path.getsize(f) // 2)
     s3 = Symbolic(mats, upload=False, cache=d)                                            # damaged image: analysed afresh
     assert not s3.from_cache and np.array_equal(s3.get("perm"), s1.get("perm"))
+
+
+def test_analysis_image_does_not_depend_on_the_thread_count(tmp_path):
+    """The image of an analysis is the same bytes whatever the size of the host thread team: a pedigree whose dense tail has a
+    side branch (the tail is moved to the end of the order and its clique sorted, so the column counts of the final order are
+    taken again by the worker beside the main path and handed over at the join), analysed in fresh processes -- the team
+    size is fixed once per process -- with one thread and with 16."""
+    import os
+    import subprocess
+    import sys
+    script = os.path.join(os.path.dirname(__file__), "symbolic_image_script.py")
+    outs = []
+    for threads in ("1", "16"):
+        d = tmp_path / ("threads" + threads)
+        d.mkdir()
+        env = dict(os.environ, SCILMM_HOST_THREADS=threads)
+        env.pop("SCILMM_SYMBOLIC_CACHE", None)
+        p = subprocess.run([sys.executable, script, str(d)], env=env, timeout=300, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs.append(p.stdout)
+    assert len(outs[0].split()) == 2 and len(outs[0].split()[1]) == 64
+    assert outs[0] == outs[1]
+
+
+def test_analysis_switches_are_the_cache_keys_environment():
+    """Every environment variable that changes what the analysis computes is part of the key of the analysis cache: the names
+    read by read_analysis_switches (csrc/symbolic.cpp) are Symbolic._ANALYSIS_ENV, but for the two diagnostics that change
+    nothing, and nothing else in the host analysis reads the environment."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scilmm_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in ("symbolic.cpp", "symbolic_image.cpp", "capi_symbolic.cpp")}
+    reader = re.search(r"^AnalysisSwitches read_analysis_switches\(\) \{\n(.*?)^\}", text["symbolic.cpp"], re.S | re.M)
+    assert reader, "read_analysis_switches not found in symbolic.cpp"
+    names = set(re.findall(r'"(SCILMM_\w+)"', reader.group(1)))
+    assert {"SCILMM_VERBOSE", "SCILMM_TAIL_DUMP"} <= names
+    assert names - {"SCILMM_VERBOSE", "SCILMM_TAIL_DUMP"} == set(Symbolic._ANALYSIS_ENV)
+    text["symbolic.cpp"] = text["symbolic.cpp"].replace(reader.group(0), "")
+    others = {f: re.findall(r'getenv\(\s*"(SCILMM_\w*)', t) for f, t in text.items()}
+    assert others == {"symbolic.cpp": [], "symbolic_image.cpp": [], "capi_symbolic.cpp": ["SCILMM_DETERMINISTIC"]}
