@@ -221,6 +221,32 @@ int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_g
  * it: ms[0] moments + dequantise (+ permute), ms[1] forward sweep, ms[2] statistics (tools/assoc_timing.py). */
 int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);
 
+/* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
+ * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y
+ * (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1) per column by the scan's algebra: predicted value, prediction error variance
+ * and reliability of an individual for one forward-sweep column, with no matrix on the host.
+ * scilmm_rel_block_dev takes the columns from the RESIDENT values: column c = (sum_k weights[k] A_k)[:, ids[c]].
+ *   weights: HOST, one per matrix of the analysis (a zero weight leaves the matrix unread).
+ *   ids    : HOST, r individuals in the ORIGINAL order (the row order of the matrices), distinct, each in 0 .. n-1.
+ * scilmm_rows_block_dev takes them from the caller: column c = row c of an r-row CSR matrix, all DEVICE pointers,
+ *   d_indptr int64[r + 1], d_indices int32 in the ORIGINAL order of the individuals, d_data double.  An index outside
+ *   0 .. n-1 is skipped, never stored; the indices of a row must be distinct, and d_indptr must be ascending inside the
+ *   two arrays (it is not read on the host).
+ *   r      : columns in the block, 1 .. 128.
+ *   d_Q    : as for scilmm_scan_block_dev, 1 <= q <= 32.
+ *   d_stats: (q + 2) x r row-major: the column's own diagonal entry G[i, i] (0 from the rows form) | |w(g)|^2 | the q rows
+ *            of Q^T w(g).
+ * The block is cleared and then only stored into (every entry has one writer, no atomics in either mode of the handle);
+ * the forward sweep and the statistics are those of scilmm_scan_block_dev, so scilmm_scan_timing reports block building |
+ * forward sweep | statistics for these blocks too.  Everything is enqueued on the handle's stream without synchronising.
+ * Null pointers, r or q out of range, an id outside 0 .. n-1 or repeated: SCILMM_ERR_ARG before anything is dereferenced;
+ * refusals as for the half-solves.  No counterpart in the reference (it stops at the variance components and the
+ * covariates' coefficients). */
+int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
+                         double* d_stats);
+int scilmm_rows_block_dev(scilmm_factor* fac, const int64_t* d_indptr, const int32_t* d_indices, const double* d_data, int32_t r,
+                          const double* d_Q, int32_t q, double* d_stats);
+
 /* SURVEY section 8f rank 4 -- the exact tr(V^-1 A_k) of the gradient instead of the reference's Monte-Carlo estimate
  * (scilmm/SparseCholesky.py:49-52, :65).  scilmm_selected_inverse replaces, IN PLACE, every stored entry of the factor by
  * the entry of Z = (V[P][:,P])^-1 at the same position (Takahashi recursion over the supernodes from the last level

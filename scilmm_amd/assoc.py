@@ -50,16 +50,15 @@ def check_genotypes(genotypes, n):
     return g
 
 
-class AssociationScan(object):
-    """Tests many candidate fixed effects next to ``covariates`` under V = sum_k sigma2[k] mats[k].
-
-    ``cholesky_func``: a ``SparseCholesky``; ``mats``: every matrix of V (the identity included), as ``_final_factor`` takes
-    them; ``sigma2``: one coefficient per matrix; ``covariates``: n x c (an intercept column is the caller's); ``y``: n.
-    ``block``: markers per device block, 1..128.  The resident factor of ``(mats, sigma2)`` is obtained or re-used; a scan
-    object is tied to it and refuses to run once the factor has been refactorized at other values (build a new one)."""
+class WhitenedModel(object):
+    """What the marker scan and the BLUP share: the resident factor of ``(mats, sigma2)``, obtained or re-used through
+    ``_final_factor``, and ``Q = L^-1 P [C | y]`` whitened once and kept in HBM, with ``R'R = w(C)'w(C)`` and
+    ``u = R^-T w(C)'w(y)`` on the host.  An object is tied to that factor and refuses to run (``_check_factor``) once the
+    factor has been refactorized at other values."""
 
     def __init__(self, cholesky_func, mats, sigma2, covariates, y, block=None):
         from .SparseCholesky import SparseCholesky, _device_buffers, _final_factor
+        who = type(self).__name__
         if block is None:
             block = DEFAULT_BLOCK
         if not (isinstance(block, (int, np.integer)) and 1 <= block <= RPMAX):
@@ -72,11 +71,11 @@ class AssociationScan(object):
         if not 1 <= c + 1 <= QMAX:
             raise ValueError("at most %d covariates" % (QMAX - 1))
         if not isinstance(cholesky_func, SparseCholesky):
-            raise _lib.ScilmmError("AssociationScan needs the device engine (a scilmm_amd.SparseCholesky): there is no CPU form")
+            raise _lib.ScilmmError("%s needs the device engine (a scilmm_amd.SparseCholesky): there is no CPU form" % who)
         _lib.lib()
         torch = _device_buffers()
         if torch is None:
-            raise _lib.ScilmmError("AssociationScan needs a GPU that torch can reach (device buffers): there is no CPU form")
+            raise _lib.ScilmmError("%s needs a GPU that torch can reach (device buffers): there is no CPU form" % who)
         self.torch, self.block, self.c, self.q = torch, int(block), c, c + 1
         self.factor = fac = _final_factor(cholesky_func, mats, np.asarray(sigma2, dtype=np.float64))
         self.sym = sym = fac.sym
@@ -94,7 +93,24 @@ class AssociationScan(object):
         G = (self.dQ.T @ self.dQ).cpu().numpy()              # [w(C) | w(y)]' [w(C) | w(y)]: (c + 1) x (c + 1)
         self.R = la.cholesky(G[:c, :c], lower=False)         # R' R = w(C)' w(C)
         self.u = la.solve_triangular(self.R, G[:c, c], trans='T', lower=False)   # R^-T w(C)' w(y)
-        self._f = stats.f(1, n - 1)
+
+    def _check_factor(self):
+        if not self.factor.holds(self._s2):
+            raise _lib.ScilmmError("the resident factor no longer holds the sigma2 this object was whitened with: build a new "
+                                   "%s" % type(self).__name__)
+
+
+class AssociationScan(WhitenedModel):
+    """Tests many candidate fixed effects next to ``covariates`` under V = sum_k sigma2[k] mats[k].
+
+    ``cholesky_func``: a ``SparseCholesky``; ``mats``: every matrix of V (the identity included), as ``_final_factor`` takes
+    them; ``sigma2``: one coefficient per matrix; ``covariates``: n x c (an intercept column is the caller's); ``y``: n.
+    ``block``: markers per device block, 1..128.  The resident factor of ``(mats, sigma2)`` is obtained or re-used; a scan
+    object is tied to it and refuses to run once the factor has been refactorized at other values (build a new one)."""
+
+    def __init__(self, cholesky_func, mats, sigma2, covariates, y, block=None):
+        super(AssociationScan, self).__init__(cholesky_func, mats, sigma2, covariates, y, block)
+        self._f = stats.f(1, self.n - 1)
 
     def _stats(self, genotypes):
         """(q + 4) x m statistics of ``scilmm_scan_block_dev`` for every marker, in chunks of whole blocks."""
@@ -127,9 +143,7 @@ class AssociationScan(object):
         are mean-imputed).  Returns a dict of length-m arrays ``beta``, ``se``, ``chi2``, ``p``, ``n_obs``, ``mean``; a
         marker without an observed value or without variation gets NaN in the first four."""
         g = check_genotypes(genotypes, self.n)
-        if not self.factor.holds(self._s2):
-            raise _lib.ScilmmError("the resident factor no longer holds the sigma2 this scan was whitened with: build a new "
-                                   "AssociationScan")
+        self._check_factor()
         m, c = g.shape[0], self.c
         S = self._stats(g) if m else np.empty((self.q + 4, 0))
         n_obs, mean, css, gg = S[0], S[1].copy(), S[2], S[3]

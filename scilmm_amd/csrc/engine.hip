@@ -11,7 +11,8 @@
 //   Sweep (run_rhs): solve_single (= forward_single, mark_mid, backward_single: the half-solves run one of the two),
 //     solve_dist, lmul_single, lmul_dist per block of RPMAX columns, built from pull / pull_groups (deterministic mode),
 //     chain, handoff (distributed) and mark_mid;
-//   Scan block (scilmm_scan_block_dev): the kernels of scan.hip.h around Sweep::forward_single.
+//   Scan block (scilmm_scan_block_dev): the kernels of scan.hip.h around Sweep::forward_single;
+//   BLUP blocks (scilmm_rel_block_dev, scilmm_rows_block_dev): the kernels of blup.hip.h in front of the same sweep and statistics.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +32,7 @@
 
 #include "kernels.hip.h"
 #include "scan.hip.h"
+#include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
 
@@ -1259,25 +1261,21 @@ int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double*
   return half_rhs(fac, dB, r, dX, RHS_SOLVE_LT, false, "scilmm_solve_Lt_dev");
 }
 
-int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
-                          double* d_stats) {
-  if (!fac || !d_geno || !d_Q || !d_stats || r < 1 || r > RPMAX || q < 1 || q > SCAN_QMAX) return SCILMM_ERR_ARG;
-  if (!fac->sym || !fac->sym->S || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  DevGuard guard(fac->sym);
+// What the three block entry points (marker scan, relationship columns, caller rows) share around their own producer of
+// the right-hand-side block.  block_begin: the refusals, the one allocation of the slice partial sums (first call on a
+// handle, or a wider q; nothing is allocated per block afterwards), the events and the inverse permutation.
+static int block_begin(scilmm_factor* fac, int32_t q, const char* who) {
   scilmm_symbolic* sym = fac->sym;
-  int st = check_half(fac, "scilmm_scan_block_dev");
+  int st = check_half(fac, who);
   if (st != SCILMM_OK) return st;
   st = begin_rhs(fac);
   if (st != SCILMM_OK) return st;
   Dev* D = (Dev*)sym->device;
   const Symbolic& S = *sym->S;
-  const int32_t n = S.n;
-  hipStream_t s0 = D->stream;
-  const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
-  // (first call on a handle, or a wider q: the one allocation of the scan; nothing is allocated per block afterwards)
+  const int64_t nslice = ((int64_t)S.n + SCAN_SLICE - 1) / SCAN_SLICE;
   const size_t need = (size_t)nslice * (size_t)(q + 1) * RPMAX;
   if (D->scan_partial_cap < need) {
-    HIPCHK(hipStreamSynchronize(s0));
+    HIPCHK(hipStreamSynchronize(D->stream));
     if (D->scan_partial) (void)hipFree(D->scan_partial);
     D->scan_partial = nullptr;
     D->scan_partial_cap = 0;
@@ -1290,6 +1288,42 @@ int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_g
     st = upload(sym, D, S.iperm, &D->d_iperm);
     if (st != SCILMM_OK) return st;
   }
+  return SCILMM_OK;
+}
+
+// block_finish: W holds the block (event 1 is recorded here): the forward sweep, then |x_c|^2 and Q^T x_c from one pass over
+// X, in fixed row slices folded in slice order, to d_out ((q + 1) x r).
+static int block_finish(Sweep& sw, int32_t r, const double* d_Q, int32_t q, double* d_out) {
+  Dev* D = sw.D;
+  scilmm_symbolic* sym = sw.sym;
+  const int32_t n = sw.S.n;
+  hipStream_t s0 = D->stream;
+  const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
+  HIPCHK(hipEventRecord(D->scan_ev[1], s0));
+  int st = sw.forward_single();
+  if (st != SCILMM_OK) return st;
+  HIPCHK(hipEventRecord(D->scan_ev[2], s0));
+  const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
+  hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, sw.rp, (const double*)D->X, d_Q, q, D->scan_partial);
+  hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_out);
+  HIPCHK(hipEventRecord(D->scan_ev[3], s0));
+  D->scan_pending = true;
+  if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
+int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
+                          double* d_stats) {
+  if (!fac || !d_geno || !d_Q || !d_stats || r < 1 || r > RPMAX || q < 1 || q > SCAN_QMAX) return SCILMM_ERR_ARG;
+  if (!fac->sym || !fac->sym->S || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
+  DevGuard guard(fac->sym);
+  scilmm_symbolic* sym = fac->sym;
+  int st = block_begin(fac, q, "scilmm_scan_block_dev");
+  if (st != SCILMM_OK) return st;
+  Dev* D = (Dev*)sym->device;
+  const int32_t n = sym->S->n;
+  hipStream_t s0 = D->stream;
   Sweep sw(fac, D);
   sw.set_block(r);
   const int32_t rp = sw.rp;
@@ -1300,19 +1334,89 @@ int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_g
   const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
   hipLaunchKernelGGL(k_scan_dequant, dim3(tiles), dim3(256), 0, s0, n, r, rp, d_geno, ld_geno, (const int32_t*)D->d_iperm,
                      (const double*)(d_stats + r), D->W);
-  HIPCHK(hipEventRecord(D->scan_ev[1], s0));
-  st = sw.forward_single();
+  // rows 3..: |w(g)|^2 and Q^T w(g)
+  return block_finish(sw, r, d_Q, q, d_stats + 3 * (int64_t)r);
+}
+
+int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
+                         double* d_stats) {
+  if (!fac || !weights || !ids || !d_Q || !d_stats || r < 1 || r > RPMAX || q < 1 || q > SCAN_QMAX) return SCILMM_ERR_ARG;
+  if (!fac->sym || !fac->sym->S) return SCILMM_ERR_ARG;
+  DevGuard guard(fac->sym);
+  scilmm_symbolic* sym = fac->sym;
+  const Symbolic& S = *sym->S;
+  const int32_t n = S.n;
+  // the requests sorted by permuted index: the kernel bisects this list; a repeated individual shows as a repeated index
+  std::pair<int32_t, int32_t> order[RPMAX];
+  for (int32_t c = 0; c < r; ++c) {
+    if (ids[c] < 0 || ids[c] >= n) {
+      sym->err = "scilmm_rel_block_dev: an individual outside 0 .. n-1";
+      return SCILMM_ERR_ARG;
+    }
+    order[c] = {S.iperm[(size_t)ids[c]], c};
+  }
+  std::sort(order, order + r);
+  for (int32_t c = 1; c < r; ++c)
+    if (order[c].first == order[c - 1].first) {
+      sym->err = "scilmm_rel_block_dev: an individual is requested twice in one block";
+      return SCILMM_ERR_ARG;
+    }
+  int st = block_begin(fac, q, "scilmm_rel_block_dev");
   if (st != SCILMM_OK) return st;
-  HIPCHK(hipEventRecord(D->scan_ev[2], s0));
-  // rows 3..: |w(g)|^2 and Q^T w(g) from one pass over X, in fixed row slices folded in slice order
-  const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
-  hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, rp, (const double*)D->X, d_Q, q, D->scan_partial);
-  hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_stats + 3 * (int64_t)r);
-  HIPCHK(hipEventRecord(D->scan_ev[3], s0));
-  D->scan_pending = true;
-  if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
-  HIPCHK(hipGetLastError());
-  return SCILMM_OK;
+  Dev* D = (Dev*)sym->device;
+  ValPtrs gen{}, dia{};
+  for (int k = 0; k < S.K; ++k) {
+    if (weights[k] == 0.0) continue;
+    if (!D->have_vals[k]) {
+      sym->err = "scilmm_rel_block_dev: the values of a matrix with a nonzero weight are not resident";
+      return SCILMM_ERR_STATE;
+    }
+    ValPtrs& t = S.is_diag[k] ? dia : gen;
+    if (t.count >= 8) {
+      sym->err = "more than 8 matrices of one kind";
+      return SCILMM_ERR_ARG;
+    }
+    t.v[t.count] = D->vals[k];
+    t.s2[t.count] = weights[k];
+    t.count++;
+  }
+  RelReq req{};
+  for (int32_t c = 0; c < r; ++c) {
+    req.p[c] = order[c].first;
+    req.col[c] = order[c].second;
+  }
+  hipStream_t s0 = D->stream;
+  Sweep sw(fac, D);
+  sw.set_block(r);
+  HIPCHK(hipEventRecord(D->scan_ev[0], s0));
+  HIPCHK(hipMemsetAsync(D->W, 0, sizeof(double) * (size_t)sw.tot, s0));
+  // W = P G[:, ids]: the stored columns (r workgroups), then one streaming pass over the pattern for the row parts; row 0 of
+  // the statistics = G[i, i]
+  const unsigned pass = gen.count > 0 ? (unsigned)std::min<int64_t>((S.nnz_pattern + 255) / 256, REL_GRID) : 0u;
+  hipLaunchKernelGGL(k_rel_gather, dim3((unsigned)r + pass), dim3(256), 0, s0, D->v, S.nnz_pattern, gen, dia, req, r, sw.rp, D->W,
+                     d_stats);
+  return block_finish(sw, r, d_Q, q, d_stats + (int64_t)r);
+}
+
+int scilmm_rows_block_dev(scilmm_factor* fac, const int64_t* d_indptr, const int32_t* d_indices, const double* d_data, int32_t r,
+                          const double* d_Q, int32_t q, double* d_stats) {
+  if (!fac || !d_indptr || !d_indices || !d_data || !d_Q || !d_stats || r < 1 || r > RPMAX || q < 1 || q > SCAN_QMAX)
+    return SCILMM_ERR_ARG;
+  if (!fac->sym || !fac->sym->S) return SCILMM_ERR_ARG;
+  DevGuard guard(fac->sym);
+  scilmm_symbolic* sym = fac->sym;
+  int st = block_begin(fac, q, "scilmm_rows_block_dev");
+  if (st != SCILMM_OK) return st;
+  Dev* D = (Dev*)sym->device;
+  hipStream_t s0 = D->stream;
+  Sweep sw(fac, D);
+  sw.set_block(r);
+  HIPCHK(hipEventRecord(D->scan_ev[0], s0));
+  HIPCHK(hipMemsetAsync(D->W, 0, sizeof(double) * (size_t)sw.tot, s0));
+  // W[iperm[idx]][c] = data: a wave per row; row 0 of the statistics = 0
+  hipLaunchKernelGGL(k_rows_scatter, dim3((unsigned)((r + 3) / 4)), dim3(256), 0, s0, sym->S->n, r, sw.rp, d_indptr, d_indices, d_data,
+                     (const int32_t*)D->d_iperm, D->W, d_stats);
+  return block_finish(sw, r, d_Q, q, d_stats + (int64_t)r);
 }
 
 int scilmm_quadforms_dev(scilmm_symbolic* sym, int32_t k, const double* dU, int32_t r, double* d_out) {

@@ -411,6 +411,20 @@ class Factor(object):
         """One block of the marker scan (``scilmm_scan_block_dev``; ``scilmm_amd.assoc.AssociationScan`` is the interface)."""
         check(lib().scilmm_scan_block_dev(self._h, dG_ptr, ld, r, dQ_ptr, q, dstats_ptr), self.sym._h)
 
+    def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
+        """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host
+        ``weights`` and ``ids``, device ``Q`` and statistics; ``scilmm_amd.blup.BLUP`` is the interface)."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if w.shape != (self.sym.K,) or ids.ndim != 1:
+            raise ValueError("weights must have one entry per matrix, ids must be 1-D")
+        check(lib().scilmm_rel_block_dev(self._h, ptr(w), ptr(ids), ids.size, dQ_ptr, q, dstats_ptr), self.sym._h)
+
+    def rows_block_dev(self, dindptr_ptr, dindices_ptr, ddata_ptr, r, dQ_ptr, q, dstats_ptr):
+        """The same for ``r`` caller rows in CSR on the device (``scilmm_rows_block_dev``): int64 ``indptr``, int32
+        ``indices`` in the matrices' row order, float64 ``data``."""
+        check(lib().scilmm_rows_block_dev(self._h, dindptr_ptr, dindices_ptr, ddata_ptr, r, dQ_ptr, q, dstats_ptr), self.sym._h)
+
     def inverse_traces(self):
         """tr(V^-1 A_k) for every matrix of the analysis, exactly: the selected inverse on the supernodal factor (Takahashi
         recursion on the device, in place) followed by one pass over each A_k's pattern.  CONSUMES the factor: it must be
