@@ -1,5 +1,7 @@
 // Device state of a symbolic handle (struct Dev), the schedule switches (struct Tuning) and the small helpers shared by
-// the two device translation units: plan.hip builds the state once per handle, engine.hip runs the launch sequences on it.
+// the device translation units: HIPCHK / TRY, DevGuard, the owner of a call's temporary device memory (DevScratch) and
+// the handle's grow-only buffers (grow, ensure_io, ensure_vals, ensure_iperm).  plan.hip builds the state once per handle,
+// engine.hip and the headers it includes run the launch sequences on it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,8 +124,8 @@ struct Dev {
   double* X = nullptr;
   double* IO = nullptr;            // staging for host<->device dense transfers
   size_t io_cap = 0;
-  double* partial = nullptr;
-  int64_t nwaves_quad = 0;
+  double* partial = nullptr;       // block partial sums of the quadratic forms
+  size_t partial_cap = 0;          // doubles
   double* d_out = nullptr;         // RPMAX doubles
   bool use_mfma = true;
   bool trsm_lite = true;           // k_trsm_lite instead of k_trsm<true> (SCILMM_TUNING=1 SCILMM_TRSM_LITE=0: the round-1 kernel)
@@ -258,7 +260,7 @@ struct Dev {
   int32_t* d_chain_err = nullptr;    // [0] error flag, [1] progress beacon, [2] ticket counter of the running sweep
   int32_t* h_chain_err = nullptr;    // pinned mirror of [0], refreshed by a queued copy after every solve
   int32_t chain_epoch = 0;
-  std::vector<hipEvent_t> pev;     // profiling: PEV_PER_LEVEL events per level (enum ProfEvent, engine.hip)
+  std::vector<hipEvent_t> pev;     // profiling: PEV_PER_LEVEL events per level (enum ProfEvent, factorize.hip.h)
   // deterministic mode (scilmm_set_deterministic): pull schedule of the forward sweep / L*R, transposed pattern index
   bool det = false;
   PullPlan pull{};
@@ -270,7 +272,7 @@ struct Dev {
   const int64_t* d_pat_rowslot = nullptr;
   const int32_t* d_pat_rowcol = nullptr;
   int64_t n_float_atomic = 0;           // launches since the handle was created that sum with floating-point atomics
-  // marker scan (scilmm_scan_block_dev): slice partial sums of the statistics, inverse permutation (original -> permuted row)
+  // marker scan and BLUP blocks: slice partial sums of the statistics; inverse permutation (ensure_iperm: the blocks, IBD and dominance values)
   double* scan_partial = nullptr;       // [slices][q + 1][RPMAX]
   size_t scan_partial_cap = 0;          // doubles
   const int32_t* d_iperm = nullptr;
@@ -287,6 +289,53 @@ struct Dev {
       return SCILMM_ERR_DEVICE;                                                                        \
     }                                                                                                  \
   } while (0)
+
+#define TRY(call)                      \
+  do {                                 \
+    int _rc = (call);                  \
+    if (_rc != SCILMM_OK) return _rc;  \
+  } while (0)
+
+// Temporary device memory of one call: whatever alloc / upload handed out is freed when the owner goes out of scope, on
+// every return path.  A failure is reported as HIPCHK does, to *err: a handle's sym->err, or a message that belongs to no
+// handle (dominance.hip).
+struct DevScratch {
+  std::string* const err;
+  std::vector<void*> held;
+
+  explicit DevScratch(std::string* e) : err(e) {}
+  DevScratch(const DevScratch&) = delete;
+  DevScratch& operator=(const DevScratch&) = delete;
+  ~DevScratch() {
+    for (void* p : held) (void)hipFree(p);
+  }
+
+  int fail(const char* call, hipError_t e) const {
+    *err = std::string(call) + ": " + hipGetErrorString(e);
+    return SCILMM_ERR_DEVICE;
+  }
+  // count elements of T (at least 8 bytes, so that an empty array still has an address)
+  template <typename T>
+  int alloc(size_t count, T** out) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 8));
+    if (e != hipSuccess) return fail("hipMalloc", e);
+    held.push_back(p);
+    *out = (T*)p;
+    return SCILMM_OK;
+  }
+  // ... filled from the host (pageable memory: the copy has left h when this returns)
+  template <typename T>
+  int upload(const T* h, size_t count, T** out, hipStream_t stream = nullptr) {
+    TRY(alloc(count, out));
+    const hipError_t e = count ? hipMemcpyAsync(*out, h, count * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess;
+    return e == hipSuccess ? SCILMM_OK : fail("hipMemcpyAsync", e);
+  }
+  template <typename T>
+  int upload(const std::vector<T>& h, T** out, hipStream_t stream = nullptr) {
+    return upload(h.data(), h.size(), out, stream);
+  }
+};
 
 // Makes the handle's device current for the duration of an entry point and restores the caller's device afterwards
 // (a handle may be used from a thread whose current device is a different one).
@@ -319,6 +368,35 @@ int upload(scilmm_symbolic* sym, Dev* D, const std::vector<T>& h, P** out) {
   if (!h.empty()) HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   *out = (P*)p;
   return SCILMM_OK;
+}
+
+// Grow-only device buffer of a handle: kept while it holds `need` elements, else replaced by one that does (the old
+// contents are dropped).  The caller has made sure that nothing queued still uses the old one.
+template <typename T>
+int grow(scilmm_symbolic* sym, T** ptr, size_t* cap, size_t need) {
+  if (*ptr && *cap >= need) return SCILMM_OK;
+  if (*ptr) (void)hipFree(*ptr);
+  *ptr = nullptr;
+  *cap = 0;
+  HIPCHK(hipMalloc((void**)ptr, std::max<size_t>(need, 1) * sizeof(T)));
+  *cap = need;
+  return SCILMM_OK;
+}
+
+// staging for host <-> device dense transfers
+inline int ensure_io(scilmm_symbolic* sym, Dev* D, size_t doubles) { return grow(sym, &D->IO, &D->io_cap, doubles); }
+
+// the value array of matrix k: pattern-slot order, or one value per row for a diagonal-only matrix
+inline int ensure_vals(scilmm_symbolic* sym, Dev* D, int32_t k) {
+  const Symbolic& S = *sym->S;
+  if (D->vals[k]) return SCILMM_OK;
+  HIPCHK(hipMalloc((void**)&D->vals[k], std::max<size_t>(S.is_diag[k] ? (size_t)S.n : (size_t)S.nnz_pattern, 1) * sizeof(double)));
+  return SCILMM_OK;
+}
+
+// the inverse permutation (original -> permuted row) on the device: uploaded once per handle
+inline int ensure_iperm(scilmm_symbolic* sym, Dev* D) {
+  return D->d_iperm ? SCILMM_OK : upload(sym, D, sym->S->iperm, &D->d_iperm);
 }
 
 // Rank-local storage of a distributed factor (world > 1).  Tail front dense_first + jj belongs to rank jj % world.

@@ -14,7 +14,7 @@
 #include <cstdint>
 #include <string>
 
-#include "../../include/scilmm_hip.h"
+#include "dev.h"
 
 namespace {
 
@@ -55,16 +55,6 @@ __global__ __launch_bounds__(256) void k_dominance(int32_t n, const int64_t* __r
 
 thread_local std::string g_dom_err;
 
-#define DCHK(call)                                                             \
-  do {                                                                         \
-    hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      g_dom_err = std::string(#call) + ": " + hipGetErrorString(_e);           \
-      st = SCILMM_ERR_DEVICE;                                                  \
-      goto done;                                                               \
-    }                                                                          \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -101,30 +91,20 @@ int scilmm_dominance(int32_t n, const int64_t* indptr, const int32_t* indices, c
     for (int q = 0; q < 2; ++q)
       if (parents[2 * (int64_t)i + q] < -1 || parents[2 * (int64_t)i + q] >= n) { g_dom_err = "parent index out of range"; return SCILMM_ERR_ARG; }
   }
-  int st = SCILMM_OK;
+  // (the temporaries are freed on every return path)
+  scilmm::DevScratch tmp(&g_dom_err);
   int64_t* dp = nullptr;
   int32_t *di = nullptr, *dpar = nullptr;
   double *dd = nullptr, *dout = nullptr;
-  DCHK(hipMalloc((void**)&dp, sizeof(int64_t) * ((size_t)n + 1)));
-  DCHK(hipMalloc((void**)&di, sizeof(int32_t) * (size_t)std::max<int64_t>(nz, 1)));
-  DCHK(hipMalloc((void**)&dd, sizeof(double) * (size_t)std::max<int64_t>(nz, 1)));
-  DCHK(hipMalloc((void**)&dout, sizeof(double) * (size_t)std::max<int64_t>(nz, 1)));
-  DCHK(hipMalloc((void**)&dpar, sizeof(int32_t) * 2 * (size_t)n));
-  DCHK(hipMemcpy(dp, indptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice));
-  DCHK(hipMemcpy(di, indices, sizeof(int32_t) * (size_t)nz, hipMemcpyHostToDevice));
-  DCHK(hipMemcpy(dd, data, sizeof(double) * (size_t)nz, hipMemcpyHostToDevice));
-  DCHK(hipMemcpy(dpar, parents, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice));
-  st = scilmm_dominance_dev(n, dp, di, dd, dpar, dout, nullptr);
-  if (st != SCILMM_OK) goto done;
-  DCHK(hipDeviceSynchronize());
-  DCHK(hipMemcpy(out, dout, sizeof(double) * (size_t)nz, hipMemcpyDeviceToHost));
-done:
-  (void)hipFree(dp);
-  (void)hipFree(di);
-  (void)hipFree(dd);
-  (void)hipFree(dout);
-  (void)hipFree(dpar);
-  return st;
+  TRY(tmp.upload(indptr, (size_t)n + 1, &dp));
+  TRY(tmp.upload(indices, (size_t)nz, &di));
+  TRY(tmp.upload(data, (size_t)nz, &dd));
+  TRY(tmp.upload(parents, 2 * (size_t)n, &dpar));
+  TRY(tmp.alloc((size_t)nz, &dout));
+  TRY(scilmm_dominance_dev(n, dp, di, dd, dpar, dout, nullptr));
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * (size_t)nz, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? SCILMM_OK : tmp.fail("scilmm_dominance: synchronise and copy back", e);
 }
 
 }  // extern "C"

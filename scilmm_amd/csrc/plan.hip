@@ -118,16 +118,7 @@ int build_cells_device(scilmm_symbolic* sym, Dev* D, const std::vector<const std
     return SCILMM_OK;
   };
   int st;
-  std::vector<void*> tmp;  // freed on exit
-  auto tmalloc = [&](void** p, size_t bytes) -> int {
-    int r = dmalloc(p, bytes);
-    if (r == SCILMM_OK) tmp.push_back(*p);
-    return r;
-  };
-  struct Cleanup {
-    std::vector<void*>& v;
-    ~Cleanup() { for (void* p : v) (void)hipFree(p); }
-  } cleanup{tmp};
+  DevScratch tmp(&sym->err);  // freed on exit
   for (int c = 0; c < 3; ++c) {
     D->cellset[c].level_ptr.assign(S.nlevels + 1, 0);
     D->cellset[c].level_short.assign(std::max<int32_t>(NL, 1), 0);
@@ -151,8 +142,8 @@ int build_cells_device(scilmm_symbolic* sym, Dev* D, const std::vector<const std
   unsigned long long *key = nullptr, *skey = nullptr, *d_ninv = nullptr;
   uint32_t *idx = nullptr, *sidx = nullptr;
   int64_t *cst = nullptr, *csq = nullptr; int32_t *cmd = nullptr, *cwd = nullptr;
-  if ((st = tmalloc((void**)&d_cc, sizeof(CellCombo) * (size_t)ncc)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&d_off, sizeof(int64_t) * (size_t)(ncc + 1))) != SCILMM_OK) return st;
+  TRY(tmp.alloc((size_t)ncc, &d_cc));
+  TRY(tmp.alloc((size_t)(ncc + 1), &d_off));
   {
     size_t at = 0;
     for (auto* pv : ccparts) {
@@ -161,24 +152,24 @@ int build_cells_device(scilmm_symbolic* sym, Dev* D, const std::vector<const std
     }
   }
   HIPCHK(hipMemcpy(d_off, off.data(), sizeof(int64_t) * (size_t)(ncc + 1), hipMemcpyHostToDevice));
-  if ((st = tmalloc((void**)&key, 8 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&skey, 8 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&idx, 4 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&sidx, 4 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&cst, 8 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&csq, 8 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&cmd, 4 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&cwd, 4 * (size_t)total)) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&d_ninv, 8)) != SCILMM_OK) return st;
+  TRY(tmp.alloc((size_t)total, &key));
+  TRY(tmp.alloc((size_t)total, &skey));
+  TRY(tmp.alloc((size_t)total, &idx));
+  TRY(tmp.alloc((size_t)total, &sidx));
+  TRY(tmp.alloc((size_t)total, &cst));
+  TRY(tmp.alloc((size_t)total, &csq));
+  TRY(tmp.alloc((size_t)total, &cmd));
+  TRY(tmp.alloc((size_t)total, &cwd));
+  TRY(tmp.alloc(1, &d_ninv));
   HIPCHK(hipMemset(d_ninv, 0, 8));
   hipStream_t s0 = D->stream;
   hipLaunchKernelGGL(k_emit_cells, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, s0, total, ncc,
                      (const CellCombo*)d_cc, (const int64_t*)d_off, D->v.sn_rows, key, idx, cst, csq, cmd, cwd, d_ninv);
-  void* cubtmp = nullptr;
+  uint8_t* cubtmp = nullptr;
   size_t cubbytes = 0, need = 0;
   auto ensure_tmp = [&](size_t bytes) -> int {
     if (bytes <= cubbytes) return SCILMM_OK;
-    if ((st = tmalloc(&cubtmp, bytes)) != SCILMM_OK) return st;  // the smaller one is freed at exit as well
+    TRY(tmp.alloc(bytes, &cubtmp));  // the smaller one is freed at exit as well
     cubbytes = bytes;
     return SCILMM_OK;
   };
@@ -193,9 +184,9 @@ int build_cells_device(scilmm_symbolic* sym, Dev* D, const std::vector<const std
   D->n_cells = nvalid;
   // groups of equal key (= equal class, level, target address)
   unsigned long long* ukey = nullptr; int64_t* ucnt = nullptr; int64_t* ustart = nullptr; int64_t* d_ng = nullptr;
-  if ((st = tmalloc((void**)&ukey, 8 * (size_t)std::max<int64_t>(nvalid, 1))) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&ucnt, 8 * (size_t)std::max<int64_t>(nvalid, 1))) != SCILMM_OK) return st;
-  if ((st = tmalloc((void**)&d_ng, 8)) != SCILMM_OK) return st;
+  TRY(tmp.alloc((size_t)std::max<int64_t>(nvalid, 1), &ukey));
+  TRY(tmp.alloc((size_t)std::max<int64_t>(nvalid, 1), &ucnt));
+  TRY(tmp.alloc(1, &d_ng));
   HIPCHK(hipMemset(d_ng, 0, 8));
   int64_t ng = 0;
   if (nvalid > 0) {
@@ -218,7 +209,7 @@ int build_cells_device(scilmm_symbolic* sym, Dev* D, const std::vector<const std
   if ((st = dmalloc((void**)&owd, 4 * (size_t)std::max<int64_t>(nvalid, 1))) != SCILMM_OK) return st; D->allocs.push_back(owd);
   std::vector<unsigned int> counters((size_t)3 * NL * 2, 0u);
   if (ng > 0) {
-    if ((st = tmalloc((void**)&ustart, 8 * (size_t)ng)) != SCILMM_OK) return st;
+    TRY(tmp.alloc((size_t)ng, &ustart));
     need = 0;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, ucnt, ustart, (int)ng, s0));
     if ((st = ensure_tmp(need)) != SCILMM_OK) return st;
@@ -226,12 +217,12 @@ int build_cells_device(scilmm_symbolic* sym, Dev* D, const std::vector<const std
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(cubtmp, need, ucnt, ustart, (int)ng, s0));
     unsigned long long *gkey = nullptr, *gkey_s = nullptr; uint32_t *gidx = nullptr, *order = nullptr; int64_t* cnt2 = nullptr;
     unsigned int* d_counters = nullptr;
-    if ((st = tmalloc((void**)&gkey, 8 * (size_t)ng)) != SCILMM_OK) return st;
-    if ((st = tmalloc((void**)&gkey_s, 8 * (size_t)ng)) != SCILMM_OK) return st;
-    if ((st = tmalloc((void**)&gidx, 4 * (size_t)ng)) != SCILMM_OK) return st;
-    if ((st = tmalloc((void**)&order, 4 * (size_t)ng)) != SCILMM_OK) return st;
-    if ((st = tmalloc((void**)&cnt2, 8 * (size_t)ng)) != SCILMM_OK) return st;
-    if ((st = tmalloc((void**)&d_counters, 4 * counters.size())) != SCILMM_OK) return st;
+    TRY(tmp.alloc((size_t)ng, &gkey));
+    TRY(tmp.alloc((size_t)ng, &gkey_s));
+    TRY(tmp.alloc((size_t)ng, &gidx));
+    TRY(tmp.alloc((size_t)ng, &order));
+    TRY(tmp.alloc((size_t)ng, &cnt2));
+    TRY(tmp.alloc(counters.size(), &d_counters));
     HIPCHK(hipMemsetAsync(d_counters, 0, 4 * counters.size(), s0));
     const unsigned gb = (unsigned)((ng + 255) / 256);
     hipLaunchKernelGGL(k_group_keys, dim3(gb), dim3(256), 0, s0, ng, (const unsigned long long*)ukey, (const int64_t*)ucnt,

@@ -431,8 +431,8 @@ class Factor(object):
         refactorized before the next solve."""
         if getattr(self, "_pending", None) is not None:
             self.wait()
+        check(lib().scilmm_selected_inverse(self._h), self.sym._h)  # (a refusal leaves the factor, and its sigma2, as they were)
         self._s2, self._pending = None, None  # (the panels hold entries of the inverse from here on)
-        check(lib().scilmm_selected_inverse(self._h), self.sym._h)
         out = np.empty(self.sym.K)
         check(lib().scilmm_inverse_traces(self._h, ptr(out)), self.sym._h)
         return out

@@ -90,3 +90,85 @@ def test_round4_entry_points_validate_and_never_fall_back(gpu_available):
             sym3.dominance_values_from(1, 0, par)            # needs the device: no CPU form exists
         with pytest.raises(_lib.ScilmmError, match="HIP|device"):
             sym3.ibd_values_from_pedigree(0, par)
+
+
+def test_entry_points_reject_bad_arguments_before_any_device_state():
+    """Every numeric entry point with a null or out-of-range argument, on a handle that has no device state (and a factor
+    whose symbolic handle is null): the code comes from the argument checks alone, so it is the same with and without a
+    GPU, and nothing is dereferenced.  The table was written from the checks as they stood before the entry points were
+    reduced to checks + one call; `one` is a non-null dummy that a correct check order never reads."""
+    import ctypes as C
+    from scilmm_amd.factor import Symbolic
+    L = _lib.lib()
+    vp = C.c_void_p
+    ARG, OK = _lib.ERR_ARG, _lib.OK
+    n = 6
+    A = (sp.diags([np.full(n - 1, 0.25), np.full(n, 2.0), np.full(n - 1, 0.25)], [-1, 0, 1])).tocsr()
+    sym = Symbolic([A, sp.identity(n, format="csr")], upload=False)   # K = 2: matrix 1 is diagonal-only
+    h = sym._h
+    one = vp(8)
+    hollow = C.create_string_buffer(256)            # a scilmm_factor with sym == NULL
+    fac = C.cast(hollow, vp)
+    dbl, i64 = C.c_double(0.0), C.c_int64(0)
+    par = np.full((n, 2), -1, dtype=np.int32)
+    late = par.copy()
+    late[1, 0] = 3                                  # a parent that follows its child
+    table = [
+        ("values_upload", (None, 0, one), ARG), ("values_upload", (h, 0, None), ARG),
+        ("values_upload", (h, -1, one), ARG), ("values_upload", (h, 2, one), ARG),
+        ("values_download", (None, 0, one), ARG), ("values_download", (h, 0, one), ARG), ("values_download", (h, 0, None), ARG),
+        ("factorize", (None, one, C.pointer(vp()), None), ARG), ("factorize", (h, None, C.pointer(vp()), None), ARG),
+        ("factorize", (h, one, None, None), ARG),
+        ("factor_create_external", (h, None, one, one, C.pointer(vp())), ARG),
+        ("factor_create_external", (h, one, one, None, C.pointer(vp())), ARG), ("factor_create_external", (h, one, one, one, None), ARG),
+        ("refactorize", (None, one, None), ARG), ("refactorize", (fac, one, None), ARG), ("refactorize", (fac, None, None), ARG),
+        ("refactorize_async", (None, one), ARG), ("refactorize_async", (fac, one), ARG),
+        ("factor_wait", (None, None), ARG), ("factor_wait", (fac, None), ARG),
+        ("logdet", (None, C.byref(dbl)), ARG), ("logdet", (fac, C.byref(dbl)), ARG), ("logdet", (fac, None), ARG),
+        ("export_L", (None, None, None, None, C.byref(i64)), ARG), ("export_L", (fac, None, None, None, C.byref(i64)), ARG),
+        ("export_L", (fac, None, None, None, None), ARG),
+        ("selected_inverse", (None,), ARG), ("selected_inverse", (fac,), ARG),
+        ("inverse_traces", (None, one), ARG), ("inverse_traces", (fac, one), ARG), ("inverse_traces", (fac, None), ARG),
+        ("he_moments", (None, 0, 1, C.byref(dbl), C.byref(dbl)), ARG), ("he_moments", (h, 0, 1, None, C.byref(dbl)), ARG),
+        ("he_moments", (h, 0, 1, C.byref(dbl), None), ARG),
+        ("ibd_values_device", (None, 0, n, _lib.ptr(par)), ARG), ("ibd_values_device", (h, 0, n, None), ARG),
+        ("ibd_values_device", (h, -1, n, _lib.ptr(par)), ARG), ("ibd_values_device", (h, 2, n, _lib.ptr(par)), ARG),
+        ("ibd_values_device", (h, 1, n, _lib.ptr(par)), ARG),        # the diagonal-only matrix
+        ("ibd_values_device", (h, 0, n + 1, _lib.ptr(par)), ARG), ("ibd_values_device", (h, 0, n, _lib.ptr(late)), ARG),
+        ("dominance_values_device", (None, 0, 1, n, _lib.ptr(par)), ARG), ("dominance_values_device", (h, 0, 1, n, None), ARG),
+        ("dominance_values_device", (h, 0, 1, n, _lib.ptr(par)), ARG),   # the diagonal-only matrix as the source
+        ("dominance_values_device", (h, 0, 2, n, _lib.ptr(par)), ARG), ("dominance_values_device", (h, 0, 0, n, _lib.ptr(par)), ARG),
+        ("sync", (None,), ARG), ("sync", (h,), ARG), ("last_timing", (None, C.pointer(_lib.Timing())), ARG),
+        ("last_timing", (h, C.pointer(_lib.Timing())), ARG), ("last_timing", (h, None), ARG),
+        ("scan_timing", (None, C.byref(dbl)), ARG), ("scan_timing", (h, C.byref(dbl)), ARG),
+        ("dist_set_work", (None, one), ARG), ("dist_set_work", (h, None), ARG),
+        ("set_front_precision", (None, 32), ARG), ("set_front_precision", (h, 16), ARG), ("set_profiling", (None, 1), ARG),
+        ("scan_block_dev", (None, one, n, 1, one, 1, one), ARG), ("scan_block_dev", (fac, one, n, 1, one, 1, one), ARG),
+        ("scan_block_dev", (one, None, n, 1, one, 1, one), ARG), ("scan_block_dev", (one, one, n, 0, one, 1, one), ARG),
+        ("scan_block_dev", (one, one, n, 129, one, 1, one), ARG), ("scan_block_dev", (one, one, n, 1, None, 1, one), ARG),
+        ("scan_block_dev", (one, one, n, 1, one, 0, one), ARG), ("scan_block_dev", (one, one, n, 1, one, 1, None), ARG),
+        ("rel_block_dev", (None, one, one, 1, one, 1, one), ARG), ("rel_block_dev", (fac, one, one, 1, one, 1, one), ARG),
+        ("rel_block_dev", (one, None, one, 1, one, 1, one), ARG), ("rel_block_dev", (one, one, None, 1, one, 1, one), ARG),
+        ("rel_block_dev", (one, one, one, 0, one, 1, one), ARG), ("rel_block_dev", (one, one, one, 129, one, 1, one), ARG),
+        ("rel_block_dev", (one, one, one, 1, None, 1, one), ARG), ("rel_block_dev", (one, one, one, 1, one, 0, one), ARG),
+        ("rel_block_dev", (one, one, one, 1, one, 1, None), ARG),
+        ("rows_block_dev", (None, one, one, one, 1, one, 1, one), ARG), ("rows_block_dev", (fac, one, one, one, 1, one, 1, one), ARG),
+        ("rows_block_dev", (one, None, one, one, 1, one, 1, one), ARG), ("rows_block_dev", (one, one, None, one, 1, one, 1, one), ARG),
+        ("rows_block_dev", (one, one, one, None, 1, one, 1, one), ARG), ("rows_block_dev", (one, one, one, one, 0, one, 1, one), ARG),
+        ("rows_block_dev", (one, one, one, one, 129, one, 1, one), ARG), ("rows_block_dev", (one, one, one, one, 1, None, 1, one), ARG),
+        ("rows_block_dev", (one, one, one, one, 1, one, 0, one), ARG), ("rows_block_dev", (one, one, one, one, 1, one, 1, None), ARG),
+    ]
+    # the products (handle, k, block, r, out) and the sweeps (factor, block, r, out): null handle / block / out, r <= 0
+    for name in ("spmm", "spmm_dev", "quadforms", "quadforms_dev"):
+        table += [(name, (None, 0, one, 1, one), ARG), (name, (h, 0, None, 1, one), ARG), (name, (h, 0, one, 1, None), ARG),
+                  (name, (h, 0, one, 0, one), ARG), (name, (h, 0, one, -3, one), ARG)]
+    # (the half-solves and the blocks look at the factor last: `one` stands for it where another argument is bad)
+    for name in ("solve", "lmul", "solve_dev", "lmul_dev", "solve_L", "solve_Lt", "solve_L_dev", "solve_Lt_dev"):
+        f = one if "_L" in name else fac
+        table += [(name, (None, one, 1, one), ARG), (name, (fac, one, 1, one), ARG), (name, (f, None, 1, one), ARG),
+                  (name, (f, one, 1, None), ARG), (name, (f, one, 0, one), ARG)]
+    got = [(name, i, getattr(L, "scilmm_" + name)(*args)) for i, (name, args, _) in enumerate(table)]
+    assert got == [(name, i, want) for i, (name, _, want) in enumerate(table)]
+    L.scilmm_factor_free(None)                      # (a null factor: nothing to do)
+    assert OK == L.scilmm_get_deterministic(h, C.pointer(C.c_int32()))   # the handle is still usable and still has no device state
+    assert L.scilmm_sync(h) == ARG

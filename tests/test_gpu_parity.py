@@ -167,6 +167,54 @@ def test_quadforms_and_spmm():
     assert rel_err(sym.spmm(0, x), A @ x) < 1e-12
 
 
+@pytest.fixture(scope="module")
+def host_device_forms():
+    """A ~300-individual pedigree with K = 2 (one general matrix, the diagonal-only identity) on a default and on a
+    deterministic handle, and for r in (1, 17, 130) -- 130 crosses RPMAX = 128: a second block of 2 columns -- the host
+    form and the device-pointer form of spmm and quadforms for both matrices, with SciPy's answers.  Computed once."""
+    import ctypes as C
+    import torch
+    from oracle import oracle as O
+    A, _ = small_pedigree(300, 0.01, 7)
+    A = A.tocsr()
+    n = A.shape[0]
+    mats = [A, sp.identity(n, format="csr")]
+    rng = np.random.default_rng(11)
+    Xs = {r: rng.standard_normal((n, r)) for r in (1, 17, 130)}
+    vp = C.c_void_p
+    out = {}
+    for det in (False, True):
+        sym = _engine(mats, deterministic=det)
+        assert sym.deterministic == det
+        for r, X in Xs.items():
+            dX = torch.from_numpy(X).cuda()
+            for k in (0, 1):
+                dY = torch.empty_like(dX)
+                dq = torch.empty(r, dtype=torch.float64, device="cuda")
+                sym.spmm_dev(k, vp(dX.data_ptr()), r, vp(dY.data_ptr()))
+                sym.quadforms_dev(k, vp(dX.data_ptr()), r, vp(dq.data_ptr()))
+                sym.sync()
+                out[det, r, k] = {"spmm": sym.spmm(k, X), "spmm_dev": dY.cpu().numpy(), "spmm_ref": mats[k] @ X,
+                                  "quad": sym.quadforms(k, X), "quad_dev": dq.cpu().numpy(), "quad_ref": O.quadforms(mats[k], X)}
+    return out
+
+
+@pytest.mark.parametrize("r", [1, 17, 130])
+@pytest.mark.parametrize("op", ["spmm", "quad"])
+def test_host_and_device_forms_share_one_body(host_device_forms, op, r):
+    """`scilmm_spmm` / `scilmm_quadforms` stage a host block around the body their `_dev` forms run (`run_spmm`, `run_quad`):
+    both meet SciPy at 1e-12 relative (the bound `test_quadforms_and_spmm` holds) in either mode, and on a deterministic
+    handle -- the same order-fixed kernels on the same data -- the two forms give the same bits."""
+    for det in (False, True):
+        for k in (0, 1):
+            c = host_device_forms[det, r, k]
+            e_host, e_dev = rel_err(c[op], c[op + "_ref"]), rel_err(c[op + "_dev"], c[op + "_ref"])
+            print("%s det=%d r=%d k=%d: host %.2e device %.2e" % (op, det, r, k, e_host, e_dev))
+            assert e_host < 1e-12 and e_dev < 1e-12
+            if det:
+                assert np.array_equal(c[op], c[op + "_dev"])
+
+
 def test_pedigree_10k_config():
     """BASELINE config 1 shape (10k simulated pedigree, sf 0.001), V = 0.4 A + 0.6 I."""
     from oracle import oracle as O
@@ -726,6 +774,49 @@ def test_dominance_values_built_on_the_device_in_slot_order_bit_for_bit():
         ref = _engine([Aref, Dfull, I]).factorize([0.3, 0.1, 0.6])
         # (same assembled values; the 100k schedule sums its prelude -> tail contributions with atomics: rounding-level only)
         assert np.array_equal(f.P(), ref.P()) and abs(f.logdet() - ref.logdet()) <= (0.0 if n <= 2000 else 1e-12) * abs(ref.logdet())
+
+
+def test_device_built_values_keep_no_temporaries_and_one_inverse_permutation():
+    """`scilmm_ibd_values_device`, then `scilmm_dominance_values_device`, twice each on one handle at the G1 / G2 golden
+    size: the values equal the goldens bit for bit after every call, and a second call leaves the device's free memory
+    (`hipMemGetInfo`) exactly where the first left it -- the temporaries of a call are gone when it returns, and the inverse
+    permutation is uploaded once per handle (`ensure_iperm`), not per call.  No margin: these are whole allocations."""
+    import os
+    import torch
+    from scilmm_amd import ibd
+    from scilmm_amd.Matrices.Dominance import parents_of
+    gold = os.path.join(os.path.dirname(__file__), "golden")
+    g1 = np.load(os.path.join(gold, "G1_reml_2000.npz"))
+    g2 = np.load(os.path.join(gold, "G2_lmm_dominance.npz"))
+    shape = tuple(g1["A_shape"])
+    n = shape[0]
+    A1 = sp.csr_matrix((g1["A_data"], g1["A_indices"], g1["A_indptr"]), shape=shape)
+    D1 = sp.csr_matrix((g2["D_data"], g2["D_indices"], g2["D_indptr"]), shape=shape)
+    par = parents_of(sp.csr_matrix((g2["rel_data"], g2["rel_indices"], g2["rel_indptr"]), shape=shape))
+    P = ibd.ibd_pattern_from_parents(par, values=False)
+    sym = _engine([P, P, sp.identity(n, format="csr")], upload=False)
+    sym.upload_values()
+    perm, colptr, prow = sym.get("perm"), sym.get("pat_colptr"), sym.get("pat_row")
+
+    def equals_golden(k, M):
+        # (copies: eliminate_zeros compacts the index arrays it was given in place, and they serve four comparisons)
+        got = sp.csc_matrix((sym.values_slots(k), prow.copy(), colptr.copy()), shape=(n, n))
+        got.eliminate_zeros()
+        want = sp.tril(M.tocsr()[perm][:, perm]).tocsc()
+        want.eliminate_zeros()
+        want.sort_indices()
+        got.sort_indices()
+        return (np.array_equal(got.indptr, want.indptr) and np.array_equal(got.indices, want.indices)
+                and np.array_equal(got.data, want.data))
+
+    for k, M, build in ((0, A1, lambda: sym.ibd_values_from_pedigree(0, par)), (1, D1, lambda: sym.dominance_values_from(1, 0, par))):
+        free = []
+        for call in range(2):
+            build()
+            free.append(torch.cuda.mem_get_info()[0])
+            assert equals_golden(k, M), (k, call)
+        print("matrix %d: free bytes after call 1 / 2: %d / %d" % (k, free[0], free[1]))
+        assert free[0] == free[1], (k, free)
 
 
 def test_integration_stub_from_the_document_runs():

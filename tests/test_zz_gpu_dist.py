@@ -62,7 +62,6 @@ def _worker(rank, world, port, out, env):
         except ScilmmError as e:
             refused += "distributed" in str(e)
     assert refused == 2
-    eng.fac._s2 = np.array([0.45, 0.5])   # (inverse_traces forgets the sigma2 before it asks the library: nothing was consumed)
     assert rel_err(eng.solve(B), X1) < 1e-14
     eng.factorize([0.3, 0.7])  # a second factorization on the same handle (stale panels must not survive)
     info = eng.sym.info()
