@@ -217,6 +217,32 @@ int scilmm_solve_Lt(scilmm_factor* fac, const double* B, int32_t r, double* X);
 int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
                           double* d_stats);
 
+/* scilmm_scan_block_dev for markers as they lie in a PLINK 1 binary file (.bed, variant-major): the 2-bit genotypes are
+ * decoded, and gathered through a sample map, inside the two kernels that build the sweep's right-hand side; the forward
+ * sweep and the statistics are those of scilmm_scan_block_dev.
+ *   d_bed    : marker j of the block = d_bed + j * ld_bed, ceil(n_samples / 4) bytes: sample s is bits 2 (s & 3) .. 2 (s & 3) + 1
+ *              of byte s >> 2; 00 = two copies of allele A1, 01 = missing, 10 = one copy, 11 = none.  The bits past the
+ *              last sample are ignored.  ld_bed >= ceil(n_samples / 4), so a slab of the file (after its 3 magic bytes) is
+ *              taken as it is.  Any alignment, under the rule of d_geno: aligned 16-byte pieces, the buffer inside an
+ *              allocation that starts and ends on 16-byte boundaries.
+ *   n_samples: samples per row of the file (N), >= 1.
+ *   d_sample : n int32, d_sample[i] = the file's sample of individual i (the row order of the matrices).  Any value outside
+ *              0 .. n_samples - 1, every negative one included, = not genotyped: missing for every marker, and no byte is
+ *              read for it.  Two individuals may share a sample.  NULL = identity; n_samples must then equal n.  With a
+ *              map the rows are read byte by byte at row + (sample >> 2).
+ *   flags    : bit 0 set = count allele A2 (g -> 2 - g for the observed); every other bit must be 0.
+ *   r, d_Q, q, d_stats: as for scilmm_scan_block_dev; d_stats is (q + 4) x r with the same rows.
+ * The moments are integer sums through the expressions of the int8 path and W holds the same doubles, so the statistics
+ * are bit for bit those of scilmm_scan_block_dev on the unpacked, gathered markers; no atomics of any kind are added.
+ * Everything is enqueued on the handle's stream without synchronising; scilmm_scan_timing reports decode + moments +
+ * dequantise in ms[0] for these blocks.  SCILMM_ERR_ARG before anything is dereferenced: a null d_bed, d_Q or d_stats, r or q
+ * out of range, n_samples < 1, ld_bed < ceil(n_samples / 4), an unknown flag bit, a null d_sample with n_samples != n;
+ * refusals as for the half-solves (a distributed handle, fp32-product fronts, a factor consumed by the selected
+ * inverse).  No counterpart in the reference: it reads no genotype files, and its only per-variable test is
+ * compute_fixed_effects_p_value on the covariates of the fit (scilmm/Estimation/LMM.py:129-133). */
+int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                              int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats);
+
 /* HIP-event times of the last scilmm_scan_block_dev on the handle, in milliseconds, valid after the scilmm_sync that follows
  * it: ms[0] moments + dequantise (+ permute), ms[1] forward sweep, ms[2] statistics (tools/assoc_timing.py). */
 int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);

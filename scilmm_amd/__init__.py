@@ -11,5 +11,6 @@ from .SparseCholesky import (SparseCholesky, REML, HE, run_estimates, run_estima
                              compute_hess, compute_varcomp_stderr)
 from .factor import Symbolic, Factor  # noqa: F401
 from .assoc import AssociationScan  # noqa: F401
+from .bed import BedFile  # noqa: F401
 from .blup import BLUP  # noqa: F401
 from ._lib import ScilmmError, NotPositiveDefiniteError  # noqa: F401

@@ -13,6 +13,7 @@ convention here is the same F(1, n - 1).
 
     scan = AssociationScan(cholesky_func, mats, sigma2, covariates, y)
     out = scan(genotypes)          # m x n int8, marker-major; dict of length-m arrays
+    out = scan.scan_bed("cohort", sample_index=idx)   # PLINK 1 .bed / .bim / .fam, 2-bit genotypes decoded on the device
 
 There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
 """
@@ -144,8 +145,11 @@ class AssociationScan(WhitenedModel):
         marker without an observed value or without variation gets NaN in the first four."""
         g = check_genotypes(genotypes, self.n)
         self._check_factor()
-        m, c = g.shape[0], self.c
-        S = self._stats(g) if m else np.empty((self.q + 4, 0))
+        return self._finish(self._stats(g) if g.shape[0] else np.empty((self.q + 4, 0)))
+
+    def _finish(self, S):
+        """The host algebra on the (q + 4) x m statistics of either block entry point: the dict ``__call__`` returns."""
+        m, c = S.shape[1], self.c
         n_obs, mean, css, gg = S[0], S[1].copy(), S[2], S[3]
         z = la.solve_triangular(self.R, S[4:4 + c], trans='T', lower=False) if m else np.empty((c, 0))
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -156,3 +160,69 @@ class AssociationScan(WhitenedModel):
             beta, se, chi2 = b / a, 1.0 / np.sqrt(a), b * b / a
         mean[n_obs == 0] = np.nan
         return {"beta": beta, "se": se, "chi2": chi2, "p": self._f.sf(chi2), "n_obs": n_obs.astype(np.int64), "mean": mean}
+
+    def scan_bed(self, bed, sample_index=None, markers=None, count="A1", chunk_bytes=None):
+        """The scan of ``__call__`` on the markers of a PLINK 1 fileset, decoded on the device: the packed rows are uploaded
+        as they lie in the file, in chunks of whole blocks (``chunk_bytes``, default ``_CHUNK_BYTES``), and every block runs
+        through ``scilmm_scan_block_bed_dev``.  ``bed``: a ``scilmm_amd.bed.BedFile`` or a path; ``sample_index``: n integers,
+        the file's sample of every individual in the row order of ``mats``, -1 = not genotyped (``BedFile.sample_index``), or
+        None when the file holds exactly the n individuals in that order; ``markers``: None, a slice or a 1-D integer array;
+        ``count``: the counted allele, "A1" or "A2".  Returns what ``__call__`` returns for the unpacked, gathered markers
+        (``bed.read(markers, sample_index, count)``), bit for bit in deterministic mode."""
+        from .bed import BedFile, count_flag, marker_indices
+        if not isinstance(bed, BedFile):
+            bed = BedFile(bed)
+        flag = count_flag(count)
+        if sample_index is None:
+            if bed.n_samples != self.n:
+                raise ValueError("the file has %d samples, the model %d individuals: give a sample_index"
+                                 % (bed.n_samples, self.n))
+            idx = None
+        else:
+            idx = bed.check_sample_index(sample_index, self.n)
+        rows = marker_indices(markers, bed.n_markers)
+        if chunk_bytes is None:
+            chunk_bytes = _CHUNK_BYTES
+        self._check_factor()
+        return self._finish(self._stats_bed(bed, rows, idx, flag, int(chunk_bytes)) if rows.size else np.empty((self.q + 4, 0)))
+
+    def _stats_bed(self, bed, rows, idx, flag, chunk_bytes):
+        """(q + 4) x m statistics of ``scilmm_scan_block_bed_dev`` for the markers ``rows``: a chunk is copied from the mapped
+        file into a pinned buffer (the one host pass over its bytes) and from there to the device in one copy; the rows keep
+        the file's pitch.  ``bed_seconds`` = (reading the file, host-to-device copies, everything) of the last call."""
+        import time
+        torch, q, blk = self.torch, self.q, self.block
+        m, nb = rows.size, bed.row_bytes
+        out = np.empty((q + 4, m))
+        per = max(blk, min(m, max(1, chunk_bytes // nb)) // blk * blk)
+        cap = (min(per, m) * nb + 15) // 16 * 16
+        hB = torch.empty((cap,), dtype=torch.uint8).pin_memory()
+        dB = torch.empty((cap,), dtype=torch.uint8, device="cuda")
+        nblk = (min(per, m) + blk - 1) // blk
+        dS = torch.empty((nblk, (q + 4) * blk), dtype=torch.float64, device="cuda")
+        dI = None if idx is None else torch.from_numpy(idx).cuda()
+        run = rows.size > 1 and bool(np.all(np.diff(rows) == 1))    # consecutive markers: a slab of the file
+        vp = C.c_void_p
+        t_read = t_copy = 0.0
+        t0 = time.perf_counter()
+        for j0 in range(0, m, per):
+            mc = min(per, m - j0)
+            t1 = time.perf_counter()
+            stage = hB.numpy()[:mc * nb].reshape(mc, nb)
+            np.copyto(stage, bed.packed[rows[j0]:rows[j0] + mc] if run else bed.packed[rows[j0:j0 + mc]])
+            t2 = time.perf_counter()
+            dB[:mc * nb].copy_(hB[:mc * nb], non_blocking=True)
+            torch.cuda.synchronize()
+            t_read, t_copy = t_read + t2 - t1, t_copy + time.perf_counter() - t2
+            for b, k0 in enumerate(range(0, mc, blk)):
+                rb = min(blk, mc - k0)
+                self.factor.scan_block_bed_dev(vp(dB.data_ptr() + k0 * nb), nb, bed.n_samples,
+                                               None if dI is None else vp(dI.data_ptr()), flag, rb, vp(self.dQ.data_ptr()), q,
+                                               vp(dS.data_ptr() + 8 * b * (q + 4) * blk))
+            self.sym.sync()
+            hS = dS.cpu().numpy()
+            for b, k0 in enumerate(range(0, mc, blk)):
+                rb = min(blk, mc - k0)
+                out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
+        self.bed_seconds = (t_read, t_copy, time.perf_counter() - t0)
+        return out

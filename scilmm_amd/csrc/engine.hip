@@ -1,5 +1,5 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, bed.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing, BlockCall (scan and BLUP blocks);
@@ -30,6 +30,7 @@
 
 #include "kernels.hip.h"
 #include "scan.hip.h"
+#include "bed.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
@@ -237,6 +238,26 @@ int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_g
   hipLaunchKernelGGL(k_scan_dequant, dim3(tiles), dim3(256), 0, s0, n, r, b.sw->rp, d_geno, ld_geno, (const int32_t*)D->d_iperm,
                      (const double*)(d_stats + r), D->W);
   // rows 3..: |w(g)|^2 and Q^T w(g)
+  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r);
+}
+
+int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                              int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
+  if (!d_bed || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 ||
+      (flags & ~BED_A2) || (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  BlockCall b(fac);
+  TRY(b.begin(q, "scilmm_scan_block_bed_dev"));
+  TRY(b.open(r, false));
+  Dev* D = b.D;
+  const int32_t n = b.sym->S->n;
+  hipStream_t s0 = D->stream;
+  // rows 0..2 of the statistics from the packed rows: the integer sums of k_scan_moments, taken class by class
+  hipLaunchKernelGGL(k_bed_moments, dim3((unsigned)r), dim3(256), 0, s0, n, n_samples, d_bed, ld_bed, d_sample, flags, r, d_stats);
+  // W = P (g - mean) decoded tile by tile, through the sample map where there is one
+  const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
+  hipLaunchKernelGGL(k_bed_dequant, dim3(tiles), dim3(256), 0, s0, n, n_samples, r, b.sw->rp, d_bed, ld_bed, d_sample, flags,
+                     (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
   return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r);
 }
 

@@ -411,6 +411,12 @@ class Factor(object):
         """One block of the marker scan (``scilmm_scan_block_dev``; ``scilmm_amd.assoc.AssociationScan`` is the interface)."""
         check(lib().scilmm_scan_block_dev(self._h, dG_ptr, ld, r, dQ_ptr, q, dstats_ptr), self.sym._h)
 
+    def scan_block_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dQ_ptr, q, dstats_ptr):
+        """One block of the marker scan from packed PLINK rows (``scilmm_scan_block_bed_dev``; ``dsample_ptr`` None = identity
+        map; ``AssociationScan.scan_bed`` is the interface)."""
+        check(lib().scilmm_scan_block_bed_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dQ_ptr, q, dstats_ptr),
+              self.sym._h)
+
     def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
         """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host
         ``weights`` and ``ids``, device ``Q`` and statistics; ``scilmm_amd.blup.BLUP`` is the interface)."""
