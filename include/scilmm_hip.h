@@ -243,6 +243,25 @@ int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_g
 int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                               int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats);
 
+/* The two scan blocks above with one more output, for variant-SET tests (burden, SKAT / famSKAT): besides the per-marker
+ * statistics the block hands back the Gram matrix of its whitened markers,
+ *   d_gram : r x r row-major, leading dimension r: d_gram[i][j] = w(g~_i)' w(g~_j) = g~_i' V^-1 g~_j.
+ * With X the forward solution and Z = R^-T w(C)' X (R'R = w(C)'w(C); w(C)'X are rows 4 .. of d_stats), X'X - Z'Z is
+ * G~' P_V G~ (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1): the null covariance of the score vector G~' P_V y, whose entries
+ * the scan's statistics already give.  The forward solution is read a second time where it lies, on the fp64 matrix pipe
+ * (v_mfma_f64_16x16x4_f64; lower-triangle tiles in fixed row slices, folded in slice order, no floating-point atomics),
+ * so every entry's bits depend on (n, r) alone in either mode of the handle, the matrix is symmetric bit for bit, and
+ * exactly r * r doubles are written.  Its diagonal is row 3 of d_stats summed in another order (agreement to rounding, not
+ * bit for bit).  d_stats holds the bits the plain entry point writes: the launches before the Gram are the same.
+ * Everything else -- arguments, their checks, the refusals, the stream, scilmm_scan_timing (the Gram counts into ms[2]) --
+ * is as for the plain entry points; a null d_gram: SCILMM_ERR_ARG.  The slice partials (12 MB per 100k individuals) are
+ * allocated by the first such call on a handle, nothing per block afterwards.  scilmm_amd.VariantSetTest is the
+ * interface.  No counterpart in the reference. */
+int scilmm_scan_block_gram_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
+                               double* d_stats, double* d_gram);
+int scilmm_scan_block_bed_gram_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                                   int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram);
+
 /* HIP-event times of the last scilmm_scan_block_dev on the handle, in milliseconds, valid after the scilmm_sync that follows
  * it: ms[0] moments + dequantise (+ permute), ms[1] forward sweep, ms[2] statistics (tools/assoc_timing.py). */
 int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);

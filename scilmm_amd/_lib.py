@@ -75,6 +75,7 @@ SYMBOLS = [
     "scilmm_set_deterministic", "scilmm_get_deterministic",
     "scilmm_solve_L", "scilmm_solve_Lt", "scilmm_solve_L_dev", "scilmm_solve_Lt_dev", "scilmm_scan_block_dev",
     "scilmm_scan_timing", "scilmm_rel_block_dev", "scilmm_rows_block_dev", "scilmm_scan_block_bed_dev",
+    "scilmm_scan_block_gram_dev", "scilmm_scan_block_bed_gram_dev",
 ]
 
 _lib = None
@@ -167,6 +168,8 @@ def lib():
     L.scilmm_solve_Lt_dev.argtypes = [vp, vp, i32, vp]
     L.scilmm_scan_block_dev.argtypes = [vp, vp, i64, i32, vp, i32, vp]
     L.scilmm_scan_block_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, i32, vp]
+    L.scilmm_scan_block_gram_dev.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
+    L.scilmm_scan_block_bed_gram_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, i32, vp, vp]
     L.scilmm_scan_timing.argtypes = [vp, P(dbl)]
     L.scilmm_rel_block_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_rows_block_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]

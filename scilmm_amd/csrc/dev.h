@@ -275,6 +275,8 @@ struct Dev {
   // marker scan and BLUP blocks: slice partial sums of the statistics; inverse permutation (ensure_iperm: the blocks, IBD and dominance values)
   double* scan_partial = nullptr;       // [slices][q + 1][RPMAX]
   size_t scan_partial_cap = 0;          // doubles
+  double* gram_partial = nullptr;       // [slices of GRAM_SLICE rows][GRAM_TILES][256]: partial tiles of X^T X (the first Gram block allocates it)
+  size_t gram_partial_cap = 0;          // doubles
   const int32_t* d_iperm = nullptr;
   hipEvent_t scan_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin | W ready | forward sweep done | statistics done
   bool scan_pending = false;            // a scan block whose events have not been read yet (scilmm_sync)

@@ -1,5 +1,5 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, bed.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, bed.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing, BlockCall (scan and BLUP blocks);
@@ -30,6 +30,7 @@
 
 #include "kernels.hip.h"
 #include "scan.hip.h"
+#include "gram.hip.h"
 #include "bed.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
@@ -222,11 +223,12 @@ int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double*
   return rhs_entry(fac, dB, r, dX, RHS_SOLVE_LT, false, "scilmm_solve_Lt_dev");
 }
 
-int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
-                          double* d_stats) {
-  if (!d_geno || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
+// One block of int8 markers; `gram`: the entry point hands X^T X back as well (d_gram, checked here).
+static int scan_block(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q, double* d_stats,
+                      bool gram, double* d_gram, const char* who) {
+  if (!d_geno || (gram && !d_gram) || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
   BlockCall b(fac);
-  TRY(b.begin(q, "scilmm_scan_block_dev"));
+  TRY(b.begin(q, who, gram));
   TRY(b.open(r, false));
   Dev* D = b.D;
   const int32_t n = b.sym->S->n;
@@ -238,16 +240,28 @@ int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_g
   hipLaunchKernelGGL(k_scan_dequant, dim3(tiles), dim3(256), 0, s0, n, r, b.sw->rp, d_geno, ld_geno, (const int32_t*)D->d_iperm,
                      (const double*)(d_stats + r), D->W);
   // rows 3..: |w(g)|^2 and Q^T w(g)
-  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r);
+  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, gram ? d_gram : nullptr);
 }
 
-int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
-                              int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
-  if (!d_bed || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 ||
-      (flags & ~BED_A2) || (!d_sample && n_samples != fac->sym->S->n))
+int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
+                          double* d_stats) {
+  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, false, nullptr, "scilmm_scan_block_dev");
+}
+
+int scilmm_scan_block_gram_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
+                               double* d_stats, double* d_gram) {
+  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, true, d_gram, "scilmm_scan_block_gram_dev");
+}
+
+// One block of packed PLINK rows, as scan_block.
+static int scan_block_bed(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample, int32_t flags,
+                          int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
+  // (what needs no handle comes first: with it wrong, nothing of the handle is read)
+  if (!d_bed || (gram && !d_gram) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) ||
+      !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
     return SCILMM_ERR_ARG;
   BlockCall b(fac);
-  TRY(b.begin(q, "scilmm_scan_block_bed_dev"));
+  TRY(b.begin(q, who, gram));
   TRY(b.open(r, false));
   Dev* D = b.D;
   const int32_t n = b.sym->S->n;
@@ -258,7 +272,18 @@ int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t 
   const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
   hipLaunchKernelGGL(k_bed_dequant, dim3(tiles), dim3(256), 0, s0, n, n_samples, r, b.sw->rp, d_bed, ld_bed, d_sample, flags,
                      (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
-  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r);
+  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, gram ? d_gram : nullptr);
+}
+
+int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                              int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
+  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, false, nullptr, "scilmm_scan_block_bed_dev");
+}
+
+int scilmm_scan_block_bed_gram_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                                   int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
+  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, true, d_gram,
+                        "scilmm_scan_block_bed_gram_dev");
 }
 
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,

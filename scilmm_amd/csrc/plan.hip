@@ -33,6 +33,7 @@ void dev_free(void* p) {
   if (D->IO) (void)hipFree(D->IO);
   if (D->partial) (void)hipFree(D->partial);
   if (D->scan_partial) (void)hipFree(D->scan_partial);
+  if (D->gram_partial) (void)hipFree(D->gram_partial);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   if (D->d_out) (void)hipFree(D->d_out);

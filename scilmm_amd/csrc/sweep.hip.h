@@ -345,8 +345,9 @@ struct BlockCall {
   explicit BlockCall(scilmm_factor* f) : fac(f), sym(f->sym), guard(f->sym) {}
 
   // the refusals, the slice partial sums (allocated on the first call on a handle, or for a wider q; nothing is allocated
-  // per block afterwards), the events and the inverse permutation
-  int begin(int32_t q, const char* who) {
+  // per block afterwards), the events and the inverse permutation; `gram`: the partial tiles of X^T X as well (allocated on
+  // the first Gram block on a handle, for the widest block: never again)
+  int begin(int32_t q, const char* who, bool gram = false) {
     TRY(check_half(fac, who));
     TRY(begin_rhs(fac, who));
     D = (Dev*)sym->device;
@@ -354,6 +355,11 @@ struct BlockCall {
     const size_t need = (size_t)nslice * (size_t)(q + 1) * RPMAX;
     if (D->scan_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
     TRY(grow(sym, &D->scan_partial, &D->scan_partial_cap, need));
+    if (gram) {
+      const size_t gneed = (size_t)gram_slices(GRAM_SLICE_MIN) * GRAM_TILES * 256;
+      if (D->gram_partial_cap < gneed) HIPCHK(hipStreamSynchronize(D->stream));
+      TRY(grow(sym, &D->gram_partial, &D->gram_partial_cap, gneed));
+    }
     if (!D->scan_ev[0])
       for (auto& e : D->scan_ev) HIPCHK(hipEventCreate(&e));
     return ensure_iperm(sym, D);
@@ -367,9 +373,12 @@ struct BlockCall {
     return SCILMM_OK;
   }
 
+  int64_t gram_slices(int slice) const { return ((int64_t)sym->S->n + slice - 1) / slice; }
+
   // W holds the block (event 1 is recorded here): the forward sweep, then |x_c|^2 and Q^T x_c from one pass over X, in fixed
-  // row slices folded in slice order, to d_out ((q + 1) x r).
-  int finish(int32_t r, const double* d_Q, int32_t q, double* d_out) {
+  // row slices folded in slice order, to d_out ((q + 1) x r).  With d_gram (begin was told so): X^T X (r x r) from a second
+  // pass over X on the matrix pipe, inside the statistics interval; without it the launches are the same as ever.
+  int finish(int32_t r, const double* d_Q, int32_t q, double* d_out, double* d_gram = nullptr) {
     const int32_t n = sym->S->n;
     hipStream_t s0 = D->stream;
     const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
@@ -379,6 +388,13 @@ struct BlockCall {
     const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
     hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, d_Q, q, D->scan_partial);
     hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_out);
+    if (d_gram) {
+      const int32_t nt = sw->rp / 16, ntile = nt * (nt + 1) / 2;
+      const GramShape g = gram_shape();
+      const int64_t gs = gram_slices(g.slice);
+      hipLaunchKernelGGL(gram_kernel(g), dim3((unsigned)gs), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, D->gram_partial);
+      hipLaunchKernelGGL(k_gram_fold, dim3((unsigned)ntile), dim3(GRAM_FOLD * 256), 0, s0, gs, ntile, (const double*)D->gram_partial, r, d_gram);
+    }
     HIPCHK(hipEventRecord(D->scan_ev[3], s0));
     D->scan_pending = true;
     if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));

@@ -417,6 +417,16 @@ class Factor(object):
         check(lib().scilmm_scan_block_bed_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dQ_ptr, q, dstats_ptr),
               self.sym._h)
 
+    def scan_block_gram_dev(self, dG_ptr, ld, r, dQ_ptr, q, dstats_ptr, dgram_ptr):
+        """``scan_block_dev`` with the r x r Gram matrix of the whitened markers as a second output
+        (``scilmm_scan_block_gram_dev``; ``scilmm_amd.sets.VariantSetTest`` is the interface)."""
+        check(lib().scilmm_scan_block_gram_dev(self._h, dG_ptr, ld, r, dQ_ptr, q, dstats_ptr, dgram_ptr), self.sym._h)
+
+    def scan_block_bed_gram_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dQ_ptr, q, dstats_ptr, dgram_ptr):
+        """``scan_block_bed_dev`` with the Gram matrix as a second output (``scilmm_scan_block_bed_gram_dev``)."""
+        check(lib().scilmm_scan_block_bed_gram_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dQ_ptr, q, dstats_ptr,
+                                                   dgram_ptr), self.sym._h)
+
     def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
         """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host
         ``weights`` and ``ids``, device ``Q`` and statistics; ``scilmm_amd.blup.BLUP`` is the interface)."""

@@ -1,0 +1,98 @@
+"""HIP-event times of one 128-wide variant-set block (scilmm_scan_block_gram_dev: moments + dequantise | forward sweep |
+statistics + Gram) against the plain marker-scan block of the same markers (scilmm_scan_block_dev) in the same run, at a seeded
+bench cohort: three warm-up rounds of every shape, then alternating rounds; medians and IQRs.  The Gram kernel and its fold
+run inside the statistics interval, so their time is the paired difference of that interval between the two blocks.
+  usage: sets_timing.py 100k|300k [--blocks 20] [--out FILE] [--shapes 256:1,512:1,1024:1,2048:1,512:0]
+--shapes times other slicings of k_scan_gram (<rows per slice>:<1 = LDS image, 0 = fragments from global memory>) side by
+side in the same run; it needs a library built with `make DIAG=1` (SCILMM_HIP_LIB), which reads SCILMM_GRAM_SHAPE per call.
+Reported per shape: Gram + fold time, its ratio to k_scan_stats + k_scan_fold on the same X, the bandwidth n * rp * 8 bytes /
+time implies (against the 6.3 TB/s a streaming read achieves on this part), the block's total as a fraction of the plain
+block's, and the agreement of X'X with the gg row and between shapes."""
+import argparse, ctypes, json, os, sys
+import numpy as np
+import scipy.sparse as sp
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench
+ap = argparse.ArgumentParser()
+ap.add_argument("workload"); ap.add_argument("--blocks", type=int, default=20); ap.add_argument("--out", default=None)
+ap.add_argument("--shapes", default=None)
+args = ap.parse_args()
+import torch
+from scilmm_amd import SparseCholesky, VariantSetTest
+vp = ctypes.c_void_p
+R, S2, HBM = 128, [0.5, 0.5], 6.3e12
+A, Cv, y = bench.build_problem(args.workload, 0)
+n = A.shape[0]
+tester = VariantSetTest(SparseCholesky(), [A, sp.identity(n, format="csr")], S2, Cv, y, block=R)
+sym, fac, q = tester.sym, tester.factor, tester.q
+rng = np.random.default_rng(0)
+G = rng.binomial(2, rng.uniform(0.005, 0.05, R)[:, None], size=(R, n)).astype(np.int8)       # rare variants, 2 % missing
+G[rng.random(G.shape) < 0.02] = -1
+ld = (n + 15) // 16 * 16
+dG = torch.zeros((R, ld), dtype=torch.int8, device="cuda"); dG[:, :n].copy_(torch.from_numpy(G))
+dS = torch.zeros(((q + 4) * R,), dtype=torch.float64, device="cuda")
+dK = torch.zeros((R * R,), dtype=torch.float64, device="cuda")
+torch.cuda.synchronize()
+shapes = ["default"] + ([s for s in args.shapes.split(",") if s] if args.shapes else [])
+
+
+def scan():
+    fac.scan_block_dev(vp(dG.data_ptr()), ld, R, vp(tester.dQ.data_ptr()), q, vp(dS.data_ptr())); sym.sync()
+    return sym.scan_timing()
+
+
+def gram(shape):
+    if shape == "default":
+        os.environ.pop("SCILMM_GRAM_SHAPE", None)
+    else:
+        os.environ["SCILMM_GRAM_SHAPE"] = shape
+    fac.scan_block_gram_dev(vp(dG.data_ptr()), ld, R, vp(tester.dQ.data_ptr()), q, vp(dS.data_ptr()), vp(dK.data_ptr())); sym.sync()
+    return sym.scan_timing()
+
+
+def summary(v):
+    v = np.asarray(v, dtype=float)
+    return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()),
+            "iqr": float(np.percentile(v, 75) - np.percentile(v, 25))}
+
+
+t_scan, t_gram = [], {s: [] for s in shapes}
+for it in range(3 + args.blocks):                     # three rounds of warm-up of every shape, then the timed rounds
+    ms = scan()
+    if it >= 3: t_scan.append(ms)
+    for s in shapes:
+        ms = gram(s)
+        if it >= 3: t_gram[s].append(ms)
+a = np.asarray(t_scan)
+rec = {"workload": args.workload, "n": int(n), "nnzL": int(sym.info().nnzL), "blocks": args.blocks, "sigma2": S2, "r": R,
+       "library": os.path.basename(os.environ.get("SCILMM_HIP_LIB", "libscilmm_hip.so")),
+       "timer": "HIP events on the engine's stream, one block per synchronise; three warm-up rounds of every shape, then "
+                "alternating rounds",
+       "x_bytes": int(n) * R * 8, "hbm_streaming_read_bytes_per_s": HBM,
+       "scan_block": {"prep_ms": summary(a[:, 0]), "sweep_ms": summary(a[:, 1]), "stats_ms": summary(a[:, 2]),
+                      "total_ms": summary(a.sum(axis=1))},
+       "gram_block": {}}
+K = {}
+for s in shapes:
+    b = np.asarray(t_gram[s])
+    extra = b[:, 2] - a[:, 2]                          # paired: the round's Gram block against the round's plain block
+    g = float(np.median(extra))
+    tot_s, tot_g = summary(a.sum(axis=1)), summary(b.sum(axis=1))
+    over = tot_g["median"] - tot_s["median"]
+    rec["gram_block"][s] = {
+        "prep_ms": summary(b[:, 0]), "sweep_ms": summary(b[:, 1]), "stats_ms": summary(b[:, 2]), "total_ms": tot_g,
+        "gram_plus_fold_ms": summary(extra), "ratio_to_scan_stats": g / float(np.median(a[:, 2])),
+        "implied_bytes_per_s": int(n) * R * 8 / (g * 1e-3), "fraction_of_hbm_streaming_read": int(n) * R * 8 / (g * 1e-3) / HBM,
+        "total_over_scan_block": tot_g["median"] / tot_s["median"],
+        "excess_within_iqr_plus_gram": bool(over <= max(tot_s["iqr"], tot_g["iqr"]) + g)}
+    gram(s)
+    K[s] = dK.cpu().numpy().reshape(R, R).copy()
+    gg = dS.cpu().numpy().reshape(q + 4, R)[3]
+    rec["gram_block"][s]["diag_rel_err_vs_gg"] = float(np.abs(np.diag(K[s]) - gg).max() / np.abs(gg).max())
+    rec["gram_block"][s]["symmetric_bits"] = bool(np.array_equal(K[s], K[s].T))
+    rec["gram_block"][s]["max_rel_diff_vs_default"] = float(np.abs(K[s] - K["default"]).max() / np.abs(K["default"]).max())
+os.environ.pop("SCILMM_GRAM_SHAPE", None)
+print(json.dumps(rec))
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(rec, open(args.out, "w"), indent=1)
