@@ -262,6 +262,40 @@ int scilmm_scan_block_gram_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t
 int scilmm_scan_block_bed_gram_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                                    int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram);
 
+/* The two scan blocks for IMPUTED DOSAGES: expected allele counts in [0, 2] (BGEN / pgen / VCF DS readers) instead of hard
+ * calls, in one of two element types, with the sample map of scilmm_scan_block_bed_dev.  Only the two kernels that build
+ * the sweep's right-hand side know the element type; the forward sweep, the statistics and the Gram matrix are those of
+ * the int8 entry points.
+ *   d_dos    : marker j of the block = d_dos + j * ld ELEMENTS, n_samples elements; aligned to the element size, otherwise
+ *              any alignment under the rule of d_geno (aligned 16-byte pieces, the buffer inside an allocation that starts
+ *              and ends on 16-byte boundaries).
+ *   dtype    : SCILMM_DOSAGE_U16 -- uint16, PLINK 2's fixed point: 16384 = 1.0, 32768 = 2.0, any code above 32768 = missing
+ *              (65535 is the canonical code).  The moments are 64-bit integer sums of the codes, scaled by powers of two
+ *              and put through the expressions of the int8 path (mean = sum / cnt, css = sq - sum * mean), so a marker of
+ *              hard calls coded g * 16384 gives the statistics of scilmm_scan_block_dev bit for bit, and a constant marker
+ *              has a centred sum of squares of exactly 0.
+ *              SCILMM_DOSAGE_F32 -- float: a non-finite value = missing, any finite value is taken at face value (the path
+ *              also serves an arbitrary quantitative candidate covariate).  fp64 sums in a fixed order (one workgroup per
+ *              marker, a fixed thread stride and a fixed tree; no atomics): a call repeats its bits.  The centred sum of
+ *              squares is a second pass, sum of (g - mean)^2, and exactly 0 when the smallest observed value equals the
+ *              largest.  The order of the sums depends on n_samples and on the row's offset inside its 16-byte piece (with
+ *              a map: on n alone), so rows that start on 16-byte boundaries give the same bits wherever they lie.
+ *   ld       : elements between rows, >= n_samples.
+ *   n_samples, d_sample: as for scilmm_scan_block_bed_dev (a sample outside 0 .. n_samples - 1 = not genotyped, nothing is
+ *              read for it; NULL = identity, n_samples must equal n).  With a map the rows are read element by element.
+ *   r, d_Q, q, d_stats, d_gram: as for scilmm_scan_block_dev / scilmm_scan_block_gram_dev.
+ * Everything is enqueued on the handle's stream without synchronising; scilmm_scan_timing reports moments + dequantise in
+ * ms[0].  SCILMM_ERR_ARG before anything of the handle is read: a null d_dos (d_gram in the Gram form), d_Q or d_stats, an
+ * unknown dtype, d_dos not aligned to its element size, n_samples < 1, ld < n_samples, r or q out of range, a null d_sample
+ * with n_samples != n; refusals as for the half-solves.  scilmm_amd.AssociationScan.scan_dosages and
+ * VariantSetTest.test_dosages are the interfaces.  No counterpart in the reference. */
+enum { SCILMM_DOSAGE_U16 = 0, SCILMM_DOSAGE_F32 = 1 };
+int scilmm_scan_block_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                 const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats);
+int scilmm_scan_block_dosage_gram_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                      const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats,
+                                      double* d_gram);
+
 /* HIP-event times of the last scilmm_scan_block_dev on the handle, in milliseconds, valid after the scilmm_sync that follows
  * it: ms[0] moments + dequantise (+ permute), ms[1] forward sweep, ms[2] statistics (tools/assoc_timing.py). */
 int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);

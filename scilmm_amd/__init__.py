@@ -13,5 +13,6 @@ from .factor import Symbolic, Factor  # noqa: F401
 from .assoc import AssociationScan  # noqa: F401
 from .bed import BedFile  # noqa: F401
 from .blup import BLUP  # noqa: F401
+from . import dosage  # noqa: F401
 from .sets import VariantSetTest  # noqa: F401
 from ._lib import ScilmmError, NotPositiveDefiniteError  # noqa: F401

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCILMM_HIP_LIB", os.path.join(_HERE, "csrc", "libscilmm_hip.so"))
 
 OK, ERR_ARG, ERR_NOT_PD, ERR_DEVICE, ERR_STATE = 0, -1, -2, -3, -4
+DOSAGE_U16, DOSAGE_F32 = 0, 1      # element types of scilmm_scan_block_dosage_dev
 
 
 class ScilmmError(RuntimeError):
@@ -76,6 +77,7 @@ SYMBOLS = [
     "scilmm_solve_L", "scilmm_solve_Lt", "scilmm_solve_L_dev", "scilmm_solve_Lt_dev", "scilmm_scan_block_dev",
     "scilmm_scan_timing", "scilmm_rel_block_dev", "scilmm_rows_block_dev", "scilmm_scan_block_bed_dev",
     "scilmm_scan_block_gram_dev", "scilmm_scan_block_bed_gram_dev",
+    "scilmm_scan_block_dosage_dev", "scilmm_scan_block_dosage_gram_dev",
 ]
 
 _lib = None
@@ -170,6 +172,8 @@ def lib():
     L.scilmm_scan_block_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, i32, vp]
     L.scilmm_scan_block_gram_dev.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
     L.scilmm_scan_block_bed_gram_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, i32, vp, vp]
+    L.scilmm_scan_block_dosage_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, i32, vp]
+    L.scilmm_scan_block_dosage_gram_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, i32, vp, vp]
     L.scilmm_scan_timing.argtypes = [vp, P(dbl)]
     L.scilmm_rel_block_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_rows_block_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]

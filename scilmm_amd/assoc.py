@@ -14,6 +14,7 @@ convention here is the same F(1, n - 1).
     scan = AssociationScan(cholesky_func, mats, sigma2, covariates, y)
     out = scan(genotypes)          # m x n int8, marker-major; dict of length-m arrays
     out = scan.scan_bed("cohort", sample_index=idx)   # PLINK 1 .bed / .bim / .fam, 2-bit genotypes decoded on the device
+    out = scan.scan_dosages(ds, sample_index=idx)     # imputed dosages: m x N uint16 codes or float32 (scilmm_amd.dosage)
 
 There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
 """
@@ -225,4 +226,79 @@ class AssociationScan(WhitenedModel):
                 rb = min(blk, mc - k0)
                 out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
         self.bed_seconds = (t_read, t_copy, time.perf_counter() - t0)
+        return out
+
+    def _dosage_input(self, dosages, sample_index):
+        """The checks ``scan_dosages`` and ``VariantSetTest.test_dosages`` share, before any launch: (array, element type of
+        the C entry point, sample map or None)."""
+        from .bed import check_sample_index
+        from .dosage import check_dosages
+        d = check_dosages(dosages, self.n if sample_index is None else None)
+        idx = None
+        if sample_index is not None:
+            if d.shape[1] < 1:
+                raise ValueError("dosages without samples")
+            idx = check_sample_index(sample_index, d.shape[1], self.n, source="dosage matrix")
+        return d, (_lib.DOSAGE_U16 if d.dtype == np.uint16 else _lib.DOSAGE_F32), idx
+
+    def _dosage_stage(self, d, rows_max):
+        """Buffers for up to ``rows_max`` dosage rows at a time and the function that brings rows to the device: host array ->
+        pinned buffer (the one host pass over the bytes) -> device rows that start on 16-byte boundaries, so every read is an
+        aligned one and the order of a float marker's sums does not depend on where its row lies.  Returns (device pointer,
+        pitch in elements, load(rows of d))."""
+        torch = self.torch
+        es, N = d.dtype.itemsize, d.shape[1]
+        nb = N * es
+        ldb = (nb + 15) // 16 * 16
+        hB = torch.empty((rows_max, nb), dtype=torch.uint8).pin_memory()
+        dB = torch.empty((rows_max, ldb), dtype=torch.uint8, device="cuda")
+
+        def load(rows):
+            k = rows.shape[0]
+            np.copyto(hB.numpy()[:k], rows.view(np.uint8).reshape(k, nb))
+            dB[:k, :nb].copy_(hB[:k], non_blocking=True)
+            torch.cuda.synchronize()
+        return dB.data_ptr(), ldb // es, load
+
+    def scan_dosages(self, dosages, sample_index=None, chunk_bytes=None):
+        """The scan of ``__call__`` on imputed dosages: ``dosages`` is m x N, marker-major, C-contiguous (``np.memmap``
+        included), uint16 codes (16384 = one allele, above 32768 = missing: ``scilmm_amd.dosage.encode``) or float32 values
+        (non-finite = missing; any finite value is taken as it is, so a quantitative candidate covariate goes the same way).
+        ``sample_index``: n integers, the column of every individual in the row order of ``mats``, -1 = not genotyped, or None
+        when the columns are exactly the n individuals in that order.  Chunks of whole blocks (``chunk_bytes``, default
+        ``_CHUNK_BYTES``) go through a pinned buffer to the device and every block through ``scilmm_scan_block_dosage_dev``.
+        Returns the dict of ``__call__``; for uint16 codes of hard calls, bit for bit what ``__call__`` returns for the int8
+        markers in deterministic mode."""
+        d, dtype, idx = self._dosage_input(dosages, sample_index)
+        if chunk_bytes is None:
+            chunk_bytes = _CHUNK_BYTES
+        if int(chunk_bytes) < 1:
+            raise ValueError("chunk_bytes must be positive")
+        self._check_factor()
+        return self._finish(self._stats_dosage(d, dtype, idx, int(chunk_bytes)) if d.shape[0] else np.empty((self.q + 4, 0)))
+
+    def _stats_dosage(self, d, dtype, idx, chunk_bytes):
+        """(q + 4) x m statistics of ``scilmm_scan_block_dosage_dev`` for every row of ``d``, in chunks of whole blocks."""
+        torch, q, blk = self.torch, self.q, self.block
+        m, N = d.shape
+        out = np.empty((q + 4, m))
+        per = max(blk, min(m, max(1, chunk_bytes // (N * d.dtype.itemsize))) // blk * blk)
+        base, ld, load = self._dosage_stage(d, min(per, m))
+        nblk = (min(per, m) + blk - 1) // blk
+        dS = torch.empty((nblk, (q + 4) * blk), dtype=torch.float64, device="cuda")
+        dI = None if idx is None else torch.from_numpy(idx).cuda()
+        vp = C.c_void_p
+        for j0 in range(0, m, per):
+            mc = min(per, m - j0)
+            load(d[j0:j0 + mc])
+            for b, k0 in enumerate(range(0, mc, blk)):
+                rb = min(blk, mc - k0)
+                self.factor.scan_block_dosage_dev(vp(base + k0 * ld * d.dtype.itemsize), dtype, ld, N,
+                                                  None if dI is None else vp(dI.data_ptr()), rb, vp(self.dQ.data_ptr()), q,
+                                                  vp(dS.data_ptr() + 8 * b * (q + 4) * blk))
+            self.sym.sync()
+            hS = dS.cpu().numpy()
+            for b, k0 in enumerate(range(0, mc, blk)):
+                rb = min(blk, mc - k0)
+                out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
         return out

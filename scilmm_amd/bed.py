@@ -42,6 +42,20 @@ def marker_indices(markers, m):
     return np.where(idx < 0, idx + m, idx)
 
 
+def check_sample_index(sample_index, n_samples, n=None, source="file"):
+    """``sample_index`` as a contiguous int32 array: 1-D (of length ``n`` where given), values in ``-1 .. n_samples - 1``;
+    ``source`` names what holds the samples in the message."""
+    idx = np.asarray(sample_index)
+    if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+        raise ValueError("sample_index must be a 1-D integer array")
+    if n is not None and idx.size != n:
+        raise ValueError("sample_index has %d entries, the model has %d individuals" % (idx.size, n))
+    if idx.size and (idx.min() < -1 or idx.max() >= n_samples):
+        raise ValueError("sample_index holds a value outside -1 .. %d (the %s has %d samples)"
+                         % (n_samples - 1, source, n_samples))
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
 def _table(path, what):
     """The six whitespace-separated columns of a ``.fam`` or ``.bim`` file, as lists of strings."""
     cols = [[] for _ in range(6)]
@@ -108,15 +122,7 @@ class BedFile(object):
 
     def check_sample_index(self, sample_index, n=None):
         """``sample_index`` as a contiguous int32 array: 1-D (of length ``n`` where given), values in ``-1 .. N-1``."""
-        idx = np.asarray(sample_index)
-        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
-            raise ValueError("sample_index must be a 1-D integer array")
-        if n is not None and idx.size != n:
-            raise ValueError("sample_index has %d entries, the model has %d individuals" % (idx.size, n))
-        if idx.size and (idx.min() < -1 or idx.max() >= self.n_samples):
-            raise ValueError("sample_index holds a value outside -1 .. %d (the file has %d samples)"
-                             % (self.n_samples - 1, self.n_samples))
-        return np.ascontiguousarray(idx, dtype=np.int32)
+        return check_sample_index(sample_index, self.n_samples, n)
 
     def read(self, markers=None, sample_index=None, count="A1"):
         """The host unpack: allele counts as an int8 ``len(markers) x N`` array (``x len(sample_index)`` with a map), -1 =

@@ -1,5 +1,5 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, bed.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, bed.hip.h, dosage.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing, BlockCall (scan and BLUP blocks);
@@ -32,6 +32,7 @@
 #include "scan.hip.h"
 #include "gram.hip.h"
 #include "bed.hip.h"
+#include "dosage.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
@@ -60,6 +61,21 @@ struct scilmm_factor {
 #include "products.hip.h"
 #include "values.hip.h"
 #include "sinv.hip.h"
+
+// The two kernels of a dosage block (scan_block_dosage below) for its element type: moments, then W.
+template <class T>
+static void launch_dosage(const BlockCall& b, const void* d_dos, int64_t ld, int32_t n_samples, const int32_t* d_sample, int32_t r,
+                          double* d_stats) {
+  Dev* D = b.D;
+  const int32_t n = b.sym->S->n;
+  hipStream_t s0 = D->stream;
+  // rows 0..2 of the statistics: integer sums (uint16) or fixed-order fp64 sums in two passes (float)
+  hipLaunchKernelGGL(k_dos_moments<T>, dim3((unsigned)r), dim3(256), 0, s0, n, n_samples, (const T*)d_dos, ld, d_sample, r, d_stats);
+  // W = P (g - mean) tile by tile, through the sample map where there is one
+  const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
+  hipLaunchKernelGGL(k_dos_dequant<T>, dim3(tiles), dim3(256), 0, s0, n, n_samples, r, b.sw->rp, (const T*)d_dos, ld, d_sample,
+                     (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
+}
 
 extern "C" {
 
@@ -284,6 +300,36 @@ int scilmm_scan_block_bed_gram_dev(scilmm_factor* fac, const uint8_t* d_bed, int
                                    int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
   return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, true, d_gram,
                         "scilmm_scan_block_bed_gram_dev");
+}
+
+// One block of dosage rows (uint16 fixed point or float), as scan_block_bed; the two kernels: launch_dosage above.
+static int scan_block_dosage(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples, const int32_t* d_sample,
+                             int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
+  // (what needs no handle comes first: with it wrong, nothing of the handle is read)
+  if (!d_dos || (gram && !d_gram) || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32)) return SCILMM_ERR_ARG;
+  const uintptr_t esize = dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float);
+  if ((uintptr_t)d_dos % esize || n_samples < 1 || ld < n_samples || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) ||
+      (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  BlockCall b(fac);
+  TRY(b.begin(q, who, gram));
+  TRY(b.open(r, false));
+  if (dtype == SCILMM_DOSAGE_U16)
+    launch_dosage<uint16_t>(b, d_dos, ld, n_samples, d_sample, r, d_stats);
+  else
+    launch_dosage<float>(b, d_dos, ld, n_samples, d_sample, r, d_stats);
+  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, gram ? d_gram : nullptr);
+}
+
+int scilmm_scan_block_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                 const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
+  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, "scilmm_scan_block_dosage_dev");
+}
+
+int scilmm_scan_block_dosage_gram_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                      const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
+  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, true, d_gram,
+                           "scilmm_scan_block_dosage_gram_dev");
 }
 
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,

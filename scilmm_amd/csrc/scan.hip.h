@@ -5,6 +5,9 @@
 //   k_scan_dequant : W = P (g - mean), missing = 0, columns padded to rp      reads  r * n bytes, writes n * rp * 8
 //   k_scan_stats   : slice partial sums of |x_c|^2 and Q^T x_c from X         reads  n * (rp + q) * 8
 //   k_scan_fold    : ... folded in slice order                                reads  slices * (q + 1) * RPMAX * 8
+// The first two have two siblings per input form, which write the same rows of the statistics and the same W:
+//   k_bed_moments / k_bed_dequant (bed.hip.h)           PLINK 1 2-bit rows       reads  r * ceil(N/4) bytes each
+//   k_dos_moments<T> / k_dos_dequant<T> (dosage.hip.h)  uint16 / float dosages   reads  r * N * sizeof(T) each (float moments twice)
 // No floating-point atomics: a marker's statistics are the same bits in every run and in either mode of the handle.
 //
 // Genotype layout: marker j = geno + j * ld, n int8 values in the ORIGINAL order of the individuals, negative = missing.

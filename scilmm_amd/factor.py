@@ -427,6 +427,18 @@ class Factor(object):
         check(lib().scilmm_scan_block_bed_gram_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dQ_ptr, q, dstats_ptr,
                                                    dgram_ptr), self.sym._h)
 
+    def scan_block_dosage_dev(self, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dQ_ptr, q, dstats_ptr):
+        """One block of the marker scan from dosage rows (``scilmm_scan_block_dosage_dev``; ``dtype``: ``_lib.DOSAGE_U16`` or
+        ``_lib.DOSAGE_F32``, ``ld`` in elements, ``dsample_ptr`` None = identity map; ``AssociationScan.scan_dosages`` is the
+        interface)."""
+        check(lib().scilmm_scan_block_dosage_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dQ_ptr, q, dstats_ptr),
+              self.sym._h)
+
+    def scan_block_dosage_gram_dev(self, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dQ_ptr, q, dstats_ptr, dgram_ptr):
+        """``scan_block_dosage_dev`` with the Gram matrix as a second output (``scilmm_scan_block_dosage_gram_dev``)."""
+        check(lib().scilmm_scan_block_dosage_gram_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dQ_ptr, q,
+                                                      dstats_ptr, dgram_ptr), self.sym._h)
+
     def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
         """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host
         ``weights`` and ``ids``, device ``Q`` and statistics; ``scilmm_amd.blup.BLUP`` is the interface)."""

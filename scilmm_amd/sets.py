@@ -14,6 +14,7 @@ after that is host algebra on at most 128 x 128 matrices.
     tester = VariantSetTest(cholesky_func, mats, sigma2, covariates, y)
     out = tester(genotypes, sets)                      # sets: a sequence of 1-D integer arrays of marker rows
     out = tester.test_bed("cohort", sets, sample_index=idx)
+    out = tester.test_dosages(ds, sets, sample_index=idx)     # imputed dosages, uint16 codes or float32
 
 Burden: ``beta = w's / w'Kw``, ``se = (w'Kw)^-1/2``, ``chi2 = (w's)^2 / w'Kw``, p from F(1, n - 1) as the scan's.  SKAT:
 ``Q = sum_j w_j^2 s_j^2``, null distribution ``sum_i lam_i chi2_1`` with ``lam`` the eigenvalues of ``diag(w) K diag(w)``
@@ -217,6 +218,16 @@ class VariantSetTest(AssociationScan):
         self._check_factor()
         return self._run(sets, weights, sf, return_kernel, self._bed_block(bed, idx, flag) if sets else None)
 
+    def test_dosages(self, dosages, sets, sample_index=None, weights="beta", method="saddlepoint", return_kernel=False):
+        """``__call__`` on imputed dosages (``scilmm_scan_block_dosage_gram_dev``): ``sets`` index the rows of ``dosages``;
+        ``dosages`` and ``sample_index`` as for ``AssociationScan.scan_dosages``.  The "beta" weights take half the mean
+        dosage for the allele frequency.  For uint16 codes of hard calls it returns the bits of ``__call__`` on the int8
+        markers in deterministic mode."""
+        d, dtype, idx = self._dosage_input(dosages, sample_index)
+        sets, weights, sf = self._check(sets, d.shape[0], weights, method)
+        self._check_factor()
+        return self._run(sets, weights, sf, return_kernel, self._dosage_block(d, dtype, idx) if sets else None)
+
     def _check(self, sets, m, weights, method):
         sets = check_sets(sets, m, self.block)
         return sets, check_weights(weights, sets), check_method(method)
@@ -263,6 +274,21 @@ class VariantSetTest(AssociationScan):
             torch.cuda.synchronize()
             self.factor.scan_block_bed_gram_dev(vp(dB.data_ptr()), nb, bed.n_samples, None if dI is None else vp(dI.data_ptr()),
                                                 flag, rows.size, vp(self.dQ.data_ptr()), q, pS, pK)
+            return fetch(rows.size)
+        return run
+
+    def _dosage_block(self, d, dtype, idx):
+        """The same from dosage rows: host array -> pinned buffer -> device (``AssociationScan._dosage_stage``)."""
+        q, N = self.q, d.shape[1]
+        base, ld, load = self._dosage_stage(d, self.block)
+        dI = None if idx is None else self.torch.from_numpy(idx).cuda()
+        pS, pK, fetch = self._buffers()
+        vp = C.c_void_p
+
+        def run(rows):
+            load(d[rows])
+            self.factor.scan_block_dosage_gram_dev(vp(base), dtype, ld, N, None if dI is None else vp(dI.data_ptr()), rows.size,
+                                                   vp(self.dQ.data_ptr()), q, pS, pK)
             return fetch(rows.size)
         return run
 
