@@ -19,12 +19,14 @@ convention here is the same F(1, n - 1).
 There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
 """
 import ctypes as C
+import time
 
 import numpy as np
 import scipy.linalg as la
 import scipy.stats as stats
 
 from . import _lib
+from .markers import BedRows, DosageRows, Int8Rows, as_run
 
 RPMAX = 128   # markers per device block at most (csrc/plan_types.h)
 QMAX = 32     # columns of [w(C) | w(y)] at most (csrc/scan.hip.h)
@@ -101,6 +103,22 @@ class WhitenedModel(object):
             raise _lib.ScilmmError("the resident factor no longer holds the sigma2 this object was whitened with: build a new "
                                    "%s" % type(self).__name__)
 
+    def _stats_buffer(self, nrows, m):
+        """Device buffer for the ``nrows`` statistics of ``m`` columns: a row of ``nrows * block`` numbers per block."""
+        return self.torch.empty(((m + self.block - 1) // self.block, nrows * self.block), dtype=self.torch.float64, device="cuda")
+
+    def _run_blocks(self, dS, out, enqueue):
+        """Fills ``out`` (nrows x m, m columns staged on the device) through ``dS``: ``enqueue(k0, rb, stats_ptr)`` queues the
+        block of columns k0 .. k0 + rb - 1; every block is queued, then one wait and one device-to-host copy."""
+        (nrows, m), blk = out.shape, self.block
+        for b, k0 in enumerate(range(0, m, blk)):
+            enqueue(k0, min(blk, m - k0), C.c_void_p(dS.data_ptr() + 8 * b * nrows * blk))
+        self.sym.sync()
+        hS = dS.cpu().numpy()
+        for b, k0 in enumerate(range(0, m, blk)):
+            rb = min(blk, m - k0)
+            out[:, k0:k0 + rb] = hS[b, :nrows * rb].reshape(nrows, rb)
+
 
 class AssociationScan(WhitenedModel):
     """Tests many candidate fixed effects next to ``covariates`` under V = sum_k sigma2[k] mats[k].
@@ -114,30 +132,23 @@ class AssociationScan(WhitenedModel):
         super(AssociationScan, self).__init__(cholesky_func, mats, sigma2, covariates, y, block)
         self._f = stats.f(1, self.n - 1)
 
-    def _stats(self, genotypes):
-        """(q + 4) x m statistics of ``scilmm_scan_block_dev`` for every marker, in chunks of whole blocks."""
-        torch, n, q, blk = self.torch, self.n, self.q, self.block
-        m = genotypes.shape[0]
+    def _stats(self, src, rows, chunk_bytes):
+        """(q + 4) x m statistics of the markers ``rows`` (a slice or an index array) of the marker source ``src``
+        (``scilmm_amd.markers``), in chunks of whole blocks of at most ``chunk_bytes`` host bytes: a chunk is brought to the
+        device, its blocks are queued, one wait.  The buffers are allocated once, for the largest chunk."""
+        q, blk = self.q, self.block
+        run = isinstance(rows, slice)
+        m = rows.stop - rows.start if run else rows.size
         out = np.empty((q + 4, m))
-        ld = (n + 15) // 16 * 16      # rows of the device copy start on 16-byte boundaries: every read is an aligned one
-        per = max(blk, min(m, max(1, _CHUNK_BYTES // ld)) // blk * blk)
-        dG = torch.empty((min(per, m), ld), dtype=torch.int8, device="cuda")
-        nblk = (min(per, m) + blk - 1) // blk
-        dS = torch.empty((nblk, (q + 4) * blk), dtype=torch.float64, device="cuda")
-        vp = C.c_void_p
+        if m == 0:
+            return out
+        per = max(blk, min(m, max(1, chunk_bytes // src.row_bytes)) // blk * blk)
+        dS = self._stats_buffer(q + 4, min(per, m))
+        src.stage(min(per, m))
         for j0 in range(0, m, per):
             mc = min(per, m - j0)
-            dG[:mc, :n].copy_(torch.from_numpy(np.ascontiguousarray(genotypes[j0:j0 + mc])))
-            torch.cuda.synchronize()
-            for b, k0 in enumerate(range(0, mc, blk)):
-                rb = min(blk, mc - k0)
-                self.factor.scan_block_dev(vp(dG.data_ptr() + k0 * ld), ld, rb, vp(self.dQ.data_ptr()), q,
-                                           vp(dS.data_ptr() + 8 * b * (q + 4) * blk))
-            self.sym.sync()
-            hS = dS.cpu().numpy()
-            for b, k0 in enumerate(range(0, mc, blk)):
-                rb = min(blk, mc - k0)
-                out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
+            src.load(slice(rows.start + j0, rows.start + j0 + mc) if run else rows[j0:j0 + mc])
+            self._run_blocks(dS, out[:, j0:j0 + mc], src.enqueue)
         return out
 
     def __call__(self, genotypes):
@@ -146,7 +157,7 @@ class AssociationScan(WhitenedModel):
         marker without an observed value or without variation gets NaN in the first four."""
         g = check_genotypes(genotypes, self.n)
         self._check_factor()
-        return self._finish(self._stats(g) if g.shape[0] else np.empty((self.q + 4, 0)))
+        return self._finish(self._stats(Int8Rows(self, g), slice(0, g.shape[0]), _CHUNK_BYTES))
 
     def _finish(self, S):
         """The host algebra on the (q + 4) x m statistics of either block entry point: the dict ``__call__`` returns."""
@@ -170,7 +181,21 @@ class AssociationScan(WhitenedModel):
         None when the file holds exactly the n individuals in that order; ``markers``: None, a slice or a 1-D integer array;
         ``count``: the counted allele, "A1" or "A2".  Returns what ``__call__`` returns for the unpacked, gathered markers
         (``bed.read(markers, sample_index, count)``), bit for bit in deterministic mode."""
-        from .bed import BedFile, count_flag, marker_indices
+        from .bed import marker_indices
+        src = self._bed_source(bed, sample_index, count)
+        rows = marker_indices(markers, src.m)
+        if chunk_bytes is None:
+            chunk_bytes = _CHUNK_BYTES
+        self._check_factor()
+        S = self._stats(src, as_run(rows), int(chunk_bytes))
+        if rows.size:
+            self.bed_seconds = (src.t_read, src.t_copy, time.perf_counter() - src.t0)
+        return self._finish(S)
+
+    def _bed_source(self, bed, sample_index, count):
+        """What ``scan_bed`` and ``VariantSetTest.test_bed`` check first, before any launch: ``bed`` as a ``BedFile``, the
+        counted allele, the sample map or the refusal of a file of another size without one.  Returns the ``BedRows``."""
+        from .bed import BedFile, count_flag
         if not isinstance(bed, BedFile):
             bed = BedFile(bed)
         flag = count_flag(count)
@@ -181,56 +206,11 @@ class AssociationScan(WhitenedModel):
             idx = None
         else:
             idx = bed.check_sample_index(sample_index, self.n)
-        rows = marker_indices(markers, bed.n_markers)
-        if chunk_bytes is None:
-            chunk_bytes = _CHUNK_BYTES
-        self._check_factor()
-        return self._finish(self._stats_bed(bed, rows, idx, flag, int(chunk_bytes)) if rows.size else np.empty((self.q + 4, 0)))
+        return BedRows(self, bed, idx, flag)
 
-    def _stats_bed(self, bed, rows, idx, flag, chunk_bytes):
-        """(q + 4) x m statistics of ``scilmm_scan_block_bed_dev`` for the markers ``rows``: a chunk is copied from the mapped
-        file into a pinned buffer (the one host pass over its bytes) and from there to the device in one copy; the rows keep
-        the file's pitch.  ``bed_seconds`` = (reading the file, host-to-device copies, everything) of the last call."""
-        import time
-        torch, q, blk = self.torch, self.q, self.block
-        m, nb = rows.size, bed.row_bytes
-        out = np.empty((q + 4, m))
-        per = max(blk, min(m, max(1, chunk_bytes // nb)) // blk * blk)
-        cap = (min(per, m) * nb + 15) // 16 * 16
-        hB = torch.empty((cap,), dtype=torch.uint8).pin_memory()
-        dB = torch.empty((cap,), dtype=torch.uint8, device="cuda")
-        nblk = (min(per, m) + blk - 1) // blk
-        dS = torch.empty((nblk, (q + 4) * blk), dtype=torch.float64, device="cuda")
-        dI = None if idx is None else torch.from_numpy(idx).cuda()
-        run = rows.size > 1 and bool(np.all(np.diff(rows) == 1))    # consecutive markers: a slab of the file
-        vp = C.c_void_p
-        t_read = t_copy = 0.0
-        t0 = time.perf_counter()
-        for j0 in range(0, m, per):
-            mc = min(per, m - j0)
-            t1 = time.perf_counter()
-            stage = hB.numpy()[:mc * nb].reshape(mc, nb)
-            np.copyto(stage, bed.packed[rows[j0]:rows[j0] + mc] if run else bed.packed[rows[j0:j0 + mc]])
-            t2 = time.perf_counter()
-            dB[:mc * nb].copy_(hB[:mc * nb], non_blocking=True)
-            torch.cuda.synchronize()
-            t_read, t_copy = t_read + t2 - t1, t_copy + time.perf_counter() - t2
-            for b, k0 in enumerate(range(0, mc, blk)):
-                rb = min(blk, mc - k0)
-                self.factor.scan_block_bed_dev(vp(dB.data_ptr() + k0 * nb), nb, bed.n_samples,
-                                               None if dI is None else vp(dI.data_ptr()), flag, rb, vp(self.dQ.data_ptr()), q,
-                                               vp(dS.data_ptr() + 8 * b * (q + 4) * blk))
-            self.sym.sync()
-            hS = dS.cpu().numpy()
-            for b, k0 in enumerate(range(0, mc, blk)):
-                rb = min(blk, mc - k0)
-                out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
-        self.bed_seconds = (t_read, t_copy, time.perf_counter() - t0)
-        return out
-
-    def _dosage_input(self, dosages, sample_index):
-        """The checks ``scan_dosages`` and ``VariantSetTest.test_dosages`` share, before any launch: (array, element type of
-        the C entry point, sample map or None)."""
+    def _dosage_source(self, dosages, sample_index):
+        """The checks ``scan_dosages`` and ``VariantSetTest.test_dosages`` share, before any launch.  Returns the
+        ``DosageRows``."""
         from .bed import check_sample_index
         from .dosage import check_dosages
         d = check_dosages(dosages, self.n if sample_index is None else None)
@@ -239,26 +219,7 @@ class AssociationScan(WhitenedModel):
             if d.shape[1] < 1:
                 raise ValueError("dosages without samples")
             idx = check_sample_index(sample_index, d.shape[1], self.n, source="dosage matrix")
-        return d, (_lib.DOSAGE_U16 if d.dtype == np.uint16 else _lib.DOSAGE_F32), idx
-
-    def _dosage_stage(self, d, rows_max):
-        """Buffers for up to ``rows_max`` dosage rows at a time and the function that brings rows to the device: host array ->
-        pinned buffer (the one host pass over the bytes) -> device rows that start on 16-byte boundaries, so every read is an
-        aligned one and the order of a float marker's sums does not depend on where its row lies.  Returns (device pointer,
-        pitch in elements, load(rows of d))."""
-        torch = self.torch
-        es, N = d.dtype.itemsize, d.shape[1]
-        nb = N * es
-        ldb = (nb + 15) // 16 * 16
-        hB = torch.empty((rows_max, nb), dtype=torch.uint8).pin_memory()
-        dB = torch.empty((rows_max, ldb), dtype=torch.uint8, device="cuda")
-
-        def load(rows):
-            k = rows.shape[0]
-            np.copyto(hB.numpy()[:k], rows.view(np.uint8).reshape(k, nb))
-            dB[:k, :nb].copy_(hB[:k], non_blocking=True)
-            torch.cuda.synchronize()
-        return dB.data_ptr(), ldb // es, load
+        return DosageRows(self, d, _lib.DOSAGE_U16 if d.dtype == np.uint16 else _lib.DOSAGE_F32, idx)
 
     def scan_dosages(self, dosages, sample_index=None, chunk_bytes=None):
         """The scan of ``__call__`` on imputed dosages: ``dosages`` is m x N, marker-major, C-contiguous (``np.memmap``
@@ -269,36 +230,10 @@ class AssociationScan(WhitenedModel):
         ``_CHUNK_BYTES``) go through a pinned buffer to the device and every block through ``scilmm_scan_block_dosage_dev``.
         Returns the dict of ``__call__``; for uint16 codes of hard calls, bit for bit what ``__call__`` returns for the int8
         markers in deterministic mode."""
-        d, dtype, idx = self._dosage_input(dosages, sample_index)
+        src = self._dosage_source(dosages, sample_index)
         if chunk_bytes is None:
             chunk_bytes = _CHUNK_BYTES
         if int(chunk_bytes) < 1:
             raise ValueError("chunk_bytes must be positive")
         self._check_factor()
-        return self._finish(self._stats_dosage(d, dtype, idx, int(chunk_bytes)) if d.shape[0] else np.empty((self.q + 4, 0)))
-
-    def _stats_dosage(self, d, dtype, idx, chunk_bytes):
-        """(q + 4) x m statistics of ``scilmm_scan_block_dosage_dev`` for every row of ``d``, in chunks of whole blocks."""
-        torch, q, blk = self.torch, self.q, self.block
-        m, N = d.shape
-        out = np.empty((q + 4, m))
-        per = max(blk, min(m, max(1, chunk_bytes // (N * d.dtype.itemsize))) // blk * blk)
-        base, ld, load = self._dosage_stage(d, min(per, m))
-        nblk = (min(per, m) + blk - 1) // blk
-        dS = torch.empty((nblk, (q + 4) * blk), dtype=torch.float64, device="cuda")
-        dI = None if idx is None else torch.from_numpy(idx).cuda()
-        vp = C.c_void_p
-        for j0 in range(0, m, per):
-            mc = min(per, m - j0)
-            load(d[j0:j0 + mc])
-            for b, k0 in enumerate(range(0, mc, blk)):
-                rb = min(blk, mc - k0)
-                self.factor.scan_block_dosage_dev(vp(base + k0 * ld * d.dtype.itemsize), dtype, ld, N,
-                                                  None if dI is None else vp(dI.data_ptr()), rb, vp(self.dQ.data_ptr()), q,
-                                                  vp(dS.data_ptr() + 8 * b * (q + 4) * blk))
-            self.sym.sync()
-            hS = dS.cpu().numpy()
-            for b, k0 in enumerate(range(0, mc, blk)):
-                rb = min(blk, mc - k0)
-                out[:, j0 + k0:j0 + k0 + rb] = hS[b, :(q + 4) * rb].reshape(q + 4, rb)
-        return out
+        return self._finish(self._stats(src, slice(0, src.m), int(chunk_bytes)))

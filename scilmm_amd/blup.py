@@ -107,20 +107,11 @@ class BLUP(WhitenedModel):
 
     def _blocks(self, m, enqueue):
         """(q + 2) x m statistics: ``enqueue(k0, rb, stats_ptr)`` queues the block of columns k0 .. k0 + rb - 1."""
-        torch, q, blk = self.torch, self.q, self.block
-        out = np.empty((q + 2, m))
-        if m == 0:
-            return out
-        starts = list(range(0, m, blk))
-        dS = torch.empty((len(starts), (q + 2) * blk), dtype=torch.float64, device="cuda")
-        torch.cuda.synchronize()
-        for b, k0 in enumerate(starts):
-            enqueue(k0, min(blk, m - k0), C.c_void_p(dS.data_ptr() + 8 * b * (q + 2) * blk))
-        self.sym.sync()
-        hS = dS.cpu().numpy()
-        for b, k0 in enumerate(starts):
-            rb = min(blk, m - k0)
-            out[:, k0:k0 + rb] = hS[b, :(q + 2) * rb].reshape(q + 2, rb)
+        out = np.empty((self.q + 2, m))
+        if m:
+            dS = self._stats_buffer(self.q + 2, m)
+            self.torch.cuda.synchronize()
+            self._run_blocks(dS, out, enqueue)
         return out
 
     def reliability(self, k=0, individuals=None):

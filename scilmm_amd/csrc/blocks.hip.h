@@ -1,0 +1,179 @@
+// The block calls on a resident factor (included by engine.hip only, behind sweep.hip.h; the entry points' argument checks
+// stay there): BlockCall, marker_block for the marker scan's input forms and their fills, rel_block and rows_block for the BLUP.
+#pragma once
+
+namespace {
+
+// One block of statistics (marker scan, relationship columns, caller rows).  The entry point checks its own arguments
+// beside args_ok, then: begin (the refusals and the one-off allocations), its own checks that need the device state, open
+// (the sweep's set-up, event 0, W zeroed where the producer only scatters), its producer kernel into W, finish.
+struct BlockCall {
+  scilmm_factor* const fac;
+  scilmm_symbolic* const sym;
+  const DevGuard guard;
+  Dev* D = nullptr;
+  std::optional<Sweep> sw;
+
+  // before anything is dereferenced (fac->sym->S is what the constructor and the entry points read next)
+  static bool args_ok(const scilmm_factor* fac, int32_t r, const double* d_Q, int32_t q, const double* d_stats) {
+    return fac && d_Q && d_stats && r >= 1 && r <= RPMAX && q >= 1 && q <= SCAN_QMAX && fac->sym && fac->sym->S;
+  }
+  explicit BlockCall(scilmm_factor* f) : fac(f), sym(f->sym), guard(f->sym) {}
+
+  // the refusals, the slice partial sums (allocated on the first call on a handle, or for a wider q; nothing is allocated
+  // per block afterwards), the events and the inverse permutation; `gram`: the partial tiles of X^T X as well (allocated on
+  // the first Gram block on a handle, for the widest block: never again)
+  int begin(int32_t q, const char* who, bool gram = false) {
+    TRY(check_half(fac, who));
+    TRY(begin_rhs(fac, who));
+    D = (Dev*)sym->device;
+    const int64_t nslice = ((int64_t)sym->S->n + SCAN_SLICE - 1) / SCAN_SLICE;
+    const size_t need = (size_t)nslice * (size_t)(q + 1) * RPMAX;
+    if (D->scan_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+    TRY(grow(sym, &D->scan_partial, &D->scan_partial_cap, need));
+    if (gram) {
+      const size_t gneed = (size_t)gram_slices(GRAM_SLICE_MIN) * GRAM_TILES * 256;
+      if (D->gram_partial_cap < gneed) HIPCHK(hipStreamSynchronize(D->stream));
+      TRY(grow(sym, &D->gram_partial, &D->gram_partial_cap, gneed));
+    }
+    if (!D->scan_ev[0])
+      for (auto& e : D->scan_ev) HIPCHK(hipEventCreate(&e));
+    return ensure_iperm(sym, D);
+  }
+
+  int open(int32_t r, bool zero_W) {
+    sw.emplace(fac, D);
+    sw->set_block(r);
+    HIPCHK(hipEventRecord(D->scan_ev[0], D->stream));
+    if (zero_W) HIPCHK(hipMemsetAsync(D->W, 0, sizeof(double) * (size_t)sw->tot, D->stream));
+    return SCILMM_OK;
+  }
+
+  int64_t gram_slices(int slice) const { return ((int64_t)sym->S->n + slice - 1) / slice; }
+
+  // W holds the block (event 1 is recorded here): the forward sweep, then |x_c|^2 and Q^T x_c from one pass over X, in fixed
+  // row slices folded in slice order, to d_out ((q + 1) x r).  With d_gram (begin was told so): X^T X (r x r) from a second
+  // pass over X on the matrix pipe, inside the statistics interval; without it the launches are the same as ever.
+  int finish(int32_t r, const double* d_Q, int32_t q, double* d_out, double* d_gram = nullptr) {
+    const int32_t n = sym->S->n;
+    hipStream_t s0 = D->stream;
+    const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
+    HIPCHK(hipEventRecord(D->scan_ev[1], s0));
+    TRY(sw->forward_single());
+    HIPCHK(hipEventRecord(D->scan_ev[2], s0));
+    const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
+    hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, d_Q, q, D->scan_partial);
+    hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_out);
+    if (d_gram) {
+      const int32_t nt = sw->rp / 16, ntile = nt * (nt + 1) / 2;
+      const GramShape g = gram_shape();
+      const int64_t gs = gram_slices(g.slice);
+      hipLaunchKernelGGL(gram_kernel(g), dim3((unsigned)gs), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, D->gram_partial);
+      hipLaunchKernelGGL(k_gram_fold, dim3((unsigned)ntile), dim3(GRAM_FOLD * 256), 0, s0, gs, ntile, (const double*)D->gram_partial, r, d_gram);
+    }
+    HIPCHK(hipEventRecord(D->scan_ev[3], s0));
+    D->scan_pending = true;
+    if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
+    HIPCHK(hipGetLastError());
+    return SCILMM_OK;
+  }
+};
+
+// One block of markers, whatever their form.  `fill(D, n, rp)` launches the form's two kernels on D->stream: rows 0..2 of the
+// statistics (n_obs, mean, centred sum of squares) by a workgroup per marker, then W = P (g - mean), missing = 0, columns padded
+// to rp, each tile of individuals written straight to its permuted rows.  Rows 3..: |w(g)|^2 and Q^T w(g); with d_gram, X^T X.
+template <class Fill>
+int marker_block(scilmm_factor* fac, const char* who, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram, Fill fill) {
+  BlockCall b(fac);
+  TRY(b.begin(q, who, d_gram != nullptr));
+  TRY(b.open(r, false));
+  fill(b.D, b.sym->S->n, b.sw->rp);
+  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, d_gram);
+}
+
+// The fills.  int8 rows: exact integer sums, no order to fix; packed PLINK rows: the same sums taken class by class; dosage rows
+// of element type T: integer sums (uint16) or fixed-order fp64 sums in two passes (float).  W goes through the sample map if any.
+unsigned scan_tiles(int32_t n) { return (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE); }
+
+auto fill_int8(const int8_t* d_geno, int64_t ld_geno, int32_t r, double* d_stats) {
+  return [=](Dev* D, int32_t n, int32_t rp) {
+    hipLaunchKernelGGL(k_scan_moments, dim3((unsigned)r), dim3(256), 0, D->stream, n, d_geno, ld_geno, r, d_stats);
+    hipLaunchKernelGGL(k_scan_dequant, dim3(scan_tiles(n)), dim3(256), 0, D->stream, n, r, rp, d_geno, ld_geno, (const int32_t*)D->d_iperm,
+                       (const double*)(d_stats + r), D->W);
+  };
+}
+
+auto fill_bed(const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample, int32_t flags, int32_t r, double* d_stats) {
+  return [=](Dev* D, int32_t n, int32_t rp) {
+    hipLaunchKernelGGL(k_bed_moments, dim3((unsigned)r), dim3(256), 0, D->stream, n, n_samples, d_bed, ld_bed, d_sample, flags, r, d_stats);
+    hipLaunchKernelGGL(k_bed_dequant, dim3(scan_tiles(n)), dim3(256), 0, D->stream, n, n_samples, r, rp, d_bed, ld_bed, d_sample, flags,
+                       (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
+  };
+}
+
+template <class T>
+auto fill_dosage(const void* d_dos, int64_t ld, int32_t n_samples, const int32_t* d_sample, int32_t r, double* d_stats) {
+  return [=](Dev* D, int32_t n, int32_t rp) {
+    hipLaunchKernelGGL(k_dos_moments<T>, dim3((unsigned)r), dim3(256), 0, D->stream, n, n_samples, (const T*)d_dos, ld, d_sample, r, d_stats);
+    hipLaunchKernelGGL(k_dos_dequant<T>, dim3(scan_tiles(n)), dim3(256), 0, D->stream, n, n_samples, r, rp, (const T*)d_dos, ld, d_sample,
+                       (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
+  };
+}
+
+// One block of columns `ids` of sum_k weights[k] A_k, built from the resident values (scilmm_rel_block_dev).
+int rel_block(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
+  BlockCall b(fac);
+  scilmm_symbolic* sym = fac->sym;
+  const Symbolic& S = *sym->S;
+  // the requests sorted by permuted index: the kernel bisects this list; a repeated individual shows as a repeated index
+  std::pair<int32_t, int32_t> order[RPMAX];
+  for (int32_t c = 0; c < r; ++c) {
+    if (ids[c] < 0 || ids[c] >= S.n) {
+      sym->err = "scilmm_rel_block_dev: an individual outside 0 .. n-1";
+      return SCILMM_ERR_ARG;
+    }
+    order[c] = {S.iperm[(size_t)ids[c]], c};
+  }
+  std::sort(order, order + r);
+  RelReq req{};
+  for (int32_t c = 0; c < r; ++c) {
+    if (c > 0 && order[c].first == order[c - 1].first) {
+      sym->err = "scilmm_rel_block_dev: an individual is requested twice in one block";
+      return SCILMM_ERR_ARG;
+    }
+    req.p[c] = order[c].first;
+    req.col[c] = order[c].second;
+  }
+  TRY(b.begin(q, "scilmm_rel_block_dev"));
+  Dev* D = b.D;
+  ValPtrs gen{}, dia{};
+  for (int k = 0; k < S.K; ++k) {
+    if (weights[k] == 0.0) continue;
+    if (!D->have_vals[k]) {
+      sym->err = "scilmm_rel_block_dev: the values of a matrix with a nonzero weight are not resident";
+      return SCILMM_ERR_STATE;
+    }
+    TRY(push_val(sym, S.is_diag[k] ? dia : gen, D->vals[k], weights[k]));
+  }
+  TRY(b.open(r, true));
+  // W = P G[:, ids]: the stored columns (r workgroups), then one streaming pass over the pattern for the row parts; row 0 of
+  // the statistics = G[i, i]
+  const unsigned pass = gen.count > 0 ? (unsigned)std::min<int64_t>((S.nnz_pattern + 255) / 256, REL_GRID) : 0u;
+  hipLaunchKernelGGL(k_rel_gather, dim3((unsigned)r + pass), dim3(256), 0, D->stream, D->v, S.nnz_pattern, gen, dia, req, r, b.sw->rp, D->W,
+                     d_stats);
+  return b.finish(r, d_Q, q, d_stats + (int64_t)r);
+}
+
+// The same for r caller rows in CSR on the device (scilmm_rows_block_dev).
+int rows_block(scilmm_factor* fac, const int64_t* d_indptr, const int32_t* d_indices, const double* d_data, int32_t r, const double* d_Q,
+               int32_t q, double* d_stats) {
+  BlockCall b(fac);
+  TRY(b.begin(q, "scilmm_rows_block_dev"));
+  TRY(b.open(r, true));
+  // W[iperm[idx]][c] = data: a wave per row; row 0 of the statistics = 0
+  hipLaunchKernelGGL(k_rows_scatter, dim3((unsigned)((r + 3) / 4)), dim3(256), 0, b.D->stream, b.sym->S->n, r, b.sw->rp, d_indptr, d_indices,
+                     d_data, (const int32_t*)b.D->d_iperm, b.D->W, d_stats);
+  return b.finish(r, d_Q, q, d_stats + (int64_t)r);
+}
+
+}  // namespace

@@ -2,13 +2,14 @@
 // (kernels.hip.h, scan.hip.h, gram.hip.h, bed.hip.h, dosage.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
-//   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing, BlockCall (scan and BLUP blocks);
+//   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
 // The device state they run on (struct Dev, dev.h) is built once per handle by plan.hip.  Everything runs on one HIP stream
 // per symbolic handle; host entry points synchronise only where they hand data back to the caller.  An entry point is its
-// argument checks (before anything is dereferenced), a DevGuard and one call.
+// argument checks (before anything is dereferenced), a DevGuard (a block call's sits in its BlockCall) and one call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,24 +59,10 @@ struct scilmm_factor {
 #include "launch.hip.h"
 #include "factorize.hip.h"
 #include "sweep.hip.h"
+#include "blocks.hip.h"
 #include "products.hip.h"
 #include "values.hip.h"
 #include "sinv.hip.h"
-
-// The two kernels of a dosage block (scan_block_dosage below) for its element type: moments, then W.
-template <class T>
-static void launch_dosage(const BlockCall& b, const void* d_dos, int64_t ld, int32_t n_samples, const int32_t* d_sample, int32_t r,
-                          double* d_stats) {
-  Dev* D = b.D;
-  const int32_t n = b.sym->S->n;
-  hipStream_t s0 = D->stream;
-  // rows 0..2 of the statistics: integer sums (uint16) or fixed-order fp64 sums in two passes (float)
-  hipLaunchKernelGGL(k_dos_moments<T>, dim3((unsigned)r), dim3(256), 0, s0, n, n_samples, (const T*)d_dos, ld, d_sample, r, d_stats);
-  // W = P (g - mean) tile by tile, through the sample map where there is one
-  const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
-  hipLaunchKernelGGL(k_dos_dequant<T>, dim3(tiles), dim3(256), 0, s0, n, n_samples, r, b.sw->rp, (const T*)d_dos, ld, d_sample,
-                     (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
-}
 
 extern "C" {
 
@@ -239,164 +226,73 @@ int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double*
   return rhs_entry(fac, dB, r, dX, RHS_SOLVE_LT, false, "scilmm_solve_Lt_dev");
 }
 
-// One block of int8 markers; `gram`: the entry point hands X^T X back as well (d_gram, checked here).
+// The marker scan's blocks, one checker per input form; `gram`: the entry point (`who`) hands X^T X back as well, to d_gram
+// (null from the others).  What needs no handle is checked first: with it wrong, nothing of the handle is read.
 static int scan_block(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q, double* d_stats,
                       bool gram, double* d_gram, const char* who) {
   if (!d_geno || (gram && !d_gram) || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  BlockCall b(fac);
-  TRY(b.begin(q, who, gram));
-  TRY(b.open(r, false));
-  Dev* D = b.D;
-  const int32_t n = b.sym->S->n;
-  hipStream_t s0 = D->stream;
-  // rows 0..2 of the statistics: n_obs, mean, centred sum of squares (exact integer sums: no order to fix)
-  hipLaunchKernelGGL(k_scan_moments, dim3((unsigned)r), dim3(256), 0, s0, n, d_geno, ld_geno, r, d_stats);
-  // W = P (g - mean), missing = 0, columns padded to rp: each tile of individuals is written straight to its permuted rows
-  const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
-  hipLaunchKernelGGL(k_scan_dequant, dim3(tiles), dim3(256), 0, s0, n, r, b.sw->rp, d_geno, ld_geno, (const int32_t*)D->d_iperm,
-                     (const double*)(d_stats + r), D->W);
-  // rows 3..: |w(g)|^2 and Q^T w(g)
-  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, gram ? d_gram : nullptr);
+  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_int8(d_geno, ld_geno, r, d_stats));
+}
+
+static int scan_block_bed(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample, int32_t flags,
+                          int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
+  if (!d_bed || (gram && !d_gram) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) ||
+      !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_bed(d_bed, ld_bed, n_samples, d_sample, flags, r, d_stats));
+}
+
+static int scan_block_dosage(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples, const int32_t* d_sample,
+                             int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
+  if (!d_dos || (gram && !d_gram) || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
+      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
+      !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return dtype == SCILMM_DOSAGE_U16
+             ? marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<uint16_t>(d_dos, ld, n_samples, d_sample, r, d_stats))
+             : marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<float>(d_dos, ld, n_samples, d_sample, r, d_stats));
 }
 
 int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
                           double* d_stats) {
-  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, false, nullptr, "scilmm_scan_block_dev");
+  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, false, nullptr, __func__);
 }
 
 int scilmm_scan_block_gram_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
                                double* d_stats, double* d_gram) {
-  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, true, d_gram, "scilmm_scan_block_gram_dev");
-}
-
-// One block of packed PLINK rows, as scan_block.
-static int scan_block_bed(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample, int32_t flags,
-                          int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
-  // (what needs no handle comes first: with it wrong, nothing of the handle is read)
-  if (!d_bed || (gram && !d_gram) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) ||
-      !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  BlockCall b(fac);
-  TRY(b.begin(q, who, gram));
-  TRY(b.open(r, false));
-  Dev* D = b.D;
-  const int32_t n = b.sym->S->n;
-  hipStream_t s0 = D->stream;
-  // rows 0..2 of the statistics from the packed rows: the integer sums of k_scan_moments, taken class by class
-  hipLaunchKernelGGL(k_bed_moments, dim3((unsigned)r), dim3(256), 0, s0, n, n_samples, d_bed, ld_bed, d_sample, flags, r, d_stats);
-  // W = P (g - mean) decoded tile by tile, through the sample map where there is one
-  const unsigned tiles = (unsigned)(((int64_t)n + SCAN_TILE - 1) / SCAN_TILE);
-  hipLaunchKernelGGL(k_bed_dequant, dim3(tiles), dim3(256), 0, s0, n, n_samples, r, b.sw->rp, d_bed, ld_bed, d_sample, flags,
-                     (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
-  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, gram ? d_gram : nullptr);
+  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, true, d_gram, __func__);
 }
 
 int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                               int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
-  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, false, nullptr, "scilmm_scan_block_bed_dev");
+  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, false, nullptr, __func__);
 }
 
 int scilmm_scan_block_bed_gram_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                                    int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
-  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, true, d_gram,
-                        "scilmm_scan_block_bed_gram_dev");
-}
-
-// One block of dosage rows (uint16 fixed point or float), as scan_block_bed; the two kernels: launch_dosage above.
-static int scan_block_dosage(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples, const int32_t* d_sample,
-                             int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
-  // (what needs no handle comes first: with it wrong, nothing of the handle is read)
-  if (!d_dos || (gram && !d_gram) || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32)) return SCILMM_ERR_ARG;
-  const uintptr_t esize = dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float);
-  if ((uintptr_t)d_dos % esize || n_samples < 1 || ld < n_samples || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) ||
-      (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  BlockCall b(fac);
-  TRY(b.begin(q, who, gram));
-  TRY(b.open(r, false));
-  if (dtype == SCILMM_DOSAGE_U16)
-    launch_dosage<uint16_t>(b, d_dos, ld, n_samples, d_sample, r, d_stats);
-  else
-    launch_dosage<float>(b, d_dos, ld, n_samples, d_sample, r, d_stats);
-  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, gram ? d_gram : nullptr);
+  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, true, d_gram, __func__);
 }
 
 int scilmm_scan_block_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                  const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
-  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, "scilmm_scan_block_dosage_dev");
+  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, __func__);
 }
 
 int scilmm_scan_block_dosage_gram_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                       const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
-  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, true, d_gram,
-                           "scilmm_scan_block_dosage_gram_dev");
+  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, true, d_gram, __func__);
 }
 
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
                          double* d_stats) {
   if (!weights || !ids || !BlockCall::args_ok(fac, r, d_Q, q, d_stats)) return SCILMM_ERR_ARG;
-  BlockCall b(fac);
-  scilmm_symbolic* sym = fac->sym;
-  const Symbolic& S = *sym->S;
-  const int32_t n = S.n;
-  // the requests sorted by permuted index: the kernel bisects this list; a repeated individual shows as a repeated index
-  std::pair<int32_t, int32_t> order[RPMAX];
-  for (int32_t c = 0; c < r; ++c) {
-    if (ids[c] < 0 || ids[c] >= n) {
-      sym->err = "scilmm_rel_block_dev: an individual outside 0 .. n-1";
-      return SCILMM_ERR_ARG;
-    }
-    order[c] = {S.iperm[(size_t)ids[c]], c};
-  }
-  std::sort(order, order + r);
-  for (int32_t c = 1; c < r; ++c)
-    if (order[c].first == order[c - 1].first) {
-      sym->err = "scilmm_rel_block_dev: an individual is requested twice in one block";
-      return SCILMM_ERR_ARG;
-    }
-  TRY(b.begin(q, "scilmm_rel_block_dev"));
-  Dev* D = b.D;
-  ValPtrs gen{}, dia{};
-  for (int k = 0; k < S.K; ++k) {
-    if (weights[k] == 0.0) continue;
-    if (!D->have_vals[k]) {
-      sym->err = "scilmm_rel_block_dev: the values of a matrix with a nonzero weight are not resident";
-      return SCILMM_ERR_STATE;
-    }
-    ValPtrs& t = S.is_diag[k] ? dia : gen;
-    if (t.count >= 8) {
-      sym->err = "more than 8 matrices of one kind";
-      return SCILMM_ERR_ARG;
-    }
-    t.v[t.count] = D->vals[k];
-    t.s2[t.count] = weights[k];
-    t.count++;
-  }
-  RelReq req{};
-  for (int32_t c = 0; c < r; ++c) {
-    req.p[c] = order[c].first;
-    req.col[c] = order[c].second;
-  }
-  TRY(b.open(r, true));
-  // W = P G[:, ids]: the stored columns (r workgroups), then one streaming pass over the pattern for the row parts; row 0 of
-  // the statistics = G[i, i]
-  const unsigned pass = gen.count > 0 ? (unsigned)std::min<int64_t>((S.nnz_pattern + 255) / 256, REL_GRID) : 0u;
-  hipLaunchKernelGGL(k_rel_gather, dim3((unsigned)r + pass), dim3(256), 0, D->stream, D->v, S.nnz_pattern, gen, dia, req, r, b.sw->rp, D->W,
-                     d_stats);
-  return b.finish(r, d_Q, q, d_stats + (int64_t)r);
+  return rel_block(fac, weights, ids, r, d_Q, q, d_stats);
 }
 
 int scilmm_rows_block_dev(scilmm_factor* fac, const int64_t* d_indptr, const int32_t* d_indices, const double* d_data, int32_t r,
                           const double* d_Q, int32_t q, double* d_stats) {
   if (!d_indptr || !d_indices || !d_data || !BlockCall::args_ok(fac, r, d_Q, q, d_stats)) return SCILMM_ERR_ARG;
-  BlockCall b(fac);
-  TRY(b.begin(q, "scilmm_rows_block_dev"));
-  TRY(b.open(r, true));
-  Dev* D = b.D;
-  // W[iperm[idx]][c] = data: a wave per row; row 0 of the statistics = 0
-  hipLaunchKernelGGL(k_rows_scatter, dim3((unsigned)((r + 3) / 4)), dim3(256), 0, D->stream, b.sym->S->n, r, b.sw->rp, d_indptr, d_indices,
-                     d_data, (const int32_t*)D->d_iperm, D->W, d_stats);
-  return b.finish(r, d_Q, q, d_stats + (int64_t)r);
+  return rows_block(fac, d_indptr, d_indices, d_data, r, d_Q, q, d_stats);
 }
 
 int scilmm_quadforms_dev(scilmm_symbolic* sym, int32_t k, const double* dU, int32_t r, double* d_out) {

@@ -30,6 +30,17 @@ enum ProfEvent {
 
 int finish_factorize(scilmm_factor* fac, int32_t* bad_col);
 
+// one more matrix (its resident values, its coefficient) in the list a kernel takes by value: at most 8 of a kind
+int push_val(scilmm_symbolic* sym, ValPtrs& t, const double* v, double s2) {
+  if (t.count >= 8) {
+    sym->err = "more than 8 matrices of one kind";
+    return SCILMM_ERR_ARG;
+  }
+  t.v[t.count] = v;
+  t.s2[t.count++] = s2;
+  return SCILMM_OK;
+}
+
 // One factorization being queued: the steps of run_factorize, in the order it calls them.
 struct Factorization : FactorLaunch {
   scilmm_symbolic* const sym;
@@ -88,16 +99,7 @@ struct Factorization : FactorLaunch {
     int32_t big = 0x7fffffff;
     HIPCHK(hipMemcpyAsync(fac->status, &big, sizeof(int32_t), hipMemcpyHostToDevice, st));
     ValPtrs gen{}, dia{};
-    for (int k = 0; k < S.K; ++k) {
-      ValPtrs& t = S.is_diag[k] ? dia : gen;
-      if (t.count >= 8) {
-        sym->err = "more than 8 matrices of one kind";
-        return SCILMM_ERR_ARG;
-      }
-      t.v[t.count] = D->vals[k];
-      t.s2[t.count] = sigma2[k];
-      t.count++;
-    }
+    for (int k = 0; k < S.K; ++k) TRY(push_val(sym, S.is_diag[k] ? dia : gen, D->vals[k], sigma2[k]));
     if (S.nnz_pattern > 0) {
       int blocks = (int)std::min<int64_t>((S.nnz_pattern + 255) / 256, 256 * 16);
       hipLaunchKernelGGL(k_assemble, dim3(blocks), dim3(256), 0, st, S.nnz_pattern, D->v.asm_dst, gen, fac->L);

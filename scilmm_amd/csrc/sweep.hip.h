@@ -5,8 +5,7 @@
 // solve_dist, lmul_single, lmul_dist -- built from pull / pull_groups (deterministic mode), chain, handoff (distributed) and
 // mark_mid; the kernels go through SweepLaunch.  begin_rhs is what every sweep call does first, run_rhs the device-pointer
 // body of the solves and L*R, host_rhs its host form (staged through Dev::IO), finish_rhs_timing what scilmm_sync reads.
-// BlockCall is what the block entry points (marker scan, relationship columns, caller rows: the kernels of scan.hip.h and
-// blup.hip.h) share around their own producer of the right-hand-side block.
+// The block calls (marker scan, BLUP) run forward_single between their own producer and reduction: blocks.hip.h.
 #pragma once
 
 namespace {
@@ -327,80 +326,5 @@ int host_rhs(scilmm_factor* fac, const double* B, int32_t r, double* X, int mode
   HIPCHK(hipStreamSynchronize(D->stream));
   return finish_rhs_timing(sym, D, mode);
 }
-
-// One block of statistics (marker scan, relationship columns, caller rows).  The entry point checks its own arguments
-// beside args_ok, then: begin (the refusals and the one-off allocations), its own checks that need the device state, open
-// (the sweep's set-up, event 0, W zeroed where the producer only scatters), its producer kernel into W, finish.
-struct BlockCall {
-  scilmm_factor* const fac;
-  scilmm_symbolic* const sym;
-  const DevGuard guard;
-  Dev* D = nullptr;
-  std::optional<Sweep> sw;
-
-  // before anything is dereferenced (fac->sym->S is what the constructor and the entry points read next)
-  static bool args_ok(const scilmm_factor* fac, int32_t r, const double* d_Q, int32_t q, const double* d_stats) {
-    return fac && d_Q && d_stats && r >= 1 && r <= RPMAX && q >= 1 && q <= SCAN_QMAX && fac->sym && fac->sym->S;
-  }
-  explicit BlockCall(scilmm_factor* f) : fac(f), sym(f->sym), guard(f->sym) {}
-
-  // the refusals, the slice partial sums (allocated on the first call on a handle, or for a wider q; nothing is allocated
-  // per block afterwards), the events and the inverse permutation; `gram`: the partial tiles of X^T X as well (allocated on
-  // the first Gram block on a handle, for the widest block: never again)
-  int begin(int32_t q, const char* who, bool gram = false) {
-    TRY(check_half(fac, who));
-    TRY(begin_rhs(fac, who));
-    D = (Dev*)sym->device;
-    const int64_t nslice = ((int64_t)sym->S->n + SCAN_SLICE - 1) / SCAN_SLICE;
-    const size_t need = (size_t)nslice * (size_t)(q + 1) * RPMAX;
-    if (D->scan_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-    TRY(grow(sym, &D->scan_partial, &D->scan_partial_cap, need));
-    if (gram) {
-      const size_t gneed = (size_t)gram_slices(GRAM_SLICE_MIN) * GRAM_TILES * 256;
-      if (D->gram_partial_cap < gneed) HIPCHK(hipStreamSynchronize(D->stream));
-      TRY(grow(sym, &D->gram_partial, &D->gram_partial_cap, gneed));
-    }
-    if (!D->scan_ev[0])
-      for (auto& e : D->scan_ev) HIPCHK(hipEventCreate(&e));
-    return ensure_iperm(sym, D);
-  }
-
-  int open(int32_t r, bool zero_W) {
-    sw.emplace(fac, D);
-    sw->set_block(r);
-    HIPCHK(hipEventRecord(D->scan_ev[0], D->stream));
-    if (zero_W) HIPCHK(hipMemsetAsync(D->W, 0, sizeof(double) * (size_t)sw->tot, D->stream));
-    return SCILMM_OK;
-  }
-
-  int64_t gram_slices(int slice) const { return ((int64_t)sym->S->n + slice - 1) / slice; }
-
-  // W holds the block (event 1 is recorded here): the forward sweep, then |x_c|^2 and Q^T x_c from one pass over X, in fixed
-  // row slices folded in slice order, to d_out ((q + 1) x r).  With d_gram (begin was told so): X^T X (r x r) from a second
-  // pass over X on the matrix pipe, inside the statistics interval; without it the launches are the same as ever.
-  int finish(int32_t r, const double* d_Q, int32_t q, double* d_out, double* d_gram = nullptr) {
-    const int32_t n = sym->S->n;
-    hipStream_t s0 = D->stream;
-    const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
-    HIPCHK(hipEventRecord(D->scan_ev[1], s0));
-    TRY(sw->forward_single());
-    HIPCHK(hipEventRecord(D->scan_ev[2], s0));
-    const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
-    hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, d_Q, q, D->scan_partial);
-    hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_out);
-    if (d_gram) {
-      const int32_t nt = sw->rp / 16, ntile = nt * (nt + 1) / 2;
-      const GramShape g = gram_shape();
-      const int64_t gs = gram_slices(g.slice);
-      hipLaunchKernelGGL(gram_kernel(g), dim3((unsigned)gs), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, D->gram_partial);
-      hipLaunchKernelGGL(k_gram_fold, dim3((unsigned)ntile), dim3(GRAM_FOLD * 256), 0, s0, gs, ntile, (const double*)D->gram_partial, r, d_gram);
-    }
-    HIPCHK(hipEventRecord(D->scan_ev[3], s0));
-    D->scan_pending = true;
-    if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
-    HIPCHK(hipGetLastError());
-    return SCILMM_OK;
-  }
-};
 
 }  // namespace

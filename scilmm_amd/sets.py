@@ -30,6 +30,7 @@ import scipy.optimize as opt
 import scipy.stats as stats
 
 from .assoc import AssociationScan, check_genotypes
+from .markers import Int8Rows
 
 LAMBDA_FLOOR = 1e-10      # eigenvalues below this fraction of the largest are dropped from the mixture
 SADDLE_SEAM = 0.05        # |q - mean| below this many standard deviations: the saddlepoint formula is singular, Liu instead
@@ -189,10 +190,7 @@ class VariantSetTest(AssociationScan):
         ``burden_beta``, ``burden_se``, ``burden_chi2``, ``burden_p``, ``skat_q``, ``skat_p``; with ``return_kernel`` also
         ``kernel``, a list of ``(s, K, w)`` per set.  A marker without an observed value or without variation is dropped
         from its set (``n_used`` counts the rest); a set with nothing left gets NaN."""
-        g = check_genotypes(genotypes, self.n)
-        sets, weights, sf = self._check(sets, g.shape[0], weights, method)
-        self._check_factor()
-        return self._run(sets, weights, sf, return_kernel, self._int8_block(g) if sets else None)
+        return self._run(Int8Rows(self, check_genotypes(genotypes, self.n)), sets, weights, method, return_kernel)
 
     def test_bed(self, bed, sets, sample_index=None, count="A1", chunk_bytes=None, weights="beta", method="saddlepoint",
                  return_kernel=False):
@@ -201,100 +199,41 @@ class VariantSetTest(AssociationScan):
         block's packed rows are uploaded as they lie in the file, so ``chunk_bytes`` has nothing to bound and is accepted
         for symmetry only.  Returns the bits of ``__call__`` on ``bed.read(None, sample_index, count)`` in deterministic
         mode."""
-        from .bed import BedFile, count_flag
-        if not isinstance(bed, BedFile):
-            bed = BedFile(bed)
-        flag = count_flag(count)
-        if sample_index is None:
-            if bed.n_samples != self.n:
-                raise ValueError("the file has %d samples, the model %d individuals: give a sample_index"
-                                 % (bed.n_samples, self.n))
-            idx = None
-        else:
-            idx = bed.check_sample_index(sample_index, self.n)
+        src = self._bed_source(bed, sample_index, count)
         if chunk_bytes is not None and int(chunk_bytes) < 1:
             raise ValueError("chunk_bytes must be positive")
-        sets, weights, sf = self._check(sets, bed.n_markers, weights, method)
-        self._check_factor()
-        return self._run(sets, weights, sf, return_kernel, self._bed_block(bed, idx, flag) if sets else None)
+        return self._run(src, sets, weights, method, return_kernel)
 
     def test_dosages(self, dosages, sets, sample_index=None, weights="beta", method="saddlepoint", return_kernel=False):
         """``__call__`` on imputed dosages (``scilmm_scan_block_dosage_gram_dev``): ``sets`` index the rows of ``dosages``;
         ``dosages`` and ``sample_index`` as for ``AssociationScan.scan_dosages``.  The "beta" weights take half the mean
         dosage for the allele frequency.  For uint16 codes of hard calls it returns the bits of ``__call__`` on the int8
         markers in deterministic mode."""
-        d, dtype, idx = self._dosage_input(dosages, sample_index)
-        sets, weights, sf = self._check(sets, d.shape[0], weights, method)
-        self._check_factor()
-        return self._run(sets, weights, sf, return_kernel, self._dosage_block(d, dtype, idx) if sets else None)
+        return self._run(self._dosage_source(dosages, sample_index), sets, weights, method, return_kernel)
 
-    def _check(self, sets, m, weights, method):
-        sets = check_sets(sets, m, self.block)
-        return sets, check_weights(weights, sets), check_method(method)
-
-    def _buffers(self):
-        """Device buffers of one block's outputs, and the function that waits for the block and brings them to the host."""
+    def _block(self, src):
+        """rows -> ((q + 4) x r statistics, r x r Gram matrix) of one block of the marker source ``src``, on the host: the rows
+        are brought to the device, one call of the form's Gram entry point, one wait, two device-to-host copies."""
         torch, q, blk = self.torch, self.q, self.block
+        src.stage(blk)
         dS = torch.empty(((q + 4) * blk,), dtype=torch.float64, device="cuda")
         dK = torch.empty((blk * blk,), dtype=torch.float64, device="cuda")
 
-        def fetch(rb):
+        def run(rows):
+            rb = rows.size
+            src.load(rows)
+            src.enqueue(0, rb, C.c_void_p(dS.data_ptr()), C.c_void_p(dK.data_ptr()))
             self.sym.sync()
             return dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb), dK[:rb * rb].cpu().numpy().reshape(rb, rb)
-        return C.c_void_p(dS.data_ptr()), C.c_void_p(dK.data_ptr()), fetch
-
-    def _int8_block(self, g):
-        """rows -> ((q + 4) x r statistics, r x r Gram matrix) of one block of int8 markers, on the host."""
-        torch, n, q, blk = self.torch, self.n, self.q, self.block
-        ld = (n + 15) // 16 * 16      # rows of the device copy start on 16-byte boundaries: every read is an aligned one
-        dG = torch.empty((blk, ld), dtype=torch.int8, device="cuda")
-        pS, pK, fetch = self._buffers()
-        vp = C.c_void_p
-
-        def run(rows):
-            dG[:rows.size, :n].copy_(torch.from_numpy(g[rows]))
-            torch.cuda.synchronize()
-            self.factor.scan_block_gram_dev(vp(dG.data_ptr()), ld, rows.size, vp(self.dQ.data_ptr()), q, pS, pK)
-            return fetch(rows.size)
         return run
 
-    def _bed_block(self, bed, idx, flag):
-        """The same from packed rows: file -> pinned buffer -> device, the rows keep the file's pitch."""
-        torch, q, blk, nb = self.torch, self.q, self.block, bed.row_bytes
-        cap = (blk * nb + 15) // 16 * 16
-        hB = torch.empty((cap,), dtype=torch.uint8).pin_memory()
-        dB = torch.empty((cap,), dtype=torch.uint8, device="cuda")
-        dI = None if idx is None else torch.from_numpy(idx).cuda()
-        pS, pK, fetch = self._buffers()
-        vp = C.c_void_p
-
-        def run(rows):
-            np.copyto(hB.numpy()[:rows.size * nb].reshape(rows.size, nb), bed.packed[rows])
-            dB[:rows.size * nb].copy_(hB[:rows.size * nb], non_blocking=True)
-            torch.cuda.synchronize()
-            self.factor.scan_block_bed_gram_dev(vp(dB.data_ptr()), nb, bed.n_samples, None if dI is None else vp(dI.data_ptr()),
-                                                flag, rows.size, vp(self.dQ.data_ptr()), q, pS, pK)
-            return fetch(rows.size)
-        return run
-
-    def _dosage_block(self, d, dtype, idx):
-        """The same from dosage rows: host array -> pinned buffer -> device (``AssociationScan._dosage_stage``)."""
-        q, N = self.q, d.shape[1]
-        base, ld, load = self._dosage_stage(d, self.block)
-        dI = None if idx is None else self.torch.from_numpy(idx).cuda()
-        pS, pK, fetch = self._buffers()
-        vp = C.c_void_p
-
-        def run(rows):
-            load(d[rows])
-            self.factor.scan_block_dosage_gram_dev(vp(base), dtype, ld, N, None if dI is None else vp(dI.data_ptr()), rows.size,
-                                                   vp(self.dQ.data_ptr()), q, pS, pK)
-            return fetch(rows.size)
-        return run
-
-    def _run(self, sets, weights, sf, return_kernel, block):
-        """Block by block: gather the block's marker rows, one device call, one device-to-host copy of the statistics and the
-        Gram matrix (``block``), then the host algebra set by set."""
+    def _run(self, src, sets, weights, method, return_kernel):
+        """The checks of the sets (before any launch), then block by block: gather the block's marker rows, one device call, the
+        statistics and the Gram matrix (``_block``), the host algebra set by set."""
+        sets = check_sets(sets, src.m, self.block)
+        weights, sf = check_weights(weights, sets), check_method(method)
+        self._check_factor()
+        block = self._block(src) if sets else None
         ns = len(sets)
         out = {k: np.full(ns, np.nan) for k in KEYS}
         out["n_used"] = np.zeros(ns, dtype=np.int64)

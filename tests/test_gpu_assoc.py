@@ -133,6 +133,20 @@ def test_deterministic_scan_repeats_its_bits():
     _compare(a, _oracle(p, S2, 4, p["G"]), p["n"])
 
 
+def test_more_than_one_chunk_gives_the_bits_of_one_chunk(monkeypatch):
+    """The int8 scan in several chunks (``assoc._CHUNK_BYTES`` is read at call time) against the one chunk of the default: one
+    block per chunk (eight full chunks and one of 2 markers), then two blocks per chunk (four full chunks and one of 2)."""
+    from scilmm_amd import assoc
+    p = _problem("pedigree")
+    scan, _ = _scan(p, 4, 16, deterministic=True)
+    ref = scan(p["G"])
+    for chunk_bytes in (1, 32 * ((p["n"] + 15) // 16 * 16)):
+        monkeypatch.setattr(assoc, "_CHUNK_BYTES", chunk_bytes)
+        out = scan(p["G"])
+        for k in ref:
+            assert np.array_equal(out[k], ref[k], equal_nan=True), (chunk_bytes, k)
+
+
 def test_repeated_use_and_a_second_sigma2():
     """One object, two marker sets; then a second object after the factor moved to another sigma2: nothing is carried over."""
     from scilmm_amd import ScilmmError
