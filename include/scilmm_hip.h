@@ -296,9 +296,50 @@ int scilmm_scan_block_dosage_gram_dev(scilmm_factor* fac, const void* d_dos, int
                                       const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats,
                                       double* d_gram);
 
+/* The three scan blocks for a marker x environment INTERACTION test (G x E): every marker of the block is tested with d = 1 + m
+ * terms, its own column g~ and g~ o e_1 .. g~ o e_m (o = the entry-wise product with an environment column: sex, treatment,
+ * herd, age, diet), so the interaction columns differ from marker to marker and cannot be covariates of the scan.  The
+ * whitening identity of scilmm_scan_block_dev holds term by term: GLS of y on [C, g~, g~ o e_1 ..] under V is OLS on the
+ * whitened columns, so a marker costs d columns of the forward sweep and one symmetric d x d system on the host.
+ *   d_E    : n x m row-major, PERMUTED order (the order of d_Q: row p = individual perm[p]); 1 <= m <= 3.  The columns are
+ *            expected among the covariates behind d_Q (the main effects in the null model): g~ o e_a is then g o e_a with mean
+ *            imputation after projection, and nothing else needs centring.  The entry points do not check it.
+ *   r      : markers in the block, 1 .. 128 / d rounded down (64, 42, 32).
+ *   d_stats: (3 + (q + 1) d + d (d - 1) / 2) x r row-major:
+ *            rows 0 .. 2           n_obs | mean | centred sum of squares, as scilmm_scan_block_dev writes them;
+ *            row 3 + k d + a       quantity k of term a: k = 0 is |x_a|^2, k = 1 .. q is row k - 1 of Q^T x_a, where
+ *                                  x_a = w(g~ o e_a), x_0 = w(g~);
+ *            then                  x_a' x_b for the pairs (a, b), a < b, in lexicographic order.
+ *   the form's own arguments, d_Q, q: as for the plain entry point of the form.
+ * The block has d r columns, column a r + c = term a of marker c: the form's two kernels write columns 0 .. r - 1 as ever,
+ * k_scan_expand multiplies them into columns r .. d r - 1 in place (one kernel for every form), the forward sweep and
+ * the statistics are those of scilmm_scan_block_dev on d r columns -- its (q + 1) x (d r) output is rows 3 .. of d_stats
+ * as they stand -- and k_scan_cross reads the forward solution a second time where it lies for the pairs: fixed row
+ * slices, rows in ascending order, folded by the statistics' own tree; no floating-point atomics, so every number's bits
+ * depend on (n, r, m) alone in either mode of the handle and the call adds to scilmm_timing.n_float_atomic_launches only
+ * what its forward sweep adds.  The pairs' partial sums live in the statistics' buffer: nothing is allocated per block.
+ * Everything is enqueued on the handle's stream without synchronising; scilmm_scan_timing counts the expansion into ms[0]
+ * and the cross products into ms[2], scilmm_gxe_timing reports the two alone.  SCILMM_ERR_ARG before anything of the handle
+ * is read: a null d_E, m outside 1 .. 3, r outside 1 .. 128 / d, and everything the plain entry point of the form rejects;
+ * refusals as for the half-solves (a distributed handle, fp32-product fronts, a factor consumed by the selected inverse).
+ * scilmm_amd.InteractionScan (AssociationScan.interaction) is the interface.  No counterpart in the reference. */
+int scilmm_scan_block_gxe_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_E, int32_t m,
+                              const double* d_Q, int32_t q, double* d_stats);
+int scilmm_scan_block_bed_gxe_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                                  int32_t flags, int32_t r, const double* d_E, int32_t m, const double* d_Q, int32_t q,
+                                  double* d_stats);
+int scilmm_scan_block_dosage_gxe_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                     const int32_t* d_sample, int32_t r, const double* d_E, int32_t m, const double* d_Q, int32_t q,
+                                     double* d_stats);
+
 /* HIP-event times of the last scilmm_scan_block_dev on the handle, in milliseconds, valid after the scilmm_sync that follows
  * it: ms[0] moments + dequantise (+ permute), ms[1] forward sweep, ms[2] statistics (tools/assoc_timing.py). */
 int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);
+
+/* The two kernels a gxe block adds, of the last scan block on the handle, in milliseconds, valid after the scilmm_sync that
+ * follows it: ms[0] k_scan_expand (part of scilmm_scan_timing's ms[0]), ms[1] k_scan_cross and its fold (part of its ms[2]);
+ * zeros after a block that was no gxe block (tools/gxe_timing.py). */
+int scilmm_gxe_timing(const scilmm_symbolic* sym, double* ms);
 
 /* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
  * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y

@@ -15,6 +15,7 @@ convention here is the same F(1, n - 1).
     out = scan(genotypes)          # m x n int8, marker-major; dict of length-m arrays
     out = scan.scan_bed("cohort", sample_index=idx)   # PLINK 1 .bed / .bim / .fam, 2-bit genotypes decoded on the device
     out = scan.scan_dosages(ds, sample_index=idx)     # imputed dosages: m x N uint16 codes or float32 (scilmm_amd.dosage)
+    gxe = scan.interaction(env)    # marker x environment interaction on the same factor and whitening (scilmm_amd.gxe)
 
 There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
 """
@@ -87,6 +88,7 @@ class WhitenedModel(object):
         if y.size != n:
             raise ValueError("y has %d entries, the matrices %d rows" % (y.size, n))
         self._s2 = np.array(sigma2, dtype=np.float64)
+        self.covariates = covariates
         # Q = L^-1 P [C | y]: one forward sweep, kept in HBM in the permuted order the scan kernels read
         perm = torch.from_numpy(fac.P()).cuda()
         dB = torch.from_numpy(np.ascontiguousarray(np.hstack([covariates, y[:, None]]))).cuda()[perm].contiguous()
@@ -103,14 +105,17 @@ class WhitenedModel(object):
             raise _lib.ScilmmError("the resident factor no longer holds the sigma2 this object was whitened with: build a new "
                                    "%s" % type(self).__name__)
 
-    def _stats_buffer(self, nrows, m):
-        """Device buffer for the ``nrows`` statistics of ``m`` columns: a row of ``nrows * block`` numbers per block."""
-        return self.torch.empty(((m + self.block - 1) // self.block, nrows * self.block), dtype=self.torch.float64, device="cuda")
+    def _stats_buffer(self, nrows, m, blk=None):
+        """Device buffer for the ``nrows`` statistics of ``m`` columns: a row of ``nrows * blk`` numbers per block of ``blk``
+        columns (default: ``block``)."""
+        blk = self.block if blk is None else blk
+        return self.torch.empty(((m + blk - 1) // blk, nrows * blk), dtype=self.torch.float64, device="cuda")
 
-    def _run_blocks(self, dS, out, enqueue):
+    def _run_blocks(self, dS, out, enqueue, blk=None):
         """Fills ``out`` (nrows x m, m columns staged on the device) through ``dS``: ``enqueue(k0, rb, stats_ptr)`` queues the
-        block of columns k0 .. k0 + rb - 1; every block is queued, then one wait and one device-to-host copy."""
-        (nrows, m), blk = out.shape, self.block
+        block of columns k0 .. k0 + rb - 1 (``blk`` columns per block, default ``block``); every block is queued, then one
+        wait and one device-to-host copy."""
+        (nrows, m), blk = out.shape, self.block if blk is None else blk
         for b, k0 in enumerate(range(0, m, blk)):
             enqueue(k0, min(blk, m - k0), C.c_void_p(dS.data_ptr() + 8 * b * nrows * blk))
         self.sym.sync()
@@ -132,23 +137,26 @@ class AssociationScan(WhitenedModel):
         super(AssociationScan, self).__init__(cholesky_func, mats, sigma2, covariates, y, block)
         self._f = stats.f(1, self.n - 1)
 
-    def _stats(self, src, rows, chunk_bytes):
-        """(q + 4) x m statistics of the markers ``rows`` (a slice or an index array) of the marker source ``src``
-        (``scilmm_amd.markers``), in chunks of whole blocks of at most ``chunk_bytes`` host bytes: a chunk is brought to the
-        device, its blocks are queued, one wait.  The buffers are allocated once, for the largest chunk."""
-        q, blk = self.q, self.block
+    def _stats(self, src, rows, chunk_bytes, nrows=None, blk=None, env=None):
+        """nrows x m statistics (default: the scan's q + 4) of the markers ``rows`` (a slice or an index array) of the marker
+        source ``src`` (``scilmm_amd.markers``), ``blk`` markers per device block (default ``block``), in chunks of whole
+        blocks of at most ``chunk_bytes`` host bytes: a chunk is brought to the device, its blocks are queued, one wait.  The
+        buffers are allocated once, for the largest chunk.  ``env``: the source's third twin (``scilmm_amd.gxe``)."""
+        nrows = self.q + 4 if nrows is None else nrows
+        blk = self.block if blk is None else blk
         run = isinstance(rows, slice)
         m = rows.stop - rows.start if run else rows.size
-        out = np.empty((q + 4, m))
+        out = np.empty((nrows, m))
         if m == 0:
             return out
         per = max(blk, min(m, max(1, chunk_bytes // src.row_bytes)) // blk * blk)
-        dS = self._stats_buffer(q + 4, min(per, m))
+        dS = self._stats_buffer(nrows, min(per, m), blk)
         src.stage(min(per, m))
+        enqueue = src.enqueue if env is None else (lambda k0, rb, pS: src.enqueue(k0, rb, pS, env=env))
         for j0 in range(0, m, per):
             mc = min(per, m - j0)
             src.load(slice(rows.start + j0, rows.start + j0 + mc) if run else rows[j0:j0 + mc])
-            self._run_blocks(dS, out[:, j0:j0 + mc], src.enqueue)
+            self._run_blocks(dS, out[:, j0:j0 + mc], enqueue, blk)
         return out
 
     def __call__(self, genotypes):
@@ -172,6 +180,12 @@ class AssociationScan(WhitenedModel):
             beta, se, chi2 = b / a, 1.0 / np.sqrt(a), b * b / a
         mean[n_obs == 0] = np.nan
         return {"beta": beta, "se": se, "chi2": chi2, "p": self._f.sf(chi2), "n_obs": n_obs.astype(np.int64), "mean": mean}
+
+    def interaction(self, env, require_main_effects=True):
+        """The marker x environment interaction scan next to this one: an ``InteractionScan`` (``scilmm_amd.gxe``) on this
+        scan's factor and whitening, for the n x m environment columns ``env``."""
+        from .gxe import InteractionScan
+        return InteractionScan(self, env, require_main_effects)
 
     def scan_bed(self, bed, sample_index=None, markers=None, count="A1", chunk_bytes=None):
         """The scan of ``__call__`` on the markers of a PLINK 1 fileset, decoded on the device: the packed rows are uploaded

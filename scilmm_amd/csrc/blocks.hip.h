@@ -1,8 +1,26 @@
 // The block calls on a resident factor (included by engine.hip only, behind sweep.hip.h; the entry points' argument checks
-// stay there): BlockCall, marker_block for the marker scan's input forms and their fills, rel_block and rows_block for the BLUP.
+// stay there): BlockCall, marker_block for the marker scan's input forms and their fills (with environment columns: the gxe
+// blocks), rel_block and rows_block for the BLUP.
 #pragma once
 
 namespace {
+
+// What makes a marker block a marker x environment block: m environment columns d_E (n x m row-major, PERMUTED order), r markers
+// of d = 1 + m terms each (column a r + c of the block = term a of marker c), the cross products' rows of the statistics.
+struct Gxe {
+  const double* d_E;
+  int32_t m, r;
+  double* d_cross;
+  int32_t pairs() const { return (m + 1) * m / 2; }
+  // before anything of the handle is read
+  static bool args_ok(const double* d_E, int32_t m, int32_t r) { return d_E && m >= 1 && m <= GXE_MMAX && r >= 1 && r <= RPMAX / (1 + m); }
+};
+
+using CrossKernel = void (*)(int32_t, int32_t, int32_t, const double*, double*);
+CrossKernel cross_kernel(int32_t d, int32_t r) {
+  if (r <= 32) return d == 2 ? k_scan_cross<2, 32> : d == 3 ? k_scan_cross<3, 32> : k_scan_cross<4, 32>;
+  return d == 2 ? k_scan_cross<2, 64> : k_scan_cross<3, 64>;  // (d = 4: r <= 32)
+}
 
 // One block of statistics (marker scan, relationship columns, caller rows).  The entry point checks its own arguments
 // beside args_ok, then: begin (the refusals and the one-off allocations), its own checks that need the device state, open
@@ -22,13 +40,14 @@ struct BlockCall {
 
   // the refusals, the slice partial sums (allocated on the first call on a handle, or for a wider q; nothing is allocated
   // per block afterwards), the events and the inverse permutation; `gram`: the partial tiles of X^T X as well (allocated on
-  // the first Gram block on a handle, for the widest block: never again)
-  int begin(int32_t q, const char* who, bool gram = false) {
+  // the first Gram block on a handle, for the widest block: never again); `pairs`: a gxe block's rows of cross products, which
+  // take the statistics' partial sums over once those are folded, and its two events
+  int begin(int32_t q, const char* who, bool gram = false, int32_t pairs = 0) {
     TRY(check_half(fac, who));
     TRY(begin_rhs(fac, who));
     D = (Dev*)sym->device;
     const int64_t nslice = ((int64_t)sym->S->n + SCAN_SLICE - 1) / SCAN_SLICE;
-    const size_t need = (size_t)nslice * (size_t)(q + 1) * RPMAX;
+    const size_t need = (size_t)nslice * (size_t)std::max(q + 1, pairs) * RPMAX;
     if (D->scan_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
     TRY(grow(sym, &D->scan_partial, &D->scan_partial_cap, need));
     if (gram) {
@@ -38,6 +57,8 @@ struct BlockCall {
     }
     if (!D->scan_ev[0])
       for (auto& e : D->scan_ev) HIPCHK(hipEventCreate(&e));
+    if (pairs > 0 && !D->gxe_ev[0])
+      for (auto& e : D->gxe_ev) HIPCHK(hipEventCreate(&e));
     return ensure_iperm(sym, D);
   }
 
@@ -53,8 +74,10 @@ struct BlockCall {
 
   // W holds the block (event 1 is recorded here): the forward sweep, then |x_c|^2 and Q^T x_c from one pass over X, in fixed
   // row slices folded in slice order, to d_out ((q + 1) x r).  With d_gram (begin was told so): X^T X (r x r) from a second
-  // pass over X on the matrix pipe, inside the statistics interval; without it the launches are the same as ever.
-  int finish(int32_t r, const double* d_Q, int32_t q, double* d_out, double* d_gram = nullptr) {
+  // pass over X on the matrix pipe, inside the statistics interval; without it the launches are the same as ever.  With gxe
+  // (begin was told its pairs; r = d * gxe->r columns): the cross products between the d columns of every marker, from a second
+  // pass over X and the same fold, to gxe->d_cross (pairs x gxe->r), inside the statistics interval as well.
+  int finish(int32_t r, const double* d_Q, int32_t q, double* d_out, double* d_gram = nullptr, const Gxe* gxe = nullptr) {
     const int32_t n = sym->S->n;
     hipStream_t s0 = D->stream;
     const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
@@ -71,8 +94,17 @@ struct BlockCall {
       hipLaunchKernelGGL(gram_kernel(g), dim3((unsigned)gs), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, D->gram_partial);
       hipLaunchKernelGGL(k_gram_fold, dim3((unsigned)ntile), dim3(GRAM_FOLD * 256), 0, s0, gs, ntile, (const double*)D->gram_partial, r, d_gram);
     }
+    if (gxe) {
+      const int32_t pairs = gxe->pairs();
+      HIPCHK(hipEventRecord(D->gxe_ev[1], s0));
+      hipLaunchKernelGGL(cross_kernel(gxe->m + 1, gxe->r), dim3((unsigned)nslice), dim3(256), 0, s0, n, gxe->r, sw->rp, (const double*)D->X,
+                         D->scan_partial);
+      hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)pairs), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, pairs - 1,
+                         gxe->r, gxe->d_cross);
+    }
     HIPCHK(hipEventRecord(D->scan_ev[3], s0));
     D->scan_pending = true;
+    D->gxe_pending = gxe != nullptr;
     if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
     HIPCHK(hipGetLastError());
     return SCILMM_OK;
@@ -82,13 +114,26 @@ struct BlockCall {
 // One block of markers, whatever their form.  `fill(D, n, rp)` launches the form's two kernels on D->stream: rows 0..2 of the
 // statistics (n_obs, mean, centred sum of squares) by a workgroup per marker, then W = P (g - mean), missing = 0, columns padded
 // to rp, each tile of individuals written straight to its permuted rows.  Rows 3..: |w(g)|^2 and Q^T w(g); with d_gram, X^T X.
+// With d_E (m environment columns; the plain and the Gram calls pass none and keep their launches): the block is d = 1 + m times
+// as wide, the fill writes its r columns and zeroes the rest, k_scan_expand multiplies them into the interaction columns, and
+// the statistics are (q + 1) x (d r) -- read as ((q + 1) d) x r -- followed by the d (d - 1) / 2 rows of cross products.
 template <class Fill>
-int marker_block(scilmm_factor* fac, const char* who, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram, Fill fill) {
+int marker_block(scilmm_factor* fac, const char* who, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram, Fill fill,
+                 const double* d_E = nullptr, int32_t m = 0) {
   BlockCall b(fac);
-  TRY(b.begin(q, who, d_gram != nullptr));
-  TRY(b.open(r, false));
-  fill(b.D, b.sym->S->n, b.sw->rp);
-  return b.finish(r, d_Q, q, d_stats + 3 * (int64_t)r, d_gram);
+  const int32_t d = 1 + m;
+  const Gxe gxe{d_E, m, r, d_stats + (3 + (int64_t)(q + 1) * d) * r};
+  TRY(b.begin(q, who, d_gram != nullptr, gxe.pairs()));
+  TRY(b.open(d * r, false));
+  scilmm_symbolic* sym = b.sym;
+  const int32_t n = sym->S->n;
+  fill(b.D, n, b.sw->rp);
+  if (d_E) {
+    HIPCHK(hipEventRecord(b.D->gxe_ev[0], b.D->stream));
+    hipLaunchKernelGGL(k_scan_expand<4>, dim3((unsigned)(((int64_t)n + GXE_ROWS - 1) / GXE_ROWS)), dim3(256), 0, b.D->stream, n, r, m, b.sw->rp,
+                       d_E, b.D->W);
+  }
+  return b.finish(d * r, d_Q, q, d_stats + 3 * (int64_t)r, d_gram, d_E ? &gxe : nullptr);
 }
 
 // The fills.  int8 rows: exact integer sums, no order to fix; packed PLINK rows: the same sums taken class by class; dosage rows

@@ -273,7 +273,7 @@ struct Dev {
   const int32_t* d_pat_rowcol = nullptr;
   int64_t n_float_atomic = 0;           // launches since the handle was created that sum with floating-point atomics
   // marker scan and BLUP blocks: slice partial sums of the statistics; inverse permutation (ensure_iperm: the blocks, IBD and dominance values)
-  double* scan_partial = nullptr;       // [slices][q + 1][RPMAX]
+  double* scan_partial = nullptr;       // [slices][q + 1][RPMAX]; after its fold, a gxe block's [slices][pairs][RPMAX]
   size_t scan_partial_cap = 0;          // doubles
   double* gram_partial = nullptr;       // [slices of GRAM_SLICE rows][GRAM_TILES][256]: partial tiles of X^T X (the first Gram block allocates it)
   size_t gram_partial_cap = 0;          // doubles
@@ -281,6 +281,9 @@ struct Dev {
   hipEvent_t scan_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin | W ready | forward sweep done | statistics done
   bool scan_pending = false;            // a scan block whose events have not been read yet (scilmm_sync)
   double scan_ms[3] = {0.0, 0.0, 0.0};  // the last block's moments + dequantise | forward sweep | statistics (scilmm_scan_timing)
+  hipEvent_t gxe_ev[2] = {nullptr, nullptr};  // a gxe block's: the form's fill done | k_scan_fold done (the first gxe block creates them)
+  bool gxe_pending = false;             // the pending scan block is a gxe block
+  double gxe_ms[2] = {0.0, 0.0};        // the last block's k_scan_expand | k_scan_cross + its fold; 0 after a plain block (scilmm_gxe_timing)
 };
 
 #define HIPCHK(call)                                                                                   \

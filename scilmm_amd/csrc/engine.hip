@@ -227,30 +227,33 @@ int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double*
 }
 
 // The marker scan's blocks, one checker per input form; `gram`: the entry point (`who`) hands X^T X back as well, to d_gram
-// (null from the others).  What needs no handle is checked first: with it wrong, nothing of the handle is read.
+// (null from the others); `d_E`, `m`: the gxe entry points' environment columns, which they have checked with r (null from the
+// others).  What needs no handle is checked first: with it wrong, nothing of the handle is read.
 static int scan_block(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q, double* d_stats,
-                      bool gram, double* d_gram, const char* who) {
+                      bool gram, double* d_gram, const char* who, const double* d_E = nullptr, int32_t m = 0) {
   if (!d_geno || (gram && !d_gram) || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_int8(d_geno, ld_geno, r, d_stats));
+  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_int8(d_geno, ld_geno, r, d_stats), d_E, m);
 }
 
 static int scan_block_bed(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample, int32_t flags,
-                          int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
+                          int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who,
+                          const double* d_E = nullptr, int32_t m = 0) {
   if (!d_bed || (gram && !d_gram) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) ||
       !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
     return SCILMM_ERR_ARG;
-  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_bed(d_bed, ld_bed, n_samples, d_sample, flags, r, d_stats));
+  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_bed(d_bed, ld_bed, n_samples, d_sample, flags, r, d_stats), d_E, m);
 }
 
 static int scan_block_dosage(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples, const int32_t* d_sample,
-                             int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who) {
+                             int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who,
+                             const double* d_E = nullptr, int32_t m = 0) {
   if (!d_dos || (gram && !d_gram) || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
       (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
       !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
     return SCILMM_ERR_ARG;
   return dtype == SCILMM_DOSAGE_U16
-             ? marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<uint16_t>(d_dos, ld, n_samples, d_sample, r, d_stats))
-             : marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<float>(d_dos, ld, n_samples, d_sample, r, d_stats));
+             ? marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<uint16_t>(d_dos, ld, n_samples, d_sample, r, d_stats), d_E, m)
+             : marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<float>(d_dos, ld, n_samples, d_sample, r, d_stats), d_E, m);
 }
 
 int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
@@ -281,6 +284,25 @@ int scilmm_scan_block_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t 
 int scilmm_scan_block_dosage_gram_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                       const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
   return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, true, d_gram, __func__);
+}
+
+int scilmm_scan_block_gxe_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_E, int32_t m,
+                              const double* d_Q, int32_t q, double* d_stats) {
+  if (!Gxe::args_ok(d_E, m, r)) return SCILMM_ERR_ARG;
+  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
+}
+
+int scilmm_scan_block_bed_gxe_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                                  int32_t flags, int32_t r, const double* d_E, int32_t m, const double* d_Q, int32_t q, double* d_stats) {
+  if (!Gxe::args_ok(d_E, m, r)) return SCILMM_ERR_ARG;
+  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
+}
+
+int scilmm_scan_block_dosage_gxe_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                     const int32_t* d_sample, int32_t r, const double* d_E, int32_t m, const double* d_Q, int32_t q,
+                                     double* d_stats) {
+  if (!Gxe::args_ok(d_E, m, r)) return SCILMM_ERR_ARG;
+  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
 }
 
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
@@ -453,6 +475,13 @@ int scilmm_sync(scilmm_symbolic* sym) {
     D->scan_ms[0] = a;
     D->scan_ms[1] = b;
     D->scan_ms[2] = c;
+    a = b = 0;
+    if (D->gxe_pending) {
+      HIPCHK(hipEventElapsedTime(&a, D->gxe_ev[0], D->scan_ev[1]));
+      HIPCHK(hipEventElapsedTime(&b, D->gxe_ev[1], D->scan_ev[3]));
+    }
+    D->gxe_ms[0] = a;
+    D->gxe_ms[1] = b;
     // (the queued copy behind the block's sweep has arrived)
     if (D->h_chain_err && *D->h_chain_err != 0) return report_chain_timeout(sym, D, " (scan block)");
   }
@@ -480,6 +509,13 @@ int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   const Dev* D = (const Dev*)sym->device;
   for (int i = 0; i < 3; ++i) ms[i] = D->scan_ms[i];
+  return SCILMM_OK;
+}
+
+int scilmm_gxe_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const Dev* D = (const Dev*)sym->device;
+  for (int i = 0; i < 2; ++i) ms[i] = D->gxe_ms[i];
   return SCILMM_OK;
 }
 

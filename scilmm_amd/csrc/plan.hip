@@ -36,6 +36,8 @@ void dev_free(void* p) {
   if (D->gram_partial) (void)hipFree(D->gram_partial);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->gxe_ev)
+    if (e) (void)hipEventDestroy(e);
   if (D->d_out) (void)hipFree(D->d_out);
   for (auto& e : D->ev)
     if (e) (void)hipEventDestroy(e);

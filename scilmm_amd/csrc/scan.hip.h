@@ -8,6 +8,9 @@
 // The first two have two siblings per input form, which write the same rows of the statistics and the same W:
 //   k_bed_moments / k_bed_dequant (bed.hip.h)           PLINK 1 2-bit rows       reads  r * ceil(N/4) bytes each
 //   k_dos_moments<T> / k_dos_dequant<T> (dosage.hip.h)  uint16 / float dosages   reads  r * N * sizeof(T) each (float moments twice)
+// A marker x environment block (scilmm_scan_block_gxe_dev; d = 1 + m columns per marker) adds two, for every input form:
+//   k_scan_expand  : W[:, a r + c] = W[:, c] E[:, a - 1] in place               reads  n * (r + m) * 8, writes n * m * r * 8
+//   k_scan_cross   : slice partial sums of x_a' x_b, a < b, per marker, from X   reads  n * d * r * 8; folded by k_scan_fold
 // No floating-point atomics: a marker's statistics are the same bits in every run and in either mode of the handle.
 //
 // Genotype layout: marker j = geno + j * ld, n int8 values in the ORIGINAL order of the individuals, negative = missing.
@@ -197,6 +200,82 @@ __global__ __launch_bounds__(SCAN_FOLD * RPMAX) void k_scan_fold(int64_t nslice,
 #pragma unroll
     for (int u = 1; u < SCAN_FOLD; ++u) t += red[u * RPMAX + c];
     out[(int64_t)k * r + c] = t;
+  }
+}
+
+// ---- marker x environment blocks (scilmm_scan_block_gxe_dev): d = 1 + m terms per marker, column a r + c = term a of marker c.
+
+constexpr int GXE_MMAX = 3;    // environment columns at most: d <= 4 terms, r <= RPMAX / d markers
+constexpr int GXE_ROWS = 64;   // rows of W per workgroup of k_scan_expand
+constexpr int GXE_PAIRS = (GXE_MMAX + 1) * GXE_MMAX / 2;
+
+// W[p][a r + c] = W[p][c] E[p][a - 1], a = 1..m, c < r: the interaction columns from the centred marker columns a form's
+// dequantise kernel has written (columns r..rp-1 hold its zeros: those past d r stay).  In place: columns < r are read,
+// columns >= r written, every entry by the lane that read its source.  Lanes run along the markers (r <= 64: one lane each),
+// a wave takes every fourth row of the workgroup's GXE_ROWS, U rows in flight; the row of E is the same for a whole wave
+// (scalar loads).  E is n x m row-major in the PERMUTED order, like W.
+template <int U>
+__global__ __launch_bounds__(256) void k_scan_expand(int32_t n, int32_t r, int32_t m, int32_t rp, const double* __restrict__ E,
+                                                     double* W) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t p0 = (int64_t)blockIdx.x * GXE_ROWS;
+  const int64_t p1 = min(p0 + GXE_ROWS, (int64_t)n);
+  if (lane >= r) return;
+  for (int64_t p = p0 + wv; p < p1; p += 4 * U) {
+    double x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) x[u] = p + 4 * u < p1 ? W[(p + 4 * u) * rp + lane] : 0.0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (p + 4 * u >= p1) break;
+      const double* e = E + (p + 4 * u) * m;
+      double* row = W + (p + 4 * u) * rp + lane;
+#pragma unroll
+      for (int a = 1; a <= GXE_MMAX; ++a)
+        if (a <= m) row[a * r] = x[u] * e[a - 1];
+    }
+  }
+}
+
+// partial[slice][k][c] = sum over the slice's rows of X[p][a r + c] X[p][b r + c], k = the index of the pair (a, b), a < b < D,
+// in lexicographic order: the cross products between the D columns of one marker, from a second pass over X where it lies.
+// The layout is k_scan_stats' with D (D - 1) / 2 rows in place of q + 1, so k_scan_fold folds it.  A slice is SCAN_SLICE
+// consecutive rows; the workgroup is 256 / CWX row groups of CWX markers (CWX = 32 when r <= 32: no idle half-waves), group g
+// takes rows g, g + G, .. of the slice in ascending order, and the groups are added in group order: the order of every sum
+// depends on (n, r, D) alone.  No atomics.
+template <int D, int CWX>
+__global__ __launch_bounds__(256) void k_scan_cross(int32_t n, int32_t r, int32_t rp, const double* __restrict__ X,
+                                                    double* __restrict__ partial) {
+  constexpr int NP = D * (D - 1) / 2, G = 256 / CWX;
+  __shared__ double red[G * NP * CWX];
+  const int tid = threadIdx.x, c = tid & (CWX - 1), g = tid / CWX;
+  const int64_t p0 = (int64_t)blockIdx.x * SCAN_SLICE;
+  const int64_t p1 = min(p0 + SCAN_SLICE, (int64_t)n);
+  const bool on = c < r;
+  double acc[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) acc[k] = 0.0;
+#pragma unroll 4
+  for (int64_t p = p0 + g; p < p1; p += G) {
+    double x[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) x[a] = on ? X[p * rp + a * r + c] : 0.0;
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = a + 1; b < D; ++b) acc[k++] += x[a] * x[b];
+  }
+#pragma unroll
+  for (int k = 0; k < NP; ++k) red[(g * NP + k) * CWX + c] = acc[k];
+  __syncthreads();
+  for (int i = tid; i < NP * CWX; i += 256) {
+    const int k = i / CWX, cc = i & (CWX - 1);
+    double s = red[k * CWX + cc];
+#pragma unroll
+    for (int u = 1; u < G; ++u) s += red[(u * NP + k) * CWX + cc];
+    if (cc < r) partial[((int64_t)blockIdx.x * NP + k) * RPMAX + cc] = s;
   }
 }
 

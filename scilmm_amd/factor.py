@@ -258,6 +258,13 @@ class Symbolic(object):
         check(lib().scilmm_scan_timing(self._h, ms), self._h)
         return tuple(ms)
 
+    def gxe_timing(self):
+        """(``k_scan_expand``, ``k_scan_cross`` + its fold) of the last scan block in ms, after ``sync()``: parts of the first
+        and the third interval of ``scan_timing``; zeros after a block that was no gxe block."""
+        ms = (C.c_double * 2)()
+        check(lib().scilmm_gxe_timing(self._h, ms), self._h)
+        return tuple(ms)
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -438,6 +445,21 @@ class Factor(object):
         """``scan_block_dosage_dev`` with the Gram matrix as a second output (``scilmm_scan_block_dosage_gram_dev``)."""
         check(lib().scilmm_scan_block_dosage_gram_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dQ_ptr, q,
                                                       dstats_ptr, dgram_ptr), self.sym._h)
+
+    def scan_block_gxe_dev(self, dG_ptr, ld, r, dE_ptr, m, dQ_ptr, q, dstats_ptr):
+        """``scan_block_dev`` for ``r`` markers with ``m`` environment columns each (``scilmm_scan_block_gxe_dev``; ``dE_ptr``:
+        n x m float64 in the permuted order of ``Q``; ``scilmm_amd.gxe.InteractionScan`` is the interface)."""
+        check(lib().scilmm_scan_block_gxe_dev(self._h, dG_ptr, ld, r, dE_ptr, m, dQ_ptr, q, dstats_ptr), self.sym._h)
+
+    def scan_block_bed_gxe_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dE_ptr, m, dQ_ptr, q, dstats_ptr):
+        """``scan_block_bed_dev`` with ``m`` environment columns (``scilmm_scan_block_bed_gxe_dev``)."""
+        check(lib().scilmm_scan_block_bed_gxe_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dE_ptr, m, dQ_ptr, q,
+                                                  dstats_ptr), self.sym._h)
+
+    def scan_block_dosage_gxe_dev(self, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dE_ptr, m, dQ_ptr, q, dstats_ptr):
+        """``scan_block_dosage_dev`` with ``m`` environment columns (``scilmm_scan_block_dosage_gxe_dev``)."""
+        check(lib().scilmm_scan_block_dosage_gxe_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dE_ptr, m, dQ_ptr, q,
+                                                     dstats_ptr), self.sym._h)
 
     def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
         """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host

@@ -4,7 +4,8 @@ input form.  A source has ``m`` (its markers), ``row_bytes`` (host bytes of one 
     stage(rows_max)            allocate the staging and device buffers for up to ``rows_max`` rows (once per scan)
     load(rows)                 bring marker rows -- a slice or an index array -- to device rows 0 .. k-1 and wait for them
     enqueue(k0, rb, pS, pK)    queue block (k0, rb) of the loaded rows: statistics to ``pS``; with ``pK`` the Gram matrix as well
-                               (the ``_gram_dev`` twin of the form's entry point)
+                               (the ``_gram_dev`` twin of the form's entry point); with ``env=(pE, m)`` the marker x environment
+                               block of ``m`` environment columns at ``pE`` (the ``_gxe_dev`` twin)
 
 Everything else -- chunks, blocks, the synchronisation, the host algebra -- is the callers' and does not depend on the form.
 """
@@ -38,14 +39,16 @@ class MarkerSource(object):
     def _map(self):
         return None if self.dI is None else vp(self.dI.data_ptr())
 
-    def _call(self, plain, gram, head, rb, pS, pK):
-        """Queue one block through the form's entry point (``plain``) or, with ``pK``, its Gram twin: ``head`` are the form's own
-        leading arguments, the rest is the same for every form."""
-        args = head + (rb, vp(self.model.dQ.data_ptr()), self.model.q, pS)
-        if pK is None:
-            plain(*args)
+    def _call(self, plain, gram, gxe, head, rb, pS, pK, env):
+        """Queue one block through the form's entry point (``plain``), with ``pK`` its Gram twin, or with ``env`` its gxe twin:
+        ``head`` are the form's own leading arguments, the rest is the same for every form."""
+        tail = (vp(self.model.dQ.data_ptr()), self.model.q, pS)
+        if env is not None:
+            gxe(*(head + (rb,) + tuple(env) + tail))
+        elif pK is None:
+            plain(*(head + (rb,) + tail))
         else:
-            gram(*args, pK)
+            gram(*(head + (rb,) + tail + (pK,)))
 
 
 class Int8Rows(MarkerSource):
@@ -65,9 +68,10 @@ class Int8Rows(MarkerSource):
         self.dG[:g.shape[0], :self.n].copy_(self.torch.from_numpy(g))
         self.torch.cuda.synchronize()
 
-    def enqueue(self, k0, rb, pS, pK=None):
+    def enqueue(self, k0, rb, pS, pK=None, env=None):
         f = self.model.factor
-        self._call(f.scan_block_dev, f.scan_block_gram_dev, (vp(self.dG.data_ptr() + k0 * self.ld), self.ld), rb, pS, pK)
+        self._call(f.scan_block_dev, f.scan_block_gram_dev, f.scan_block_gxe_dev, (vp(self.dG.data_ptr() + k0 * self.ld), self.ld),
+                   rb, pS, pK, env)
 
 
 class BedRows(MarkerSource):
@@ -99,10 +103,10 @@ class BedRows(MarkerSource):
         self.torch.cuda.synchronize()
         self.t_read, self.t_copy = self.t_read + t2 - t1, self.t_copy + time.perf_counter() - t2
 
-    def enqueue(self, k0, rb, pS, pK=None):
+    def enqueue(self, k0, rb, pS, pK=None, env=None):
         f, nb = self.model.factor, self.row_bytes
-        self._call(f.scan_block_bed_dev, f.scan_block_bed_gram_dev,
-                   (vp(self.dB.data_ptr() + k0 * nb), nb, self.bed.n_samples, self._map(), self.flag), rb, pS, pK)
+        self._call(f.scan_block_bed_dev, f.scan_block_bed_gram_dev, f.scan_block_bed_gxe_dev,
+                   (vp(self.dB.data_ptr() + k0 * nb), nb, self.bed.n_samples, self._map(), self.flag), rb, pS, pK, env)
 
 
 class DosageRows(MarkerSource):
@@ -127,7 +131,8 @@ class DosageRows(MarkerSource):
         self.dB[:k, :self.row_bytes].copy_(self.hB[:k], non_blocking=True)
         self.torch.cuda.synchronize()
 
-    def enqueue(self, k0, rb, pS, pK=None):
+    def enqueue(self, k0, rb, pS, pK=None, env=None):
         f = self.model.factor
-        self._call(f.scan_block_dosage_dev, f.scan_block_dosage_gram_dev, (vp(self.dB.data_ptr() + k0 * self.ldb), self.dtype,
-                   self.ldb // self.d.dtype.itemsize, self.d.shape[1], self._map()), rb, pS, pK)
+        self._call(f.scan_block_dosage_dev, f.scan_block_dosage_gram_dev, f.scan_block_dosage_gxe_dev,
+                   (vp(self.dB.data_ptr() + k0 * self.ldb), self.dtype, self.ldb // self.d.dtype.itemsize, self.d.shape[1], self._map()),
+                   rb, pS, pK, env)
