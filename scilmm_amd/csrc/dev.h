@@ -56,8 +56,11 @@ struct Tuning {
   int64_t push_slice = 512;            // SCILMM_PUSH_SLICE      rows per slice of a long backward push group (>= 256)
   // -- read per call (the parity tests force each value on one handle)
   bool shadow = true;                  // SCILMM_SHADOW=0        run_factorize: k_dense32 instead of the fp32 shadow (k_dense_h)
-  int chain_wide_t = 256;              // SCILMM_CHAIN_WIDE_T    run_rhs: chains from this length on sweep 64-column windows
+  int chain_wide_t = 160;              // SCILMM_CHAIN_WIDE_T    run_rhs: chains from this length on sweep 64-column windows (pipelined pair loop)
   int chain_full_t = 768;              // SCILMM_CHAIN_FULL_T    run_rhs: ... and from this length on one 112-column window
+  bool chain_pipe = true;              // SCILMM_CHAIN_PIPE=0    run_rhs: k_chain's pair loop without the software pipeline
+  int chain_stagger = 0;               // SCILMM_CHAIN_STAGGER   run_rhs: a chain workgroup with more pairs than this first waits for
+                                       //                        its k-th-from-last pair (short chains reach the pipelined branch); 0: off
   bool sinv_generic = false;           // SCILMM_SINV_GENERIC=1  selected inverse: the gather kernel for the dense tail too
 };
 
@@ -99,6 +102,8 @@ inline Tuning read_tuning() {
   t.shadow = not0("SCILMM_SHADOW");
   if ((e = env("SCILMM_CHAIN_WIDE_T"))) t.chain_wide_t = atoi(e);
   if ((e = env("SCILMM_CHAIN_FULL_T"))) t.chain_full_t = atoi(e);
+  t.chain_pipe = not0("SCILMM_CHAIN_PIPE");
+  if ((e = env("SCILMM_CHAIN_STAGGER"))) t.chain_stagger = std::max(0, atoi(e));
   t.sinv_generic = is1("SCILMM_SINV_GENERIC");
   return t;
 }
@@ -248,6 +253,9 @@ struct Dev {
   ChainPair* d_cf = nullptr;
   int32_t* d_cb_ptr = nullptr;     // backward: pairs of chain descendant i (targets descending)
   ChainPair* d_cb = nullptr;
+  ChainDesc* d_cfd = nullptr;      // flat descriptors of the same pairs, in the same order (the pipelined pair loop)
+  ChainDesc* d_cbd = nullptr;
+  int64_t chain_desc_bytes = 0;    // ... and what they add to the plan
   int64_t* d_cg_ptr = nullptr;     // backward: pairs (chain target, non-chain descendant) grouped by descendant
   int32_t* d_cg_pairs = nullptr;
   int64_t chain_groups = 0;

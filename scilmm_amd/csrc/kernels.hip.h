@@ -17,6 +17,7 @@
 #define SCILMM_UPD_WAVES 2
 #endif
 #include <stdint.h>
+#include <type_traits>
 
 #include "plan_types.h"
 
@@ -2143,9 +2144,11 @@ __global__ __launch_bounds__(256) void k_pull_fold(DevSym S, const int32_t* __re
 // and publishes x_i through a flag (flag value = epoch of this launch, so flags are never reset).  The XCDs'
 // L2s are not coherent with each other, and device-scope fences (L2 write-back / invalidate) cost tens of
 // microseconds per step; instead only the communicated data is accessed coherently: x windows and flags are
-// written with agent-scope (write-through) stores and read with agent-scope (cache-bypassing) loads, the
+// written with agent-scope (write-through) stores, the flags are read with agent-scope (cache-bypassing) loads, the
 // producer drains its stores (s_waitcnt vmcnt(0)) before the barrier that precedes the flag store, and the
-// panels of L keep using ordinary cached loads.
+// panels of L keep using ordinary cached loads.  The x windows are read with ordinary cached loads as well: that is safe
+// because x of a block is NEVER requested on a CU before that block's flag has been seen there (no stale line can exist), and
+// a 128-byte line never holds x of two producers.  Every prefetch of the pipelined loop keeps to that rule.
 // A workgroup takes its chain position from an atomic TICKET drawn when it starts (not from blockIdx: HIP does not
 // promise a dispatch order across XCDs / priorities / concurrent kernels).  It only ever waits for positions with a
 // lower ticket, whose workgroups have therefore already started and cannot be starved by it: no co-residency
@@ -2196,16 +2199,24 @@ __device__ unsigned long long g_chain_prof[8 * 4096];  // per front (window 0, f
 // columns, one workgroup per CU) or 7 (112 columns: every fused right-hand side of an evaluation in ONE window) for long
 // chains, where every window re-reads the whole dense tail (1M config: 4 -> 1 passes over 127 GB per sweep) and the
 // fixed cost of a pair (flag, x window, two barriers) is spread over 2 - 3.5 times the MFMAs.
-template <bool MFMA, bool BWD, int NCTW>
+// PIPE (MFMA form, instantiated for the 64-column windows only: the other widths do not fit its registers without scratch):
+// the pair loop is software-pipelined over the pairs that are already final -- see the loop itself.
+// The sums are the same in the same order, so every x is bit-identical to the PIPE == false form (SCILMM_CHAIN_PIPE=0), which
+// stays compiled as the reference.  stagger (tuning only): a workgroup with more pairs than that first waits for its
+// stagger-th-from-last pair, so that short chains, too, meet a long final prefix followed by waiting pairs.
+template <bool MFMA, bool BWD, int NCTW, bool PIPE>
 __global__ __launch_bounds__(512, NCTW == 2 ? SCILMM_CHAIN_WAVES : 1) void k_chain(DevSym S, int32_t T, const int32_t* __restrict__ chain,
                                                const int32_t* __restrict__ pair_ptr, const ChainPair* __restrict__ pairs,
+                                               const ChainDesc* __restrict__ descs,
                                                const int32_t* __restrict__ colmap, const double* __restrict__ L,
                                                const double* __restrict__ invD, const double* W, double* X, int32_t rp,
-                                               int32_t ncw, int32_t* flags, int32_t epoch, int32_t* err, int32_t* ticket) {
+                                               int32_t ncw, int32_t* flags, int32_t epoch, int32_t* err, int32_t* ticket,
+                                               int32_t stagger) {
+  static_assert(MFMA || !PIPE, "k_chain: the scalar form has no pipelined loop");
   constexpr int CW = 16 * NCTW, LDW = NCTW == 2 ? 48 : NCTW == 4 ? 80 : 112, NCT = NCTW;  // (LDW == 16 mod 32, >= CW: shadows the file-wide window constants)
   static_assert(NCTW == 2 || NCTW == 4 || NCTW == 7, "k_chain: 32-, 64- or 112-column windows");
   __shared__ __attribute__((aligned(16))) double Ys[NB * LDW];  // x window of the other block, then w_i: [k][c]
-  __shared__ int s_ok, s_ready, s_ticket;
+  __shared__ int s_ok, s_ready, s_deep, s_ticket;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   if (tid == 0) s_ticket = atomicAdd(ticket, 1);  // chain position = order of ARRIVAL on the device
@@ -2225,7 +2236,7 @@ __global__ __launch_bounds__(512, NCTW == 2 ? SCILMM_CHAIN_WAVES : 1) void k_cha
   const int jrow = 16 * wv + li;  // A-operand row of this lane
   const int32_t e0 = pair_ptr[i], e1 = pair_ptr[i + 1];
   // ---- how many leading pairs are already final?  one parallel look at their flags instead of one round trip each
-  if (wv == 0) {
+  if (!PIPE && wv == 0) {
     int ready = 0;
     bool open = true;
     for (int32_t base = e0; base < e1 && open; base += 64) {
@@ -2274,7 +2285,7 @@ __global__ __launch_bounds__(512, NCTW == 2 ? SCILMM_CHAIN_WAVES : 1) void k_cha
 #pragma unroll
   for (int cn = 0; cn < NCT; ++cn) acc[cn] = (d4){0.0, 0.0, 0.0, 0.0};
   __syncthreads();
-  const int32_t nready = s_ready;
+  const int32_t nready = PIPE ? 0 : s_ready;
   bool ok = true;
   // L fragment of pair e -> registers (independent of every flag): issued one pair ahead of its use
   auto load_frag = [&](int32_t e, double (&av)[NK]) {
@@ -2392,13 +2403,237 @@ __global__ __launch_bounds__(512, NCTW == 2 ? SCILMM_CHAIN_WAVES : 1) void k_cha
     __syncthreads();  // Ys is reused by the next pair
     if (e == e1 - 1) CPROF(2);  // last pair multiplied
   };
+  constexpr bool HOP_EARLY = PIPE && NCTW == 4;  // inverse fragment and own rows before the wait for the newest block
   if (NCTW == 2 && e0 == e1) load_iv();
-  for (int32_t e = e0; e < e1 && ok; ++e) {
-    double av[NK];
-    load_frag(e, av);
-    consume(e, av);
+  if constexpr (!PIPE) {
+    for (int32_t e = e0; e < e1 && ok; ++e) {
+      double av[NK];
+      load_frag(e, av);
+      consume(e, av);
+    }
+  } else if (e0 < e1) {
+    // ---- the pipelined pair loop:  look -> run -> wait -> look again.
+    // look: wave 0's ballot over the flags from the current pair on = length of the final prefix (again whenever it is used up:
+    //   after a wait several blocks have usually become final).
+    // run (>= 2 final pairs that are NB deep, so that the products need no k test): the fragment of pair e + 1 is issued before the products of pair e (two register sets, unrolled by
+    //   two), its x window is requested into registers after the barrier that publishes pair e's window and written to Ys after
+    //   the barrier that ends pair e.  The run body is straight-line code: every load is unconditional (clamped address, masked
+    //   where it is used) so that the waits for memory count only the loads in front of the one that is needed.
+    // wait (the next pair is not final): chain_wait, then the x window, then the product; the fragment of the pair, which depends
+    //   on no flag, is in registers already.  The last pair of the list always takes this path: the hop happens there.
+    // x of a block that is not final is never requested (the rule of the header comment).
+    // 112 columns: accumulators, two fragment sets and the x window do not fit 256 registers; there the one set is refilled as
+    // soon as the products of the pair have read it, and only the x window is fetched ahead
+    constexpr bool PF_FRAG = NCTW != 7;
+    const int32_t e1u = uniform_int(e1);
+    int32_t e = uniform_int(e0);
+    int32_t fin = e;  // pairs in front of fin are known to be final
+    auto ldesc = [&](int32_t q) __attribute__((always_inline)) { return descs[min(q, e1u - 1)]; };
+    constexpr int XL = NCTW == 2 ? 32 : 64, XR = 512 / XL, XU = NB / XR, XP = (CW + XL - 1) / XL;
+    const int xc = tid & (XL - 1), xk = tid / XL;
+    const int64_t rowbase = BWD ? S.sn_rowptr[s] : 0;
+    double xv[XP][XU];
+    // One LDS base per lane and compile-time offsets, the k mask as lk against a scalar: no per-k-step registers.  The base
+    // passes through an empty asm statement at every use, or the compiler computes all the addresses once, in front of the
+    // loop, and spills them.
+    auto opaque = [](int v) __attribute__((always_inline)) {
+      __asm__ volatile("" : "+v"(v));
+      return v;
+    };
+    // x window of a FINAL pair -> registers, all rows requested before the first is used
+    auto xload = [&](int32_t xrow, int32_t nx, int32_t jp0, int32_t map) __attribute__((always_inline)) {
+      if (BWD && jp0 < 0) {  // (uniform; the x loads are repeated in both branches so that as many are in flight behind either)
+        const int32_t* rows = S.sn_rows + (rowbase + map);
+#pragma unroll
+        for (int p = 0; p < XP; ++p)
+#pragma unroll
+          for (int u = 0; u < XU; ++u) {
+            const int kc = max(min(xk + XR * u, nx - 1), 0), cc = XL * p + xc;
+            xv[p][u] = X[(int64_t)rows[kc] * rp + c_lo + (cc < rpl ? cc : 0)];
+          }
+      } else {
+        const double* Xb = X + uniform_i64((int64_t)xrow * rp + c_lo);
+#pragma unroll
+        for (int p = 0; p < XP; ++p)
+#pragma unroll
+          for (int u = 0; u < XU; ++u) {
+            const int kc = max(min(xk + XR * u, nx - 1), 0), cc = XL * p + xc;
+            xv[p][u] = ld_off(Xb, (uint32_t)(kc * rp + (cc < rpl ? cc : 0)) * 8u);
+          }
+      }
+    };
+    auto xwrite = [&](int32_t nx) __attribute__((always_inline)) {
+      const int kn = (nx + 3) & ~3;
+      double* Yw = Ys + opaque(xk * LDW + xc);
+#pragma unroll
+      for (int p = 0; p < XP; ++p)
+#pragma unroll
+        for (int u = 0; u < XU; ++u) {
+          const int k = xk + XR * u, cc = XL * p + xc;
+          if (cc < CW && k < kn) Yw[XR * u * LDW + XL * p] = (k < nx && cc < rpl) ? xv[p][u] : 0.0;
+        }
+    };
+    // fragment of a pair -> one register set (qm: the pair's entry of the column map for this lane's row, forward)
+    auto frag = [&](const ChainDesc& d, int32_t qm, double (&av)[NK], bool& rowok) __attribute__((always_inline)) {
+      const int klast = max(((d.depth + 3) & ~3) - 4, 0);
+      const double* P = L + d.loff;
+      if (!BWD) {
+        const int q = d.jp0 < 0 ? qm : jrow - d.jp0;
+        rowok = q >= 0 && q < d.nq;
+        const uint32_t voff = (uint32_t)(lk * d.ld + (rowok ? q : 0));
+#pragma unroll
+        for (int u = 0; u < NK; ++u) av[u] = ld_off(P + (int64_t)min(4 * u, klast) * d.ld, voff * 8u);
+      } else {
+        rowok = jrow < w;
+        const uint32_t voff = (uint32_t)((rowok ? jrow : 0) * d.ld + lk);
+#pragma unroll
+        for (int u = 0; u < NK; ++u) av[u] = ld_off(P + min(4 * u, klast), voff * 8u);
+      }
+    };
+    auto cmap = [&](const ChainDesc& d) __attribute__((always_inline)) { return BWD ? 0 : colmap[d.map + jrow]; };  // (contiguous pairs: map == 0, not used)
+    const int ncnu = uniform_int(ncn);
+    auto mult = [&](const ChainDesc& d, double (&av)[NK], bool rowok) __attribute__((always_inline)) {
+      const int kn = (d.depth + 3) & ~3, kvalid = d.depth;
+      const double* Yb = Ys + opaque(lk * LDW + li);
+      if (kvalid == NB && ncnu == NCT) {  // a full pair in a full window: no test between the products, the reads of Ys run ahead
+#pragma unroll
+        for (int u = 0; u < NK; ++u)
+#pragma unroll
+          for (int cn = 0; cn < NCT; ++cn) acc[cn] = mfma_f64(rowok ? av[u] : 0.0, Yb[4 * u * LDW + 16 * cn], acc[cn]);
+      } else {
+        const int lko = opaque(lk);
+#pragma unroll
+        for (int u = 0; u < NK; ++u)
+          if (4 * u < kn) {
+#pragma unroll
+            for (int cn = 0; cn < NCT; ++cn)
+              if (cn < ncnu) acc[cn] = mfma_f64((rowok && 4 * u + lko < kvalid) ? av[u] : 0.0, Yb[4 * u * LDW + 16 * cn], acc[cn]);
+          }
+      }
+    };
+    if (stagger > 0 && e1u - e > stagger) {
+      if (tid == 0) s_ok = chain_wait(flags + (int64_t)ldesc(e1u - 1 - stagger).other * ncw + c, epoch, err, stagger) ? 1 : 0;
+      __syncthreads();
+      ok = uniform_int(s_ok) != 0;  // (uniform for the compiler too: the loop below must not become divergent control flow)
+    }
+    ChainDesc d0 = ldesc(e), d1 = ldesc(e + 1), d2 = ldesc(e + 2), d3;
+    double avA[NK], avB[NK];
+    bool rokA, rokB = false;
+    int32_t qm1 = cmap(d1), qm2;
+    frag(d0, cmap(d0), avA, rokA);
+    // one pair of a run: cur holds the fragment of pair e, the x window of pair e is in xv; `more`: pair e + 1 belongs to the run
+    auto run_step = [&](double (&cur)[NK], bool& rokc, double (&nxt)[NK], bool& rokn, bool more) __attribute__((always_inline)) {
+      d3 = ldesc(e + 3);
+      qm2 = cmap(d2);
+      if (PF_FRAG) frag(d1, qm1, nxt, rokn);
+      __builtin_amdgcn_sched_barrier(0);
+      xwrite(d0.depth);
+      __syncthreads();
+      // (the last pair of the run requests its own window again: pair e + 1 may not be final)
+      xload(more ? d1.xrow : d0.xrow, more ? d1.depth : d0.depth, more ? d1.jp0 : d0.jp0, more ? d1.map : d0.map);
+      __builtin_amdgcn_sched_barrier(0);
+      {  // (every pair of a run is NB deep; all column tiles: those past the last column multiply the zeros xwrite left there)
+        const double* Yb = Ys + opaque(lk * LDW + li);
+#pragma unroll
+        for (int u = 0; u < NK; ++u)
+#pragma unroll
+          for (int cn = 0; cn < NCT; ++cn) acc[cn] = mfma_f64(rokc ? cur[u] : 0.0, Yb[4 * u * LDW + 16 * cn], acc[cn]);
+      }
+      if (!PF_FRAG) {  // (one register set: as soon as the products have read it, and not before)
+        __builtin_amdgcn_sched_barrier(0);
+        frag(d1, qm1, cur, rokc);
+      }
+      __syncthreads();  // Ys is reused by the next pair
+      d0 = d1, d1 = d2, d2 = d3, qm1 = qm2;
+      ++e;
+    };
+    // one pair on its own: waits for it unless it is known to be final; last: the hop (cur holds its fragment, nothing is fetched ahead)
+    auto single = [&](bool last) __attribute__((always_inline)) {
+      if (!last) {
+        d3 = ldesc(e + 3);
+        qm2 = cmap(d2);
+        if (PF_FRAG) frag(d1, qm1, avB, rokB);
+      } else {
+        if (NCTW == 2 || HOP_EARLY) load_iv();
+        if (HOP_EARLY) load_yv();
+      }
+      if (e >= fin) {
+        if (tid == 0) s_ok = chain_wait(flags + (int64_t)d0.other * ncw + c, epoch, err, e1u - 1 - e) ? 1 : 0;
+        __syncthreads();
+        ok = uniform_int(s_ok) != 0;
+      }
+      if (last) CPROF(0);  // flag of the newest block observed (or known from the last look)
+      if (ok) {
+        xload(d0.xrow, d0.depth, d0.jp0, d0.map);
+        xwrite(d0.depth);
+      }
+      __syncthreads();
+      if (last) CPROF(1);  // x window staged
+      if (ok) mult(d0, avA, rokA);
+      if (!last && !PF_FRAG) {
+        __builtin_amdgcn_sched_barrier(0);
+        frag(d1, qm1, avA, rokA);
+      }
+      __syncthreads();  // Ys is reused by the next pair
+      if (last) CPROF(2);  // last pair multiplied
+      if (!last) {
+        if (PF_FRAG) {
+#pragma unroll
+          for (int u = 0; u < NK; ++u) avA[u] = avB[u];
+          rokA = rokB;
+        }
+        d0 = d1, d1 = d2, d2 = d3, qm1 = qm2;
+      }
+      ++e;
+    };
+    int32_t runfin = e;  // ... and in front of runfin also NB deep: the pairs a run takes (its products have no k test)
+    while (e < e1u - 1 && ok) {
+      if (e >= runfin) {
+        if (wv == 0) {
+          int ready = 0, deep = 0;
+          bool open = true, opend = true;
+          for (int32_t base = e; base < e1u && open; base += 64) {
+            bool r = false, d = false;
+            if (base + lane < e1u) {
+              r = __hip_atomic_load(flags + (int64_t)descs[base + lane].other * ncw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= epoch;
+              d = r && descs[base + lane].depth == NB;
+            }
+            const unsigned long long b = __ballot(r), bd = __ballot(d);
+            const int lead = (~b == 0ull) ? 64 : __builtin_ctzll(~b);
+            const int leadd = (~bd == 0ull) ? 64 : __builtin_ctzll(~bd);
+            ready += lead;
+            if (opend) deep += leadd;
+            open = lead == 64;
+            opend = opend && leadd == 64;
+          }
+          if (lane == 0) s_ready = ready, s_deep = deep;
+        }
+        __syncthreads();
+        fin = e + uniform_int(s_ready);
+        runfin = e + uniform_int(s_deep);
+      }
+      const int32_t run_end = e + ((min(runfin, e1u - 1) - e) & ~1);  // an even number of pairs: the next fragment ends up in set A
+      if (e < run_end) {
+        xload(d0.xrow, d0.depth, d0.jp0, d0.map);
+        while (e < run_end) {
+          if (PF_FRAG) {
+            run_step(avA, rokA, avB, rokB, true);
+            run_step(avB, rokB, avA, rokA, e + 1 < run_end);
+          } else {
+            run_step(avA, rokA, avA, rokA, true);
+            run_step(avA, rokA, avA, rokA, e + 1 < run_end);
+          }
+        }
+      } else {
+        single(false);
+      }
+    }
+    if (ok) single(true);
+  } else if (HOP_EARLY) {
+    load_iv();
+    load_yv();
   }
-  if (NCTW != 2) {
+  if (NCTW != 2 && !HOP_EARLY) {
     load_iv();
     load_yv();
   }
@@ -2418,7 +2653,29 @@ __global__ __launch_bounds__(512, NCTW == 2 ? SCILMM_CHAIN_WAVES : 1) void k_cha
     d4 xa[NCT];
 #pragma unroll
     for (int cn = 0; cn < NCT; ++cn) xa[cn] = (d4){0.0, 0.0, 0.0, 0.0};
-    if (MFMA) {
+    if (MFMA && w == NB && uniform_int(ncn) == NCT) {
+      // A full block in a full window: the k range of each wave is a compile-time constant (one straight-line body per wave,
+      // chosen by a scalar branch).
+      // The same products in the same order as the tested form below, without its copies of the accumulators between tests.
+      const double* Yd = Ys + lk * LDW + li;
+      auto diag_wave = [&](auto WV) __attribute__((always_inline)) {
+        constexpr int u0 = BWD ? 4 * decltype(WV)::value : 0, u1 = BWD ? NK : 4 * (decltype(WV)::value + 1);
+#pragma unroll
+        for (int u = u0; u < u1; ++u)
+#pragma unroll
+          for (int cn = 0; cn < NCT; ++cn) xa[cn] = mfma_f64(iv[u], Yd[4 * u * LDW + 16 * cn], xa[cn]);
+      };
+      switch (uniform_int(wv)) {
+        case 0: diag_wave(std::integral_constant<int, 0>{}); break;
+        case 1: diag_wave(std::integral_constant<int, 1>{}); break;
+        case 2: diag_wave(std::integral_constant<int, 2>{}); break;
+        case 3: diag_wave(std::integral_constant<int, 3>{}); break;
+        case 4: diag_wave(std::integral_constant<int, 4>{}); break;
+        case 5: diag_wave(std::integral_constant<int, 5>{}); break;
+        case 6: diag_wave(std::integral_constant<int, 6>{}); break;
+        default: diag_wave(std::integral_constant<int, 7>{}); break;
+      }
+    } else if (MFMA) {
 #pragma unroll
       for (int u = 0; u < NK; ++u)
         if (4 * u >= kbeg && 4 * u < kend) {

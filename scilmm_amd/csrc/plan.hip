@@ -1679,9 +1679,32 @@ int plan_chain(scilmm_symbolic* sym, Dev* D, PlanBuild& pb) {
       if (gslot.empty()) gslot.push_back(-1);
     }
     D->chain_groups = (int64_t)gptr.size() - 1;
+    // the flat descriptors of the pipelined pair loop, pair for pair beside fl / bl
+    std::vector<ChainDesc> fd(fl.size()), bd(bl.size());
+    for (int32_t i = 0; i < T; ++i) {
+      const int32_t s = chain[i];
+      const int32_t ms = (int32_t)(S.sn_rowptr[s + 1] - S.sn_rowptr[s]);
+      for (int32_t e = fptr[i]; e < fptr[i + 1]; ++e) {
+        const ChainPair& p = fl[(size_t)e];
+        const int32_t so = chain[p.other];
+        fd[(size_t)e] = ChainDesc{S.sn_loff[so] + p.p0, (int32_t)(S.sn_rowptr[so + 1] - S.sn_rowptr[so]), S.sn_start[so + 1] - S.sn_start[so],
+                                  S.sn_start[so], p.other, p.map, (int16_t)p.jp0, (int16_t)p.nq};
+      }
+      for (int32_t e = bptr[i]; e < bptr[i + 1]; ++e) {
+        const ChainPair& p = bl[(size_t)e];
+        const int32_t so = chain[p.other];
+        bd[(size_t)e] = ChainDesc{S.sn_loff[s] + p.p0, ms, p.nq, S.sn_start[so] + std::max(p.jp0, 0), p.other, p.p0, (int16_t)p.jp0, (int16_t)p.nq};
+      }
+    }
+    D->chain_desc_bytes = (int64_t)(fd.size() + bd.size()) * (int64_t)sizeof(ChainDesc);
     if (fl.empty()) fl.push_back(ChainPair{0, 0, 0, 0, 0});
     if (bl.empty()) bl.push_back(ChainPair{0, 0, 0, 0, 0});
-    if (colmap.empty()) colmap.push_back(-1);
+    if (fd.empty()) fd.push_back(ChainDesc{0, 0, 0, 0, 0, 0, 0, 0});
+    if (bd.empty()) bd.push_back(ChainDesc{0, 0, 0, 0, 0, 0, 0, 0});
+    const long long n_colmaps = (long long)(colmap.size() / NB);
+    colmap.resize(std::max(colmap.size(), (size_t)NB), -1);  // (the pipelined loop reads colmap[map + column] of contiguous pairs too)
+    if ((st = upload(sym, D, fd, &D->d_cfd)) != SCILMM_OK) return st;
+    if ((st = upload(sym, D, bd, &D->d_cbd)) != SCILMM_OK) return st;
     if ((st = upload(sym, D, colmap, &D->d_colmap)) != SCILMM_OK) return st;
     if (gpairs.empty()) gpairs.assign(3, 0);
     const int64_t n_ranges = (int64_t)gpairs.size() / 3;
@@ -1700,8 +1723,8 @@ int plan_chain(scilmm_symbolic* sym, Dev* D, PlanBuild& pb) {
     HIPCHK(hipHostMalloc((void**)&D->h_chain_err, sizeof(int32_t), hipHostMallocDefault));
     *D->h_chain_err = 0;
     if (pb.verbose)
-      fprintf(stderr, "[scilmm plan] chain sweep: %d fronts (levels %d..%d), %lld inner pairs (%lld column maps), %lld outside pairs in %lld groups\n",
-              T, l0, S.nlevels - 1, (long long)fl.size(), (long long)(colmap.size() / NB), (long long)outside.size(), (long long)D->chain_groups);
+      fprintf(stderr, "[scilmm plan] chain sweep: %d fronts (levels %d..%d), %lld inner pairs (%lld column maps, %lld descriptor bytes), %lld outside pairs in %lld groups\n",
+              T, l0, S.nlevels - 1, (long long)fl.size(), n_colmaps, (long long)D->chain_desc_bytes, (long long)outside.size(), (long long)D->chain_groups);
     (void)n_ranges;
   }
   return SCILMM_OK;

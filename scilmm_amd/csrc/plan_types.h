@@ -99,6 +99,19 @@ struct ChainPair {
   int32_t map;    // jp0 < 0, forward: offset into the column -> row map (NB entries, -1 = no such row)
 };
 
+// k_chain, pipelined pair loop: everything about a pair that the kernel otherwise derives by chasing chain[] and the symbolic
+// arrays, in one aligned record (two scalar loads), in the order of the ChainPair list beside it
+struct alignas(32) ChainDesc {
+  int64_t loff;   // element offset of the fragment's first entry: sn_loff[descendant] + p0
+  int32_t ld;     // leading dimension of the descendant panel (rows)
+  int32_t depth;  // depth of the product: width of the descendant (forward), nq (backward)
+  int32_t xrow;   // first x row: first column of the descendant (forward), of the target + jp0 (backward, jp0 >= 0)
+  int32_t other;  // as ChainPair::other
+  int32_t map;    // jp0 < 0: forward, offset into the column -> row map; backward, p0 (the x rows are sn_rows[rowptr + p0 + k])
+  int16_t jp0, nq;  // as ChainPair
+};
+static_assert(sizeof(ChainDesc) == 32, "ChainDesc: one 32-byte record per pair");
+
 // selected inverse
 struct SinvOwner {  // where the entries Z(., lo) with lo in one front live
   int64_t loff;       // panel offset

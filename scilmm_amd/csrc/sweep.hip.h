@@ -30,7 +30,8 @@ struct Sweep : SweepLaunch {
   scilmm_symbolic* const sym;
   const Symbolic& S;
   int64_t tot = 0;  // doubles of the block: n * rp
-  int chain_wide_T = 0, chain_full_T = 0;
+  int chain_wide_T = 0, chain_full_T = 0, chain_stagger = 0;
+  bool chain_pipe = true;
   bool mid_recorded = false;
 
   Sweep(scilmm_factor* f, Dev* d) : SweepLaunch{d, f, d->stream}, sym(f->sym), S(*f->sym->S) {}
@@ -45,6 +46,8 @@ struct Sweep : SweepLaunch {
     const Tuning tune = read_tuning();
     chain_wide_T = tune.chain_wide_t;
     chain_full_T = tune.chain_full_t;
+    chain_pipe = tune.chain_pipe;
+    chain_stagger = tune.chain_stagger;
   }
 
   // the event between the forward and the backward half (of the call's first block)
@@ -65,15 +68,28 @@ struct Sweep : SweepLaunch {
     HIPCHK(hipMemsetAsync(D->d_chain_err + 2, 0, sizeof(int32_t), st));
     const int32_t* cptr = bwd ? (const int32_t*)D->d_cb_ptr : (const int32_t*)D->d_cf_ptr;
     const ChainPair* cpairs = bwd ? (const ChainPair*)D->d_cb : (const ChainPair*)D->d_cf;
-#define SCILMM_CHAIN_LAUNCH(MF, BW, NC)                                                                                                  \
-  hipLaunchKernelGGL((k_chain<MF, BW, NC>), dim3(grid), dim3(512), 0, st, D->v, D->chain_T, (const int32_t*)D->d_chain, cptr, cpairs, \
-                     (const int32_t*)D->d_colmap, (const double*)fac->L, (const double*)fac->invD, (const double*)D->W, D->X, rp, gyc,  \
-                     D->d_chain_flags, ep, D->d_chain_err, D->d_chain_err + 2)
+    const ChainDesc* cdesc = bwd ? (const ChainDesc*)D->d_cbd : (const ChainDesc*)D->d_cfd;
+#define SCILMM_CHAIN_LAUNCH(MF, BW, NC, PP)                                                                                                  \
+  hipLaunchKernelGGL((k_chain<MF, BW, NC, PP>), dim3(grid), dim3(512), 0, st, D->v, D->chain_T, (const int32_t*)D->d_chain, cptr, cpairs,   \
+                     cdesc, (const int32_t*)D->d_colmap, (const double*)fac->L, (const double*)fac->invD, (const double*)D->W, D->X, rp, gyc, \
+                     D->d_chain_flags, ep, D->d_chain_err, D->d_chain_err + 2, (int32_t)chain_stagger)
+    // (the pipelined pair loop exists in the 64-column form only: two fragment sets and the x window fit its 256 registers,
+    //  not those of the 112-column accumulators; the 32-column chains are bound by the hop)
+    const bool pipe = chain_pipe && wide && !full;
     if (mf) {
-      if (bwd) { if (full) SCILMM_CHAIN_LAUNCH(true, true, 7); else if (wide) SCILMM_CHAIN_LAUNCH(true, true, 4); else SCILMM_CHAIN_LAUNCH(true, true, 2); }
-      else { if (full) SCILMM_CHAIN_LAUNCH(true, false, 7); else if (wide) SCILMM_CHAIN_LAUNCH(true, false, 4); else SCILMM_CHAIN_LAUNCH(true, false, 2); }
+      if (bwd) {
+        if (full) SCILMM_CHAIN_LAUNCH(true, true, 7, false);
+        else if (pipe) SCILMM_CHAIN_LAUNCH(true, true, 4, true);
+        else if (wide) SCILMM_CHAIN_LAUNCH(true, true, 4, false);
+        else SCILMM_CHAIN_LAUNCH(true, true, 2, false);
+      } else {
+        if (full) SCILMM_CHAIN_LAUNCH(true, false, 7, false);
+        else if (pipe) SCILMM_CHAIN_LAUNCH(true, false, 4, true);
+        else if (wide) SCILMM_CHAIN_LAUNCH(true, false, 4, false);
+        else SCILMM_CHAIN_LAUNCH(true, false, 2, false);
+      }
     } else {
-      if (bwd) SCILMM_CHAIN_LAUNCH(false, true, 2); else SCILMM_CHAIN_LAUNCH(false, false, 2);
+      if (bwd) SCILMM_CHAIN_LAUNCH(false, true, 2, false); else SCILMM_CHAIN_LAUNCH(false, false, 2, false);
     }
 #undef SCILMM_CHAIN_LAUNCH
     return SCILMM_OK;
