@@ -341,6 +341,33 @@ int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms);
  * zeros after a block that was no gxe block (tools/gxe_timing.py). */
 int scilmm_gxe_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Phenotype panels: X^T Y for the forward solution X that the LAST scan block on this handle left behind (any form: plain,
+ * Gram or gxe -- for gxe, r is the block's d r columns) and a resident panel Y of t phenotype columns.  The whitened markers
+ * do not depend on the phenotype, so one forward sweep serves any number of traits, or of simulated null phenotypes (a
+ * parametric bootstrap of the genome-wide maximum): one more GEMM-shaped pass over X on the fp64 matrix pipe.
+ *   r      : columns of the block left behind, 1 .. 128; it must be the r of that block.
+ *   d_Y    : n x ld_y row-major, PERMUTED order (the order of d_Q), 16-byte aligned; t <= ld_y, ld_y % 16 == 0.  The values
+ *            of the padding columns t .. ld_y - 1 reach no output (they may be anything, NaN included).
+ *   t      : columns of the panel, 1 .. 4096.
+ *   d_xty  : r x t, leading dimension ld_out >= t: xty[j][k] = x_j . y_k.  Exactly r t numbers are written.
+ * Fixed row slices, folded in a fixed tree, no floating-point atomics: the bits of xty[j][k] depend on n and on the values of
+ * x_j and y_k alone -- not on t, on where y_k sits in Y, on r, or on the mode of the handle -- and
+ * scilmm_timing.n_float_atomic_launches is not touched.  The call is enqueued on the handle's stream without synchronising;
+ * it writes nothing of the work buffers, so several panels may follow one block.  Its partial tiles are allocated on the
+ * first call and grown for a wider panel only (the stream is synchronised before that).
+ * SCILMM_ERR_ARG before anything is dereferenced: a null fac, d_Y or d_xty, r outside 1 .. 128, t outside 1 .. 4096,
+ * ld_y < t or ld_y % 16 != 0, ld_out < t, d_Y not 16-byte aligned.  SCILMM_ERR_STATE with a message, the handle left usable:
+ * no block left behind -- whatever may overwrite the work buffers (a solve, a half-solve, L*R, a product) forgets it, and so
+ * do a refactorization and scilmm_inverse_traces -- or another r than that block's; refusals as for the half-solves (a
+ * distributed handle, fp32-product fronts, a factor consumed by the selected inverse).  scilmm_scan_timing is unaffected;
+ * scilmm_panel_timing reports the call's own two kernels.  scilmm_amd.TraitPanel (AssociationScan.traits, .null_panel) is
+ * the interface.  No counterpart in the reference. */
+int scilmm_scan_panel_dev(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, int32_t t, double* d_xty, int64_t ld_out);
+
+/* HIP-event times of the last scilmm_scan_panel_dev on the handle, in milliseconds, valid after the scilmm_sync that
+ * follows it: ms[0] k_scan_panel, ms[1] k_panel_fold (tools/panel_timing.py).  No counterpart in the reference. */
+int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms);
+
 /* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
  * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y
  * (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1) per column by the scan's algebra: predicted value, prediction error variance

@@ -79,6 +79,7 @@ SYMBOLS = [
     "scilmm_scan_block_gram_dev", "scilmm_scan_block_bed_gram_dev",
     "scilmm_scan_block_dosage_dev", "scilmm_scan_block_dosage_gram_dev",
     "scilmm_scan_block_gxe_dev", "scilmm_scan_block_bed_gxe_dev", "scilmm_scan_block_dosage_gxe_dev", "scilmm_gxe_timing",
+    "scilmm_scan_panel_dev", "scilmm_panel_timing",
 ]
 
 _lib = None
@@ -180,6 +181,8 @@ def lib():
     L.scilmm_scan_block_dosage_gxe_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, i32, vp, i32, vp]
     L.scilmm_scan_timing.argtypes = [vp, P(dbl)]
     L.scilmm_gxe_timing.argtypes = [vp, P(dbl)]
+    L.scilmm_scan_panel_dev.argtypes = [vp, i32, vp, i64, i32, vp, i64]
+    L.scilmm_panel_timing.argtypes = [vp, P(dbl)]
     L.scilmm_rel_block_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_rows_block_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_order.argtypes = [i32, vp, vp, i32, vp]

@@ -16,6 +16,7 @@ convention here is the same F(1, n - 1).
     out = scan.scan_bed("cohort", sample_index=idx)   # PLINK 1 .bed / .bim / .fam, 2-bit genotypes decoded on the device
     out = scan.scan_dosages(ds, sample_index=idx)     # imputed dosages: m x N uint16 codes or float32 (scilmm_amd.dosage)
     gxe = scan.interaction(env)    # marker x environment interaction on the same factor and whitening (scilmm_amd.gxe)
+    panel = scan.traits(Y)         # many traits, or scan.null_panel(...): simulated null phenotypes (scilmm_amd.panel)
 
 There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
 """
@@ -111,13 +112,16 @@ class WhitenedModel(object):
         blk = self.block if blk is None else blk
         return self.torch.empty(((m + blk - 1) // blk, nrows * blk), dtype=self.torch.float64, device="cuda")
 
-    def _run_blocks(self, dS, out, enqueue, blk=None):
+    def _run_blocks(self, dS, out, enqueue, blk=None, after=None):
         """Fills ``out`` (nrows x m, m columns staged on the device) through ``dS``: ``enqueue(k0, rb, stats_ptr)`` queues the
-        block of columns k0 .. k0 + rb - 1 (``blk`` columns per block, default ``block``); every block is queued, then one
-        wait and one device-to-host copy."""
+        block of columns k0 .. k0 + rb - 1 (``blk`` columns per block, default ``block``), ``after(k0, rb)``, if given, what
+        follows it on the block it leaves behind (``scilmm_amd.panel``); every block is queued, then one wait and one
+        device-to-host copy."""
         (nrows, m), blk = out.shape, self.block if blk is None else blk
         for b, k0 in enumerate(range(0, m, blk)):
             enqueue(k0, min(blk, m - k0), C.c_void_p(dS.data_ptr() + 8 * b * nrows * blk))
+            if after is not None:
+                after(k0, min(blk, m - k0))
         self.sym.sync()
         hS = dS.cpu().numpy()
         for b, k0 in enumerate(range(0, m, blk)):
@@ -137,11 +141,14 @@ class AssociationScan(WhitenedModel):
         super(AssociationScan, self).__init__(cholesky_func, mats, sigma2, covariates, y, block)
         self._f = stats.f(1, self.n - 1)
 
-    def _stats(self, src, rows, chunk_bytes, nrows=None, blk=None, env=None):
+    def _stats(self, src, rows, chunk_bytes, nrows=None, blk=None, env=None, follow=None, rows_max=None):
         """nrows x m statistics (default: the scan's q + 4) of the markers ``rows`` (a slice or an index array) of the marker
         source ``src`` (``scilmm_amd.markers``), ``blk`` markers per device block (default ``block``), in chunks of whole
         blocks of at most ``chunk_bytes`` host bytes: a chunk is brought to the device, its blocks are queued, one wait.  The
-        buffers are allocated once, for the largest chunk.  ``env``: the source's third twin (``scilmm_amd.gxe``)."""
+        buffers are allocated once, for the largest chunk.  ``env``: the source's third twin (``scilmm_amd.gxe``).  ``follow``:
+        a per-block follow-up (``scilmm_amd.panel``) -- ``stage(rows)`` once, ``block(k0, rb)`` behind every block of a chunk,
+        ``chunk(j0, mc, dS, nrows, blk)`` when the chunk has been waited for; ``rows_max``: markers per chunk at most (whole
+        blocks, at least one: what the follow-up keeps per chunk is bounded too)."""
         nrows = self.q + 4 if nrows is None else nrows
         blk = self.block if blk is None else blk
         run = isinstance(rows, slice)
@@ -150,13 +157,19 @@ class AssociationScan(WhitenedModel):
         if m == 0:
             return out
         per = max(blk, min(m, max(1, chunk_bytes // src.row_bytes)) // blk * blk)
+        if rows_max is not None:
+            per = min(per, max(blk, rows_max // blk * blk))
         dS = self._stats_buffer(nrows, min(per, m), blk)
         src.stage(min(per, m))
+        if follow is not None:
+            follow.stage(min(per, m))
         enqueue = src.enqueue if env is None else (lambda k0, rb, pS: src.enqueue(k0, rb, pS, env=env))
         for j0 in range(0, m, per):
             mc = min(per, m - j0)
             src.load(slice(rows.start + j0, rows.start + j0 + mc) if run else rows[j0:j0 + mc])
-            self._run_blocks(dS, out[:, j0:j0 + mc], enqueue, blk)
+            self._run_blocks(dS, out[:, j0:j0 + mc], enqueue, blk, None if follow is None else follow.block)
+            if follow is not None:
+                follow.chunk(j0, mc, dS, nrows, blk)
         return out
 
     def __call__(self, genotypes):
@@ -186,6 +199,22 @@ class AssociationScan(WhitenedModel):
         scan's factor and whitening, for the n x m environment columns ``env``."""
         from .gxe import InteractionScan
         return InteractionScan(self, env, require_main_effects)
+
+    def traits(self, Y, scale="fixed"):
+        """A panel of T traits next to this scan: a ``TraitPanel`` (``scilmm_amd.panel``) on this scan's factor and whitening.
+        ``Y``: n x T float64, finite, 1 <= T <= 4096, rows in the order of ``mats``; ``scale``: "fixed" (V as given) or "profile"
+        (the variance ratios shared, the scale profiled per trait: EMMAX).  ``panel(genotypes)`` tests every marker against
+        every trait for one forward sweep per block."""
+        from .panel import TraitPanel
+        return TraitPanel.from_traits(self, Y, scale)
+
+    def null_panel(self, n_rep=1000, seed=0):
+        """A panel of ``n_rep`` (1..4096) null phenotypes simulated under this scan's model, ``N(C beta, V)``: in whitened space
+        ``z ~ N(0, I)`` drawn on the device from ``torch.Generator(device="cuda").manual_seed(seed)`` and projected off the
+        whitened covariates -- no solve.  The same seed, device and torch version give the same panel bits.
+        ``null(genotypes, reduce="max")`` gives the per-replicate maximum chi2 for ``panel_thresholds``."""
+        from .panel import TraitPanel
+        return TraitPanel.null(self, n_rep, seed)
 
     def scan_bed(self, bed, sample_index=None, markers=None, count="A1", chunk_bytes=None):
         """The scan of ``__call__`` on the markers of a PLINK 1 fileset, decoded on the device: the packed rows are uploaded

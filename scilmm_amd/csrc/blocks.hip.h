@@ -105,6 +105,8 @@ struct BlockCall {
     HIPCHK(hipEventRecord(D->scan_ev[3], s0));
     D->scan_pending = true;
     D->gxe_pending = gxe != nullptr;
+    D->block_r = r;  // X holds this block until the work buffers are asked for again (scan_panel)
+    D->block_rp = sw->rp;
     if (D->h_chain_err) HIPCHK(hipMemcpyAsync(D->h_chain_err, D->d_chain_err, sizeof(int32_t), hipMemcpyDeviceToHost, s0));
     HIPCHK(hipGetLastError());
     return SCILMM_OK;
@@ -163,6 +165,48 @@ auto fill_dosage(const void* d_dos, int64_t ld, int32_t n_samples, const int32_t
     hipLaunchKernelGGL(k_dos_dequant<T>, dim3(scan_tiles(n)), dim3(256), 0, D->stream, n, n_samples, r, rp, (const T*)d_dos, ld, d_sample,
                        (const int32_t*)D->d_iperm, (const double*)(d_stats + r), D->W);
   };
+}
+
+// X^T Y for the block the last scan block on the handle left in X (scilmm_scan_panel_dev): the refusals of the half-solves, the
+// record of that block, the partial tiles (grown for a wider panel only: the stream is synchronised first, and nothing is
+// allocated afterwards for the same or a smaller t), k_scan_panel and k_panel_fold between the call's own events.  Nothing of
+// the work buffers is written: the block stays where it is, and any number of panels may follow one block.
+int scan_panel(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, int32_t t, double* d_xty, int64_t ld_out) {
+  const char* who = "scilmm_scan_panel_dev";
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  if (D->block_r == 0) {
+    sym->err = std::string(who) + ": no scan block on this handle since the work buffers were last used (a solve, a product or a "
+                                  "refactorization came in between): run the block first";
+    return SCILMM_ERR_STATE;
+  }
+  if (D->block_r != r) {
+    sym->err = std::string(who) + ": r = " + std::to_string(r) + ", the block left behind has " + std::to_string(D->block_r) + " columns";
+    return SCILMM_ERR_STATE;
+  }
+  const int32_t n = sym->S->n, rp = D->block_rp, ntile = (rp / 16) * PANEL_NJ;
+  const int32_t npanel = (t + PANEL_COLS - 1) / PANEL_COLS;
+  const int slice = panel_slice();
+  const int64_t nslice = ((int64_t)n + slice - 1) / slice;
+  const size_t need = (size_t)(((int64_t)n + PANEL_SLICE_MIN - 1) / PANEL_SLICE_MIN) * (size_t)npanel * PANEL_NI * PANEL_NJ * 256;
+  if (D->panel_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  TRY(grow(sym, &D->panel_partial, &D->panel_partial_cap, need));
+  if (!D->panel_ev[0])
+    for (auto& e : D->panel_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->panel_ev[0], s0));
+  hipLaunchKernelGGL(panel_kernel(slice), dim3((unsigned)nslice, (unsigned)npanel), dim3(256), 0, s0, n, rp, (const double*)D->X, d_Y, ld_y, t,
+                     D->panel_partial);
+  HIPCHK(hipEventRecord(D->panel_ev[1], s0));
+  hipLaunchKernelGGL(k_panel_fold, dim3((unsigned)(npanel * ntile)), dim3(PANEL_FOLD * 256), 0, s0, nslice, npanel, ntile,
+                     (const double*)D->panel_partial, r, t, d_xty, ld_out);
+  HIPCHK(hipEventRecord(D->panel_ev[2], s0));
+  D->panel_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
 }
 
 // One block of columns `ids` of sum_k weights[k] A_k, built from the resident values (scilmm_rel_block_dev).

@@ -292,6 +292,15 @@ struct Dev {
   hipEvent_t gxe_ev[2] = {nullptr, nullptr};  // a gxe block's: the form's fill done | k_scan_fold done (the first gxe block creates them)
   bool gxe_pending = false;             // the pending scan block is a gxe block
   double gxe_ms[2] = {0.0, 0.0};        // the last block's k_scan_expand | k_scan_cross + its fold; 0 after a plain block (scilmm_gxe_timing)
+  // phenotype panels (scilmm_scan_panel_dev): X^T Y for the forward solution the last scan block left in X
+  int32_t block_r = 0, block_rp = 0;    // X holds a block of block_r columns padded to block_rp (BlockCall::finish); 0: it does not --
+                                        // whatever may overwrite the work buffers or replaces the factor clears the record (clear_block)
+  double* panel_partial = nullptr;      // [slices of PANEL_SLICE rows][column panels][tiles][256]: partial tiles of X^T Y
+  size_t panel_partial_cap = 0;         // doubles (grown for a wider panel only)
+  hipEvent_t panel_ev[3] = {nullptr, nullptr, nullptr};  // panel begin | k_scan_panel done | k_panel_fold done (the first panel call creates them)
+  bool panel_pending = false;           // a panel call whose events have not been read yet (scilmm_sync)
+  double panel_ms[2] = {0.0, 0.0};      // the last call's k_scan_panel | k_panel_fold (scilmm_panel_timing)
+  void clear_block() { block_r = block_rp = 0; }
 };
 
 #define HIPCHK(call)                                                                                   \

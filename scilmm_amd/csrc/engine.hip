@@ -1,9 +1,9 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, bed.hip.h, dosage.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
@@ -32,6 +32,7 @@
 #include "kernels.hip.h"
 #include "scan.hip.h"
 #include "gram.hip.h"
+#include "panel.hip.h"
 #include "bed.hip.h"
 #include "dosage.hip.h"
 #include "blup.hip.h"
@@ -305,6 +306,14 @@ int scilmm_scan_block_dosage_gxe_dev(scilmm_factor* fac, const void* d_dos, int3
   return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
 }
 
+// X^T Y for the block the last scan block left behind and a resident phenotype panel: what needs no handle is checked first
+int scilmm_scan_panel_dev(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, int32_t t, double* d_xty, int64_t ld_out) {
+  if (!fac || !d_Y || !d_xty || r < 1 || r > RPMAX || t < 1 || t > PANEL_TMAX || ld_y < t || ld_y % 16 != 0 || ld_out < t ||
+      (uintptr_t)d_Y % 16 != 0 || !fac->sym || !fac->sym->S)
+    return SCILMM_ERR_ARG;
+  return scan_panel(fac, r, d_Y, ld_y, t, d_xty, ld_out);
+}
+
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
                          double* d_stats) {
   if (!weights || !ids || !BlockCall::args_ok(fac, r, d_Q, q, d_stats)) return SCILMM_ERR_ARG;
@@ -485,6 +494,14 @@ int scilmm_sync(scilmm_symbolic* sym) {
     // (the queued copy behind the block's sweep has arrived)
     if (D->h_chain_err && *D->h_chain_err != 0) return report_chain_timeout(sym, D, " (scan block)");
   }
+  if (D->panel_pending) {
+    D->panel_pending = false;
+    float a = 0, b = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->panel_ev[0], D->panel_ev[1]));
+    HIPCHK(hipEventElapsedTime(&b, D->panel_ev[1], D->panel_ev[2]));
+    D->panel_ms[0] = a;
+    D->panel_ms[1] = b;
+  }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
 }
@@ -516,6 +533,13 @@ int scilmm_gxe_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   const Dev* D = (const Dev*)sym->device;
   for (int i = 0; i < 2; ++i) ms[i] = D->gxe_ms[i];
+  return SCILMM_OK;
+}
+
+int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const Dev* D = (const Dev*)sym->device;
+  for (int i = 0; i < 2; ++i) ms[i] = D->panel_ms[i];
   return SCILMM_OK;
 }
 

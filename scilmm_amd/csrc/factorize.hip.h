@@ -332,6 +332,7 @@ int run_factorize(scilmm_factor* fac, const double* sigma2, int32_t* bad_col, bo
       sym->err = "scilmm_values_upload has not been called for every matrix";
       return SCILMM_ERR_STATE;
     }
+  D->clear_block();  // (a block left in X belongs to the factor that is replaced here)
   fac->valid = false;
   fac->inverted = false;
   if (D->world > 1 && (!sym->comm_fn || !D->comm)) {

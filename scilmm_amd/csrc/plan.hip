@@ -34,9 +34,12 @@ void dev_free(void* p) {
   if (D->partial) (void)hipFree(D->partial);
   if (D->scan_partial) (void)hipFree(D->scan_partial);
   if (D->gram_partial) (void)hipFree(D->gram_partial);
+  if (D->panel_partial) (void)hipFree(D->panel_partial);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->gxe_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->panel_ev)
     if (e) (void)hipEventDestroy(e);
   if (D->d_out) (void)hipFree(D->d_out);
   for (auto& e : D->ev)

@@ -66,6 +66,7 @@ int inverse_traces(scilmm_factor* fac, double* out) {
   Dev* D = (Dev*)sym->device;
   const Symbolic& S = *sym->S;
   constexpr int NBLK = 1024;
+  D->clear_block();  // (the factor a block in X was swept with is gone)
   TRY(ensure_io(sym, D, 2 * NBLK));
   hipStream_t s0 = D->stream;
   double* part = D->IO;

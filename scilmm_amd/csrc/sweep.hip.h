@@ -12,6 +12,7 @@ namespace {
 
 int ensure_work(scilmm_symbolic* sym, Dev* D) {
   const Symbolic& S = *sym->S;
+  D->clear_block();  // (whoever asks for the work buffers is about to write them: X no longer holds a scan block, scilmm_scan_panel_dev)
   size_t bytes = (size_t)std::max(S.n, 1) * RPMAX * sizeof(double);
   if (D->world > 1 && !D->work_external) {
     sym->err = "multi-GPU: scilmm_dist_set_work has not been called (the sweeps' buffers must be addressable by the communication layer)";

@@ -265,6 +265,12 @@ class Symbolic(object):
         check(lib().scilmm_gxe_timing(self._h, ms), self._h)
         return tuple(ms)
 
+    def panel_timing(self):
+        """(``k_scan_panel``, ``k_panel_fold``) of the last ``Factor.scan_panel_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 2)()
+        check(lib().scilmm_panel_timing(self._h, ms), self._h)
+        return tuple(ms)
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -460,6 +466,13 @@ class Factor(object):
         """``scan_block_dosage_dev`` with ``m`` environment columns (``scilmm_scan_block_dosage_gxe_dev``)."""
         check(lib().scilmm_scan_block_dosage_gxe_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dE_ptr, m, dQ_ptr, q,
                                                      dstats_ptr), self.sym._h)
+
+    def scan_panel_dev(self, r, dY_ptr, ld_y, t, dxty_ptr, ld_out):
+        """``xty[j][k] = x_j . y_k`` (r x t, leading dimension ``ld_out``) for the ``r`` whitened columns the last scan block on
+        this handle left behind and the ``t`` columns of the device panel ``dY_ptr`` (n x ``ld_y`` float64 in the permuted order
+        of ``Q``, 16-byte aligned, ``ld_y`` a multiple of 16); enqueues without synchronising (``scilmm_scan_panel_dev``;
+        ``scilmm_amd.panel.TraitPanel`` is the interface).  ``ScilmmError`` when no block was left behind or ``r`` is not its."""
+        check(lib().scilmm_scan_panel_dev(self._h, r, dY_ptr, ld_y, t, dxty_ptr, ld_out), self.sym._h)
 
     def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
         """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host
