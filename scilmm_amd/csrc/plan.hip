@@ -1858,6 +1858,12 @@ int ensure_sinv_plan(scilmm_symbolic* sym, Dev* D) {
     }
     D->sinv_work_ptr[(size_t)jj + 1] = (int64_t)sw.size();
   }
+  if (verbose()) {
+    int64_t multi = 0;
+    for (const SinvWork& it : sw) multi += it.kb - it.ka > 1;
+    fprintf(stderr, "[scilmm plan] selected inverse: %d tail fronts, %lld items, %lld of them over more than one front, pre-tail tiles %lld\n",
+            (int)nT, (long long)sw.size(), (long long)multi, (long long)pre_tiles.size());
+  }
   if (sw.empty()) sw.push_back(SinvWork{0, 0, 0, 0});
   if (tails.empty()) tails.push_back(0);
   if (pre_tiles.empty()) pre_tiles.push_back(0);
