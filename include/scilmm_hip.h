@@ -427,10 +427,15 @@ int scilmm_set_front_precision(scilmm_symbolic* sym, int32_t bits);
  *     atomic pushes,
  *   - Y = A_k X (scilmm_spmm / _dev, and with it the refinement of solves on fp32 fronts) with row ownership through a
  *     transposed index of the pattern (k_spmm_row; 12 bytes per strictly lower pattern entry of device memory, allocated
- *     only in this mode: scilmm_symbolic_get "pat_rowptr" / "pat_rowslot" / "pat_rowcol" give the counts).
+ *     only in this mode: scilmm_symbolic_get "pat_rowptr" / "pat_rowslot" / "pat_rowcol" give the counts),
+ *   - the selected inverse (scilmm_selected_inverse, and with it scilmm_inverse_traces) in store-and-sum form: the items of
+ *     the dense-tail kernel store their accumulator tiles into slots that a second kernel adds in K-range order
+ *     (k_sinv_tail<true> + k_sinv_tail_fold), the diagonal blocks are summed over fixed segments of consecutive row tiles
+ *     (k_sinv_cc_ordered + k_sinv_cc_fold); every entry of Z is written with plain stores.  The slots are allocated with
+ *     the handle's first inversion: at most about 2048 + (rows / 256) tiles of 256 x 128 doubles (0.54 GB) for the tail,
+ *     one 128 x 128 tile per two row tiles of the largest level for the diagonal blocks (SCILMM_VERBOSE prints both).
  * The backward sweep, the chain sweeps, quadratic forms, the log-determinant and the Haseman-Elston moments are order-fixed in
- * either mode.  NOT covered: the selected inverse (scilmm_selected_inverse keeps working and keeps its atomics), and
- * distributed handles -- the summation order of an all-reduce belongs to the communication library, so on a handle with
+ * either mode.  NOT covered: distributed handles -- the summation order of an all-reduce belongs to the communication library, so on a handle with
  * scilmm_dist_init(world > 1) the mode is refused with SCILMM_ERR_STATE (in either call order: scilmm_dist_init refuses a
  * deterministic handle as well).  Results in this mode differ from the default mode's in the last bits; the default
  * schedule is unchanged.  The initial value of a handle is SCILMM_DETERMINISTIC=1 in the environment at creation.  Must be
@@ -496,7 +501,7 @@ typedef struct scilmm_timing {
    * critical path); 0 on one GPU */
   int64_t n_late_split;
   /* kernel launches on this handle SINCE IT WAS CREATED whose results are summed with floating-point atomics (k_outside,
-   * the atomic forms of k_fwd, k_spmm_w, k_sinv_w / k_sinv_tail): 0 in deterministic mode unless the selected inverse ran */
+   * the atomic forms of k_fwd, k_spmm_w, k_sinv_tail / k_sinv_cc): 0 in deterministic mode */
   int64_t n_float_atomic_launches;
 } scilmm_timing;
 int scilmm_last_timing(const scilmm_symbolic* sym, scilmm_timing* out);

@@ -80,9 +80,9 @@ class SparseCholesky(object):
         if front_bits not in (32, 64):
             raise ValueError("front_bits must be 32 or 64")
         self.front_bits = front_bits
-        # deterministic=True: every engine this object creates sums in a fixed order (factorization, sweeps, L*R, SpMM:
-        # scilmm_set_deterministic) -- an evaluation then repeats bit for bit, between processes as well; None follows
-        # SCILMM_DETERMINISTIC.  Not covered: exact_trace (the selected inverse keeps its atomics).
+        # deterministic=True: every engine this object creates sums in a fixed order (factorization, sweeps, L*R, SpMM and
+        # the selected inverse of exact_trace: scilmm_set_deterministic) -- an evaluation then repeats bit for bit, between
+        # processes as well; None follows SCILMM_DETERMINISTIC.
         if deterministic is None:
             deterministic = os.environ.get("SCILMM_DETERMINISTIC", "")[:1] == "1"
         self.deterministic = bool(deterministic)

@@ -62,6 +62,10 @@ struct Tuning {
   int chain_stagger = 0;               // SCILMM_CHAIN_STAGGER   run_rhs: a chain workgroup with more pairs than this first waits for
                                        //                        its k-th-from-last pair (short chains reach the pipelined branch); 0: off
   bool sinv_generic = false;           // SCILMM_SINV_GENERIC=1  selected inverse: the gather kernel for the dense tail too
+  bool sinv_reverse = false;           // SCILMM_SINV_REVERSE=1  selected inverse, deterministic mode: workgroup b of an ordered launch
+                                       //                        takes item gridDim.x - 1 - b (the bits must not move)
+  // -- read when the selected inverse's plan is built (the handle's first scilmm_selected_inverse)
+  int sinv_cc_tiles = 2;               // SCILMM_SINV_CC_TILES   deterministic mode: 128-row tiles per segment of k_sinv_cc_ordered (>= 1)
 };
 
 // The environment is read on every call: tests switch SCILMM_TUNING and a switch on and off inside one process.
@@ -105,6 +109,8 @@ inline Tuning read_tuning() {
   t.chain_pipe = not0("SCILMM_CHAIN_PIPE");
   if ((e = env("SCILMM_CHAIN_STAGGER"))) t.chain_stagger = std::max(0, atoi(e));
   t.sinv_generic = is1("SCILMM_SINV_GENERIC");
+  t.sinv_reverse = is1("SCILMM_SINV_REVERSE");
+  if ((e = env("SCILMM_SINV_CC_TILES"))) t.sinv_cc_tiles = std::max(1, atoi(e));
   return t;
 }
 
@@ -211,6 +217,14 @@ struct Dev {
   int32_t* d_sinv_tail_fronts = nullptr;      // the tail fronts, one per entry (k_sinv_zero takes a list)
   SinvWork* d_sinv_work = nullptr;            // items of k_sinv_tail, grouped by tail front
   std::vector<int64_t> sinv_work_ptr;         // [ntail+1]
+  // ... in deterministic mode (the order-fixed forms): nothing below is built on a default handle
+  std::vector<int32_t> sinv_tail_nseg;        // [ntail] K ranges per row tile of the front's items; > 1: slots + k_sinv_tail_fold
+  double* d_sinv_tail_partial = nullptr;      // [items of the largest folded front][256 x NB]
+  SinvSeg* d_sinv_cc_segs = nullptr;          // segments of k_sinv_cc_ordered, by level
+  std::vector<int64_t> sinv_cc_seg_ptr;       // [nlevels+1]
+  SinvFold* d_sinv_cc_folds = nullptr;        // fronts with several segments, by level (k_sinv_cc_fold)
+  std::vector<int64_t> sinv_cc_fold_ptr;      // [nlevels+1]
+  double* d_sinv_cc_partial = nullptr;        // [slots of the largest level][TM x NB]
   bool work_external = false;           // W / X / ACC belong to the caller (scilmm_dist_set_work)
   // dense tail (Symbolic::dense_first): implicit work items of k_dense, early (side streams) and late (main stream)
   // prelude -> tail contributions in descendant coordinates (k_outside; fp64 atomics): one launch between the last

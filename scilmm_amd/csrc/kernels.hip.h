@@ -3141,13 +3141,26 @@ __global__ __launch_bounds__(256) void k_sinv_w(DevSym S, const int32_t* __restr
 //    diagonal need no special case.
 //  * the sum is ADDED to the panel with fp64 atomics (the front's rows were zeroed after Y was taken): several K ranges
 //    of one row tile run as separate workgroups, which is what keeps a launch at >= 1000 items for every front.
+//  * ORDERED (deterministic mode): the same items, no atomics.  The items of a launch are [K range][row tile]; where the
+//    front has ONE K range the item stores -acc straight into the panel (it is the only writer of its rows), otherwise it
+//    stores its accumulators as they lie in the registers -- whole fragments, 512 contiguous bytes per wave store -- into
+//    slot `item` of ord.partial, and k_sinv_tail_fold adds a row tile's slots in K-range order.  The slot belongs to the
+//    ITEM, not to the workgroup: ord.reverse turns the dispatch order round and leaves every sum as it was.
+struct SinvTailOrd {
+  double* partial;  // [items of the launch][sinv_tail_slot(ncb)]
+  int32_t nseg;     // K ranges per row tile of the launch's front; 1: plain stores into the panel
+  int32_t reverse;  // workgroup b takes item gridDim.x - 1 - b (test switch SCILMM_SINV_REVERSE)
+};
+template <bool ORDERED>
 __global__ __launch_bounds__(512, 1) void k_sinv_tail(DevSym S, int32_t dense_first, const SinvWork* __restrict__ work, double* L,
                                                       const double* __restrict__ Ybuf, const int64_t* __restrict__ yoff,
-                                                      const int32_t* __restrict__ col_front, const double* __restrict__ zeros) {
+                                                      const int32_t* __restrict__ col_front, const double* __restrict__ zeros,
+                                                      SinvTailOrd ord) {
   extern __shared__ __attribute__((aligned(16))) double smem[];  // [2][KBA][LDB]
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lk = lane >> 4;
-  const SinvWork wk = work[blockIdx.x];
+  const unsigned item = ORDERED && ord.reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const SinvWork wk = work[item];
   const int32_t s = wk.front;
   const int32_t c0 = S.sn_start[s], w = S.sn_start[s + 1] - c0;
   const int32_t m = S.n - c0, u = m - w;
@@ -3264,6 +3277,18 @@ __global__ __launch_bounds__(512, 1) void k_sinv_tail(DevSym S, int32_t dense_fi
     buf ^= 1;
   }
   double* P = L + S.sn_loff[s];
+  if (ORDERED && ord.nseg > 1) {
+    const int ncb = (w + 15) >> 4;
+    double* o = ord.partial + (int64_t)item * sinv_tail_slot(ncb) + (int64_t)wv * (ncb * 512) + lane;
+#pragma unroll
+    for (int jb = 0; jb < NJB; ++jb)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (jb < ncb) o[(2 * jb + ib) * 256 + 64 * r] = acc16[jb][ib][r];
+    return;
+  }
 #pragma unroll
   for (int jb = 0; jb < NJB; ++jb)
 #pragma unroll
@@ -3271,8 +3296,63 @@ __global__ __launch_bounds__(512, 1) void k_sinv_tail(DevSym S, int32_t dense_fi
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = ib == 0 ? ia : ib_, jc = 16 * jb + lk + 4 * r;
-        if (i < nrow && jc < w) unsafeAtomicAdd(&P[(int64_t)jc * m + w + r0 + i], -acc16[jb][ib][r]);
+        if (i < nrow && jc < w) {
+          if (ORDERED) P[(int64_t)jc * m + w + r0 + i] = -acc16[jb][ib][r];
+          else unsafeAtomicAdd(&P[(int64_t)jc * m + w + r0 + i], -acc16[jb][ib][r]);
+        }
       }
+}
+
+// rows [256 q, 256 q + 256) of R of tail front s, columns [16 jb, 16 jb + 16) <- -(sum of the row tile's nseg slots, in
+// K-range order); one workgroup per (row tile q = blockIdx.x, column tile jb = blockIdx.y), every thread the two fragments
+// its namesake of k_sinv_tail stored there (slot of (range g, tile q): g * ntile + q).  Four slots' loads are in flight at a
+// time; the additions keep the order g = 0, 1, 2, ...
+__global__ __launch_bounds__(512) void k_sinv_tail_fold(DevSym S, int32_t s, int32_t nseg, const double* __restrict__ partial,
+                                                        double* __restrict__ L) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int li = lane & 15, lk = lane >> 4;
+  const int32_t c0 = S.sn_start[s], w = S.sn_start[s + 1] - c0;
+  const int32_t m = S.n - c0, u = m - w;
+  const int32_t ntile = (u + 255) / 256;
+  const int32_t r0 = 256 * (int32_t)blockIdx.x;
+  const int32_t nrow = min(256, u - r0);
+  const int ncb = (w + 15) >> 4, jb = blockIdx.y;
+  const double* p = partial + (int64_t)blockIdx.x * sinv_tail_slot(ncb) + (int64_t)wv * (ncb * 512) + 2 * jb * 256 + lane;
+  const int64_t step = (int64_t)ntile * sinv_tail_slot(ncb);
+  double* P = L + S.sn_loff[s];
+  double sum[2][4];
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sum[ib][r] = p[ib * 256 + 64 * r];
+  int32_t g = 1;
+  for (; g + 4 <= nseg; g += 4) {
+    double v[4][2][4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[x][ib][r] = p[(g + x) * step + ib * 256 + 64 * r];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sum[ib][r] += v[x][ib][r];
+  }
+  for (; g < nseg; ++g)
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sum[ib][r] += p[g * step + ib * 256 + 64 * r];
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = 32 * wv + 16 * ib + li, jc = 16 * jb + lk + 4 * r;
+      if (i < nrow && jc < w) P[(int64_t)jc * m + w + r0 + i] = -sum[ib][r];
+    }
 }
 
 // rows [w, m) of every column of the panels of `fronts` <- 0 (before the atomic accumulation of Z_RC); one workgroup per
@@ -3354,6 +3434,122 @@ __global__ __launch_bounds__(256) void k_sinv_cc(DevSym S, const int32_t* __rest
         const int a = 32 * wv + 16 * ib + li;    // row
         if (a < w && b <= a) unsafeAtomicAdd(&P[(int64_t)b * m + a], -acc[jb][ib][r]);
       }
+}
+
+// The order-fixed form of k_sinv_cc (deterministic mode): a workgroup takes a SEGMENT of consecutive 128-row tiles of one
+// front and walks their rows in ascending order, 16 at a time, with the accumulators in registers.  slot < 0: the segment is
+// the front's only one and subtracts from the diagonal block with a plain read-modify-write (after k_sinv_cc0 nothing else
+// writes the block); otherwise the accumulators go to slot `slot` of `partial` as they lie in the registers and
+// k_sinv_cc_fold adds the front's slots in segment order.  The segment belongs to the list entry, not to the workgroup:
+// `reverse` turns the dispatch order round and leaves every sum as it was.
+template <bool MFMA>
+__global__ __launch_bounds__(256) void k_sinv_cc_ordered(DevSym S, const SinvSeg* __restrict__ segs, double* L,
+                                                         const double* __restrict__ Ybuf, const int64_t* __restrict__ yoff,
+                                                         int32_t dense_first, double* __restrict__ partial, int32_t reverse) {
+  __shared__ __attribute__((aligned(16))) double As[KCS * LDA];  // [k = row of the segment][a] = Y[row][a]
+  __shared__ __attribute__((aligned(16))) double Bs[KCS * LDB];  // [k][b] = Z_RC[row][b]
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const SinvSeg sg = segs[reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x];
+  const int32_t s = sg.front;
+  const int32_t w = S.sn_start[s + 1] - S.sn_start[s];
+  const int32_t m = (int32_t)(S.sn_rowptr[s + 1] - S.sn_rowptr[s]);
+  const int32_t R0 = sg.t0 * TM;
+  const int32_t nrow = min(sg.nt * TM, m - R0);
+  const int32_t u = m - w;
+  const int ncb = (w + 15) >> 4;
+  double* P = L + S.sn_loff[s];
+  const double* Y = Ybuf + yoff[s];
+  d4 acc[NJB][2];
+#pragma unroll
+  for (int a = 0; a < NJB; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
+  const int cq = tid & 127, kh = tid >> 7;  // column a (or b) and row parity inside a 16-row chunk
+  for (int32_t i0 = 0; i0 < nrow; i0 += KCS) {
+    if (i0 > 0) __syncthreads();
+#pragma unroll
+    for (int x = 0; x < KCS / 2; ++x) {
+      const int k = kh + 2 * x;
+      const int32_t row = R0 + i0 + k;  // panel row
+      const bool on = i0 + k < nrow && row >= w && cq < w;
+      As[k * LDA + cq] = on ? (s >= dense_first ? Y[(int64_t)(row - w) * NB + cq] : Y[(int64_t)cq * u + (row - w)]) : 0.0;
+      Bs[k * LDB + cq] = on ? P[(int64_t)cq * m + row] : 0.0;
+    }
+    __syncthreads();
+    if (32 * wv < w) tile_mma<MFMA>(As, Bs, KCS, ncb, lane, wv, acc);  // D[b][a] += sum_k Z_RC[k][b] Y[k][a]
+  }
+  if (32 * wv >= w) return;
+  const int li = lane & 15, lr = lane >> 4;
+  if (sg.slot >= 0) {
+    double* o = partial + (int64_t)sg.slot * SINV_CC_SLOT + (int64_t)wv * (NJB * 512) + lane;
+#pragma unroll
+    for (int jb = 0; jb < NJB; ++jb)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (jb < ncb) o[(2 * jb + ib) * 256 + 64 * r] = acc[jb][ib][r];
+    return;
+  }
+#pragma unroll
+  for (int jb = 0; jb < NJB; ++jb)
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int b = 16 * jb + lr + 4 * r;      // column of the diagonal block
+        const int a = 32 * wv + 16 * ib + li;    // row
+        if (a < w && b <= a) P[(int64_t)b * m + a] -= acc[jb][ib][r];
+      }
+}
+
+// diagonal block of front f.front, columns [16 jb, 16 jb + 16) -= (sum of its f.nseg slots from f.slot0 on, in segment
+// order); one workgroup per (front = blockIdx.x, column tile jb = blockIdx.y), every thread the two fragments its namesake
+// of k_sinv_cc_ordered stored there.  Four slots' loads are in flight at a time; the additions keep the segments' order.
+__global__ __launch_bounds__(256) void k_sinv_cc_fold(DevSym S, const SinvFold* __restrict__ folds, const double* __restrict__ partial,
+                                                      double* __restrict__ L) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int li = lane & 15, lr = lane >> 4;
+  const SinvFold f = folds[blockIdx.x];
+  const int32_t w = S.sn_start[f.front + 1] - S.sn_start[f.front];
+  const int32_t m = (int32_t)(S.sn_rowptr[f.front + 1] - S.sn_rowptr[f.front]);
+  const int jb = blockIdx.y;
+  if (32 * wv >= w || 16 * jb >= w) return;
+  const double* p = partial + (int64_t)f.slot0 * SINV_CC_SLOT + (int64_t)wv * (NJB * 512) + 2 * jb * 256 + lane;
+  double* P = L + S.sn_loff[f.front];
+  double sum[2][4];
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sum[ib][r] = p[ib * 256 + 64 * r];
+  int32_t g = 1;
+  for (; g + 4 <= f.nseg; g += 4) {
+    double v[4][2][4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[x][ib][r] = p[(g + x) * SINV_CC_SLOT + ib * 256 + 64 * r];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sum[ib][r] += v[x][ib][r];
+  }
+  for (; g < f.nseg; ++g)
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sum[ib][r] += p[g * SINV_CC_SLOT + ib * 256 + 64 * r];
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int b = 16 * jb + lr + 4 * r, a = 32 * wv + 16 * ib + li;
+      if (a < w && b <= a) P[(int64_t)b * m + a] -= sum[ib][r];
+    }
 }
 
 // part[block] = sum over this block's slots of vals[e] * Z[asm_dst[e]] (all slots once); the caller doubles it and takes

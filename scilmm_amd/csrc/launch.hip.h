@@ -194,8 +194,7 @@ inline void sinv_y(Dev* D, const scilmm_factor* fac, hipStream_t st, const int32
 
 inline void sinv_w(Dev* D, const scilmm_factor* fac, hipStream_t st, const int32_t* tiles, int64_t cnt) {
   if (cnt <= 0) return;
-  const auto k = D->use_mfma ? k_sinv_w<true> : k_sinv_w<false>;
-  D->n_float_atomic++;
+  const auto k = D->use_mfma ? k_sinv_w<true> : k_sinv_w<false>;  // (a tile runs its whole reduction and stores: no atomics)
   hipLaunchKernelGGL(k, dim3((unsigned)cnt), dim3(256), 0, st, D->v, tiles, fac->L, D->d_ybuf, D->d_yoff, D->d_col_front,
                      fac->sym->S->dense_first);
 }
@@ -203,7 +202,48 @@ inline void sinv_w(Dev* D, const scilmm_factor* fac, hipStream_t st, const int32
 inline void sinv_cc(Dev* D, const scilmm_factor* fac, hipStream_t st, const int32_t* tiles, int64_t cnt, int32_t ydf) {
   if (cnt <= 0) return;
   const auto k = D->use_mfma ? k_sinv_cc<true> : k_sinv_cc<false>;
+  D->n_float_atomic++;
   hipLaunchKernelGGL(k, dim3((unsigned)cnt), dim3(256), 0, st, D->v, tiles, fac->L, D->d_ybuf, D->d_yoff, ydf);
+}
+
+// Z_RC of tail front dense_first + jj: the atomic form behind k_sinv_zero, or (deterministic mode) the ordered form, which
+// writes every row of R x C exactly once -- straight from the items where the front has one K range, else from
+// k_sinv_tail_fold
+inline void sinv_tail(Dev* D, const scilmm_factor* fac, hipStream_t st, int32_t jj, bool reverse) {
+  const Symbolic& S = *fac->sym->S;
+  const int64_t i0 = D->sinv_work_ptr[(size_t)jj], i1 = D->sinv_work_ptr[(size_t)jj + 1];
+  if (i1 <= i0) return;
+  const int32_t tf = S.dense_first + jj;
+  const size_t lds = sizeof(double) * (size_t)(2 * KBA * LDB);
+  if (!D->det) {
+    const int32_t wtf = S.sn_start[tf + 1] - S.sn_start[tf];
+    hipLaunchKernelGGL(k_sinv_zero, dim3(1, (unsigned)wtf), dim3(256), 0, st, D->v, (const int32_t*)(D->d_sinv_tail_fronts + jj), fac->L);
+    D->n_float_atomic++;
+    hipLaunchKernelGGL(k_sinv_tail<false>, dim3((unsigned)(i1 - i0)), dim3(512), lds, st, D->v, S.dense_first,
+                       (const SinvWork*)(D->d_sinv_work + i0), fac->L, (const double*)D->d_ybuf, (const int64_t*)D->d_yoff,
+                       (const int32_t*)D->d_col_front, (const double*)D->d_zeros, SinvTailOrd{nullptr, 1, 0});
+    return;
+  }
+  const int32_t nseg = D->sinv_tail_nseg[(size_t)jj];
+  hipLaunchKernelGGL(k_sinv_tail<true>, dim3((unsigned)(i1 - i0)), dim3(512), lds, st, D->v, S.dense_first,
+                     (const SinvWork*)(D->d_sinv_work + i0), fac->L, (const double*)D->d_ybuf, (const int64_t*)D->d_yoff,
+                     (const int32_t*)D->d_col_front, (const double*)D->d_zeros, SinvTailOrd{D->d_sinv_tail_partial, nseg, reverse ? 1 : 0});
+  if (nseg > 1)
+    hipLaunchKernelGGL(k_sinv_tail_fold, dim3((unsigned)((i1 - i0) / nseg), (unsigned)((S.sn_start[tf + 1] - S.sn_start[tf] + 15) / 16)),
+                       dim3(512), 0, st, D->v, tf, nseg, (const double*)D->d_sinv_tail_partial, fac->L);
+}
+
+// deterministic mode: the diagonal blocks of level l, segment by segment, and the fronts with several segments folded
+inline void sinv_cc_ordered(Dev* D, const scilmm_factor* fac, hipStream_t st, int32_t l, int32_t ydf, bool reverse) {
+  const int64_t s0 = D->sinv_cc_seg_ptr[(size_t)l], ns = D->sinv_cc_seg_ptr[(size_t)l + 1] - s0;
+  const int64_t f0 = D->sinv_cc_fold_ptr[(size_t)l], nf = D->sinv_cc_fold_ptr[(size_t)l + 1] - f0;
+  if (ns <= 0) return;
+  const auto k = D->use_mfma ? k_sinv_cc_ordered<true> : k_sinv_cc_ordered<false>;
+  hipLaunchKernelGGL(k, dim3((unsigned)ns), dim3(256), 0, st, D->v, (const SinvSeg*)(D->d_sinv_cc_segs + s0), fac->L,
+                     (const double*)D->d_ybuf, (const int64_t*)D->d_yoff, ydf, D->d_sinv_cc_partial, reverse ? 1 : 0);
+  if (nf > 0)
+    hipLaunchKernelGGL(k_sinv_cc_fold, dim3((unsigned)nf, NJB), dim3(256), 0, st, D->v, (const SinvFold*)(D->d_sinv_cc_folds + f0),
+                       (const double*)D->d_sinv_cc_partial, fac->L);
 }
 
 }  // namespace

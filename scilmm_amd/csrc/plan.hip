@@ -1800,6 +1800,64 @@ int ensure_device(scilmm_symbolic* sym, Dev** out) {
   return SCILMM_OK;
 }
 
+// The order-fixed selected inverse (deterministic mode): which sums go through slots, and where.  Everything is a function
+// of the analysis and of T alone.
+//  * tail: the items of a front are [K range][row tile] (ensure_sinv_plan), so item i of the front's launch is its own
+//    slot i and row tile q sums slots q, ntile + q, ...; a front with one K range stores straight into its panel.
+//  * diagonal blocks: the 128-row tiles of a front that hold rows of R are cut into segments of T consecutive tiles, in row
+//    order; a front with one segment subtracts in place, the others take consecutive slots of their level.
+struct SinvOrderedStats {
+  int64_t tail_direct = 0, tail_folded = 0, tail_slots = 0;  // row tiles | row tiles | their slots
+  int64_t cc_direct = 0, cc_folded = 0;                      // segments
+  int64_t tail_bytes = 0, cc_bytes = 0;                      // the two slot buffers
+  int T = 0;
+};
+
+static void plan_sinv_ordered(const Symbolic& S, Dev* D, int T, std::vector<SinvSeg>* segs, std::vector<SinvFold>* folds,
+                              SinvOrderedStats* os) {
+  os->T = T;
+  const int32_t nT = S.nsuper - S.dense_first;
+  D->sinv_tail_nseg.assign((size_t)std::max(nT, 1), 0);
+  int64_t tail_slots_max = 0;  // doubles: slots of the front that needs most, each of its own width
+  for (int32_t jj = 0; jj < nT; ++jj) {
+    const int64_t items = D->sinv_work_ptr[(size_t)jj + 1] - D->sinv_work_ptr[(size_t)jj];
+    if (items == 0) continue;
+    const int32_t f = S.dense_first + jj;
+    const int64_t u = (int64_t)S.n - S.sn_start[f + 1], ntile = (u + 255) / 256;
+    const int64_t nseg = items / ntile;  // (every K range holds all ntile row tiles)
+    D->sinv_tail_nseg[(size_t)jj] = (int32_t)nseg;
+    if (nseg > 1) {
+      os->tail_folded += ntile;
+      os->tail_slots += items;
+      tail_slots_max = std::max(tail_slots_max, items * sinv_tail_slot((int)((S.sn_start[f + 1] - S.sn_start[f] + 15) / 16)));
+    } else {
+      os->tail_direct += ntile;
+    }
+  }
+  os->tail_bytes = tail_slots_max * (int64_t)sizeof(double);
+  D->sinv_cc_seg_ptr.assign((size_t)S.nlevels + 1, 0);
+  D->sinv_cc_fold_ptr.assign((size_t)S.nlevels + 1, 0);
+  int64_t cc_slots_max = 0;
+  for (int32_t l = 0; l < S.nlevels; ++l) {
+    int32_t slot = 0;
+    for (int32_t q = S.level_ptr[l]; q < S.level_ptr[l + 1]; ++q) {
+      const int32_t f = S.level_fronts[q];
+      const int64_t w = S.sn_start[f + 1] - S.sn_start[f], m = S.sn_rowptr[f + 1] - S.sn_rowptr[f];
+      if (m <= w) continue;  // no R: the diagonal block is L11^-T L11^-1 already
+      const int32_t t0 = (int32_t)(w / TM), t1 = (int32_t)((m + TM - 1) / TM);  // tiles [t0, t1) hold the rows w .. m
+      const int32_t nseg = (t1 - t0 + T - 1) / T;
+      if (nseg > 1) folds->push_back(SinvFold{f, slot, nseg});
+      for (int32_t g = 0; g < nseg; ++g)
+        segs->push_back(SinvSeg{f, t0 + g * T, std::min(T, t1 - (t0 + g * T)), nseg > 1 ? slot++ : -1});
+      (nseg > 1 ? os->cc_folded : os->cc_direct) += nseg;
+    }
+    cc_slots_max = std::max<int64_t>(cc_slots_max, slot);
+    D->sinv_cc_seg_ptr[(size_t)l + 1] = (int64_t)segs->size();
+    D->sinv_cc_fold_ptr[(size_t)l + 1] = (int64_t)folds->size();
+  }
+  os->cc_bytes = cc_slots_max * SINV_CC_SLOT * (int64_t)sizeof(double);
+}
+
 // The selected inverse's plan, built with the first scilmm_selected_inverse of a handle: column -> front, where every
 // front's Y = L21 L11^-1 lives inside the per-level scratch (dense-tail fronts keep it transposed, [u][128]), the
 // non-tail tiles by level, and the items of the dense-tail kernel
@@ -1858,16 +1916,41 @@ int ensure_sinv_plan(scilmm_symbolic* sym, Dev* D) {
     }
     D->sinv_work_ptr[(size_t)jj + 1] = (int64_t)sw.size();
   }
+  // deterministic mode: the same items, summed in an order the lists below fix (k_sinv_tail<true> + k_sinv_tail_fold,
+  // k_sinv_cc_ordered + k_sinv_cc_fold)
+  SinvOrderedStats os;
+  std::vector<SinvSeg> cc_segs;
+  std::vector<SinvFold> cc_folds;
+  if (D->det) plan_sinv_ordered(S, D, read_tuning().sinv_cc_tiles, &cc_segs, &cc_folds, &os);
   if (verbose()) {
     int64_t multi = 0;
     for (const SinvWork& it : sw) multi += it.kb - it.ka > 1;
     fprintf(stderr, "[scilmm plan] selected inverse: %d tail fronts, %lld items, %lld of them over more than one front, pre-tail tiles %lld\n",
             (int)nT, (long long)sw.size(), (long long)multi, (long long)pre_tiles.size());
+    if (D->det)
+      fprintf(stderr, "[scilmm plan] selected inverse, order-fixed: tail row tiles %lld direct, %lld folded from %lld slots (%lld bytes); "
+                      "cc segments of up to %d tiles: %lld direct, %lld folded (%lld bytes)\n",
+              (long long)os.tail_direct, (long long)os.tail_folded, (long long)os.tail_slots, (long long)os.tail_bytes, os.T,
+              (long long)os.cc_direct, (long long)os.cc_folded, (long long)os.cc_bytes);
   }
   if (sw.empty()) sw.push_back(SinvWork{0, 0, 0, 0});
   if (tails.empty()) tails.push_back(0);
   if (pre_tiles.empty()) pre_tiles.push_back(0);
   int stq;
+  if (D->det) {  // (before d_col_front, which marks the plan as built: a handle that could not get its slots has no plan)
+    if (cc_segs.empty()) cc_segs.push_back(SinvSeg{0, 0, 0, -1});
+    if (cc_folds.empty()) cc_folds.push_back(SinvFold{0, 0, 0});
+    if ((stq = upload(sym, D, cc_segs, &D->d_sinv_cc_segs)) != SCILMM_OK) return stq;
+    if ((stq = upload(sym, D, cc_folds, &D->d_sinv_cc_folds)) != SCILMM_OK) return stq;
+    void* pt = nullptr;
+    HIPCHK(hipMalloc(&pt, (size_t)std::max<int64_t>(os.tail_bytes, 8)));
+    D->allocs.push_back(pt);
+    D->d_sinv_tail_partial = (double*)pt;
+    void* pc = nullptr;
+    HIPCHK(hipMalloc(&pc, (size_t)std::max<int64_t>(os.cc_bytes, 8)));
+    D->allocs.push_back(pc);
+    D->d_sinv_cc_partial = (double*)pc;
+  }
   if ((stq = upload(sym, D, cf, &D->d_col_front)) != SCILMM_OK) return stq;
   if ((stq = upload(sym, D, yo, &D->d_yoff)) != SCILMM_OK) return stq;
   if ((stq = upload(sym, D, pre_tiles, &D->d_sinv_pre_tiles)) != SCILMM_OK) return stq;

@@ -127,4 +127,21 @@ struct SinvWork {
   int32_t ka, kb;  // source fronts [ka, kb) (absolute front ids, all > s)
 };
 
+// deterministic mode: doubles per slot of k_sinv_tail<true> for a front of ncb = ceil(w / 16) column tiles, [wave 8][jb < ncb]
+// [ib 2][reg 4][lane 64] (a launch is one front: its slots are of one size), and of k_sinv_cc_ordered, whose launches mix
+// fronts of every width: [wave 4][jb NB / 16][ib 2][reg 4][lane 64]
+constexpr int64_t sinv_tail_slot(int ncb) { return (int64_t)8 * ncb * 512; }
+constexpr int64_t SINV_CC_SLOT = (int64_t)4 * (NB / 16) * 512;
+
+// k_sinv_cc_ordered / k_sinv_cc_fold (deterministic mode)
+struct SinvSeg {
+  int32_t front;
+  int32_t t0, nt;  // 128-row tiles [t0, t0 + nt) of the front's panel; the first one holds rows of R
+  int32_t slot;    // partial slot of the level, or -1: the front's only segment
+};
+struct SinvFold {
+  int32_t front;
+  int32_t slot0, nseg;  // the front's slots [slot0, slot0 + nseg), in segment (= row) order
+};
+
 }  // namespace scilmm

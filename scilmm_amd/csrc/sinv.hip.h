@@ -1,6 +1,7 @@
 // The selected inverse (included by engine.hip only, behind values.hip.h): the Takahashi recursion over the levels from
-// the top down, in place on the factor's panels (the launchers sinv_y / sinv_w / sinv_cc of launch.hip.h around the
-// dense-tail kernels), and tr(V^-1 A_k) for every matrix from one pass over its pattern.
+// the top down, in place on the factor's panels (the launchers sinv_y / sinv_tail / sinv_w / sinv_cc of launch.hip.h; on a
+// deterministic handle the ordered branch of sinv_tail, and sinv_cc_ordered), and tr(V^-1 A_k) for every matrix from one
+// pass over its pattern.
 #pragma once
 
 namespace {
@@ -17,11 +18,17 @@ int selected_inverse(scilmm_factor* fac) {
   hipStream_t st = D->stream;
   const bool new_sinv_plan = !D->d_col_front;
   TRY(ensure_sinv_plan(sym, D));
-  if (new_sinv_plan)
-    HIPCHK(hipFuncSetAttribute((const void*)k_sinv_tail, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  if (new_sinv_plan) {  // (the attribute belongs to an instance)
+    HIPCHK(hipFuncSetAttribute((const void*)k_sinv_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void*)k_sinv_tail<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  }
   HIPCHK(hipEventRecord(D->ev[6], st));
   // SCILMM_SINV_GENERIC=1: the gather kernel for the dense tail as well (the round's first form)
-  const bool tail_kernel = D->use_mfma && !read_tuning().sinv_generic;
+  const Tuning tune = read_tuning();
+  const bool tail_kernel = D->use_mfma && !tune.sinv_generic;
+  // deterministic mode: every entry of Z from a sum whose order the plan fixes (k_sinv_tail<true> / k_sinv_cc_ordered and
+  // their folds; plain stores).  SCILMM_SINV_REVERSE=1 turns the dispatch order of the two round: the bits must not move.
+  const bool reverse = D->det && tune.sinv_reverse;
   for (int32_t l = S.nlevels - 1; l >= 0; --l) {
     const int64_t t0 = D->lv_tile_ptr[l], nt = D->lv_tile_ptr[l + 1] - t0;
     const int32_t f0 = D->lv_ptr[l], f1 = D->lv_ptr[l + 1];
@@ -33,22 +40,14 @@ int selected_inverse(scilmm_factor* fac) {
     hipLaunchKernelGGL(k_sinv_cc0, dim3((unsigned)(f1 - f0)), dim3(256), 0, st, D->v, D->d_level_fronts + f0, fac->L,
                        (const double*)fac->invD);
     if (tf >= 0) {
-      const int32_t jj = tf - S.dense_first;
-      const int64_t i0 = D->sinv_work_ptr[(size_t)jj], i1 = D->sinv_work_ptr[(size_t)jj + 1];
-      if (i1 > i0) {
-        const int32_t wtf = S.sn_start[tf + 1] - S.sn_start[tf];
-        hipLaunchKernelGGL(k_sinv_zero, dim3(1, (unsigned)wtf), dim3(256), 0, st, D->v, (const int32_t*)(D->d_sinv_tail_fronts + jj), fac->L);
-        D->n_float_atomic++;
-        hipLaunchKernelGGL(k_sinv_tail, dim3((unsigned)(i1 - i0)), dim3(512), sizeof(double) * (size_t)(2 * KBA * LDB), st, D->v,
-                           S.dense_first, (const SinvWork*)(D->d_sinv_work + i0), fac->L, (const double*)D->d_ybuf,
-                           (const int64_t*)D->d_yoff, (const int32_t*)D->d_col_front, (const double*)D->d_zeros);
-      }
+      sinv_tail(D, fac, st, tf - S.dense_first, reverse);
       // the gather kernel takes the non-tail fronts' tiles only
       sinv_w(D, fac, st, D->d_sinv_pre_tiles + D->sinv_pre_ptr[(size_t)l], D->sinv_pre_ptr[(size_t)l + 1] - D->sinv_pre_ptr[(size_t)l]);
     } else {
       sinv_w(D, fac, st, tiles, nt);  // ... or all of the level's
     }
-    sinv_cc(D, fac, st, tiles, nt, ydf);
+    if (D->det) sinv_cc_ordered(D, fac, st, l, ydf, reverse);
+    else sinv_cc(D, fac, st, tiles, nt, ydf);
   }
   HIPCHK(hipEventRecord(D->ev[7], st));
   HIPCHK(hipStreamSynchronize(st));

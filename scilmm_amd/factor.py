@@ -491,7 +491,8 @@ class Factor(object):
     def inverse_traces(self):
         """tr(V^-1 A_k) for every matrix of the analysis, exactly: the selected inverse on the supernodal factor (Takahashi
         recursion on the device, in place) followed by one pass over each A_k's pattern.  CONSUMES the factor: it must be
-        refactorized before the next solve."""
+        refactorized before the next solve.  On a deterministic handle the inverse is summed in a fixed order (no
+        floating-point atomics): the same factor gives the same bits, entries and traces."""
         if getattr(self, "_pending", None) is not None:
             self.wait()
         check(lib().scilmm_selected_inverse(self._h), self.sym._h)  # (a refusal leaves the factor, and its sigma2, as they were)
