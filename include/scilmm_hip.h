@@ -408,6 +408,29 @@ int scilmm_rows_block_dev(scilmm_factor* fac, const int64_t* d_indptr, const int
 int scilmm_selected_inverse(scilmm_factor* fac);
 int scilmm_inverse_traces(scilmm_factor* fac, double* out);
 
+/* Entries of the inverse on V's OWN pattern, read off an inverted handle: with Z = V^-1 the call writes the entries of
+ *     M = alpha * diag(s) Z diag(s) + beta * T T'
+ * that lie on the pattern of V (a subset of L's pattern: the value-assembly maps give their positions in the panels).
+ *   d_diag : n doubles, d_diag[i] = M_ii, i in the ORIGINAL order of the matrices' rows.
+ *   d_off  : nnz_pattern doubles, d_off[e] = M_ij for pattern slot e in the slot order of scilmm_symbolic_get "pat_colptr" /
+ *            "pat_row" (the order of the resident values; the diagonal slot comes first in each column), i and j the slot's
+ *            two individuals.  A diagonal slot holds the bits of d_diag.
+ *   d_s    : n doubles in the original order, NULL = all ones.
+ *   d_T    : n x c row-major in the original order, 0 <= c <= 32; NULL or c = 0: no low-rank term.  Rows are read 16 bytes
+ *            at a time when c is even and d_T 16-byte aligned, else 8; the bits are the same.
+ * Either output may be NULL to skip it.  Everything is a device pointer; two streaming kernels (one over the n diagonals,
+ * one over the slots) are enqueued on the handle's stream without synchronising.  One thread owns one output element and
+ * stores it once: no floating-point atomics, no scratch reductions, the dot product over c in ascending order, so the bits
+ * depend on the inputs alone in either mode of the handle and scilmm_timing.n_float_atomic_launches is not touched.  The
+ * handle stays inverted and no work buffer is written: the call may be repeated with other s, T, alpha, beta.
+ * SCILMM_ERR_ARG before anything is dereferenced: a null fac, c outside 0 .. 32, both outputs NULL.  SCILMM_ERR_STATE with a
+ * message: a handle that scilmm_selected_inverse has not inverted (so never a distributed one).  With alpha = -1, s = the
+ * diagonal residual variances and T = C R^-1 - E H this is the prediction error (co)variance of every total genetic value
+ * up to the diagonal's + e_i (scilmm_amd.BLUP.reliability_all, .prediction_error_covariance,
+ * .leave_one_out are the interfaces).  No counterpart in the reference. */
+int scilmm_inverse_pattern_dev(scilmm_factor* fac, double alpha, const double* d_s, double beta, const double* d_T, int32_t c,
+                               double* d_diag, double* d_off);
+
 /* BASELINE configs[4] ("fp64 factor with fp32 MFMA fronts"): bits = 32 runs the products of the dense-tail update on
  * the fp32 matrix pipe: the finished tail panels get an fp32 shadow (one rounding per entry; + 50 % tail storage -- of a rank's own
  * panels and ring slots when the tail is distributed --, dropped when the device has no room for it: the operands are then

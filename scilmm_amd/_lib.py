@@ -69,7 +69,7 @@ SYMBOLS = [
     "scilmm_dominance_values_device", "scilmm_values_download",
     "scilmm_order", "scilmm_fill_count",
     "scilmm_dist_init", "scilmm_dist_work_size", "scilmm_dist_set_work", "scilmm_dist_layout", "scilmm_factor_sizes", "scilmm_factor_create_external", "scilmm_he_moments", "scilmm_set_front_precision",
-    "scilmm_selected_inverse", "scilmm_inverse_traces",
+    "scilmm_selected_inverse", "scilmm_inverse_traces", "scilmm_inverse_pattern_dev",
     "scilmm_mm_read", "scilmm_mm_export", "scilmm_mm_error", "scilmm_mm_free",
     "scilmm_dominance", "scilmm_dominance_dev", "scilmm_dominance_error",
     "scilmm_csr_spmm_dev", "scilmm_csr_spmm_error",
@@ -154,6 +154,7 @@ def lib():
     L.scilmm_get_deterministic.argtypes = [vp, P(i32)]
     L.scilmm_selected_inverse.argtypes = [vp]
     L.scilmm_inverse_traces.argtypes = [vp, vp]
+    L.scilmm_inverse_pattern_dev.argtypes = [vp, dbl, vp, dbl, vp, i32, vp, vp]
     L.scilmm_he_moments.argtypes = [vp, i32, i32, P(dbl), P(dbl)]
     L.scilmm_dist_init.argtypes = [vp, i32, i32, vp, vp, vp]
     L.scilmm_factor_sizes.argtypes = [vp, P(i64), P(i64), P(i64)]

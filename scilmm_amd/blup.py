@@ -19,6 +19,9 @@ individual come back.  The reference stops at the variance components and the co
     blup.effects(0)                   # all n predicted values of component 0: one backward half-solve, one SpMM
     blup.reliability(0, individuals)  # dict of u, pev, reliability, self_rel
     blup.predict(rows, self_rel, 0)   # the same for relatives without a phenotype
+    blup.reliability_all("total")     # everybody at once from ONE selected inverse, and with it
+    blup.prediction_error_covariance()   # PEV / PEC of every pair of relatives, CSR on V's pattern
+    blup.leave_one_out()              # leave-one-out residuals, variances, studentised residuals: no refit
 
 There is no CPU form: without a GPU or the built library the constructor raises ``ScilmmError``.
 """
@@ -63,6 +66,23 @@ def check_rows(rows, self_rel, n):
     return (R.indptr.astype(np.int64), R.indices.astype(np.int32), np.ascontiguousarray(R.data, dtype=np.float64)), self_rel
 
 
+def check_all_component(k, K):
+    """The component argument of ``BLUP.reliability_all``: ``"total"`` always, the index 0 when there is one relationship
+    matrix (K == 2: component 0 IS the total genetic value).  ValueError otherwise -- for an index with K >= 3 naming
+    ``reliability()``, whose column path is the exact one for a single component among several."""
+    if isinstance(k, str):
+        if k != "total":
+            raise ValueError("k must be \"total\" (or 0 when there is one relationship matrix)")
+        return k
+    if not (isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_)) and 0 <= k < K - 1):
+        raise ValueError("k must be \"total\" (or 0 when there is one relationship matrix), got %r" % (k,))
+    if K != 2:
+        raise ValueError("reliability_all(%d) with %d relationship matrices: diag(A_k V^-1 A_k) couples pairs of relatives that "
+                         "need not lie on the factor's pattern, so one component among several is not exact from the selected "
+                         "inverse; use reliability(%d) (one sweep column per individual), or k=\"total\"" % (k, K - 1, k))
+    return int(k)
+
+
 class BLUP(WhitenedModel):
     """Predicted random effects, prediction error variances and reliabilities under V = sum_k sigma2[k] mats[k].
 
@@ -77,6 +97,8 @@ class BLUP(WhitenedModel):
             raise ValueError("sigma2 must have one entry per matrix")
         self.beta = la.solve_triangular(self.R, self.u, lower=False)      # GLS fixed effects (C' V^-1 C)^-1 C' V^-1 y
         self._dv = None                                                    # V^-1 (y - C beta), original order (effects)
+        self._y = np.asarray(y, dtype=np.float64).ravel()
+        self._inv = None                                                   # the whole-cohort pass (_inverse_pass)
 
     def _component(self, k):
         """(weights of the matrices in G, factor that takes g' P_V y to the predicted value)."""
@@ -164,3 +186,102 @@ class BLUP(WhitenedModel):
             self.sym.sync()
             out += (scale * w[j]) * dY.cpu().numpy()
         return out
+
+    # ---- everybody at once, from the selected inverse.  With G the total genetic covariance,
+    #      E = sigma2[K-1] mats[K-1] diagonal (e_i its entries), V = G + E, Z = V^-1, H = Z C R^-1 and T = C R^-1 - E H = G H:
+    #          G - G P_V G = E - E Z E + T T'        (G = V - E, so G Z G = V - 2 E + E Z E)
+    #          P_V         = Z - H H'                u = G P_V y = y - C beta - E r,   r = P_V y
+    #      so the diagonal of Z, and its entries on V's pattern for pairs of relatives, are all that is needed of the inverse.
+
+    def _last_is_diagonal(self):
+        ix = self.sym._indices[self.sym.K - 1]
+        return ix.size == self.n and np.array_equal(ix, np.arange(self.n))
+
+    def _diagonals(self):
+        """(e, [diag(mats[k]) for k < K - 1]) in the matrices' row order, from the values resident on the device."""
+        sym, P = self.sym, self.factor.P()
+        first = sym.get("pat_colptr")[:-1]                         # (the diagonal slot comes first in its column)
+        out = []
+        for k in range(sym.K):
+            v, d = sym.values_slots(k), np.empty(self.n)
+            d[P] = v if v.size == self.n else v[first]             # (a diagonal-only matrix keeps one value per column)
+            out.append(d)
+        return self._s2[sym.K - 1] * out[-1], out[:-1]
+
+    def _inverse_pass(self):
+        """The pass the three whole-cohort methods share, run once and kept: ``V^-1 [C | y]`` from one device solve, ``H``,
+        ``T`` and ``r`` from it (n x c arrays: torch), then the selected inverse, ``scilmm_inverse_pattern_dev`` twice --
+        ``-E Z E + T T'`` on the pattern and its diagonal, ``Z - H H'`` on the diagonal -- and a refactorization at the
+        object's own sigma2, so that the resident factor, a scan on it and this object go on as before.  Costs one inversion
+        plus one factorization; on a deterministic handle the restored factor has the bits it had."""
+        if self._inv is not None:
+            return self._inv
+        from .SparseCholesky import _solve_on_device
+        torch, vp, c, n, sym, fac = self.torch, C.c_void_p, self.c, self.n, self.sym, self.factor
+        e, gdiag = self._diagonals()
+        dB = torch.from_numpy(np.ascontiguousarray(np.hstack([self.covariates, self._y[:, None]]))).cuda()
+        dS = _solve_on_device(torch, sym, fac, dB)                 # Z [C | y], original order
+        dRinv = torch.from_numpy(la.solve_triangular(self.R, np.eye(c), lower=False)).cuda()
+        de = torch.from_numpy(e).cuda()
+        dH = (dS[:, :c] @ dRinv).contiguous()                      # Z C R^-1
+        dT = (dB[:, :c] @ dRinv - de[:, None] * dH).contiguous()   # C R^-1 - E H = G H
+        dr = dS[:, c] - dH @ torch.from_numpy(self.u).cuda()       # P_V y   (H'y = R^-T C' Z y = u)
+        nnz = int(sym.info().nnz_pattern)
+        dpev, dpvd = (torch.empty((n,), dtype=torch.float64, device="cuda") for _ in range(2))
+        doff = torch.empty((max(nnz, 1),), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        fac.selected_inverse()
+        try:
+            fac.inverse_pattern_dev(vp(dpev.data_ptr()), vp(doff.data_ptr()), -1.0, vp(de.data_ptr()), 1.0, vp(dT.data_ptr()), c)
+            fac.inverse_pattern_dev(vp(dpvd.data_ptr()), None, 1.0, None, -1.0, vp(dH.data_ptr()), c)
+            sym.sync()
+        finally:
+            fac.refactorize(self._s2)                              # (whatever happened: the factor is the caller's again)
+        r = dr.cpu().numpy()
+        self._inv = dict(e=e, gdiag=gdiag, r=r, pvd=dpvd.cpu().numpy(), pev=e + dpev.cpu().numpy(),
+                         u=self._y - self.covariates @ self.beta - e * r, doff=doff[:nnz])
+        return self._inv
+
+    def _whole_cohort(self):
+        if not self._last_is_diagonal():
+            raise ValueError("the last matrix (the residual covariance) must be diagonal -- the identity or record weights -- for "
+                             "the whole-cohort forms; reliability() has no such condition")
+        self._check_factor()
+        return self._inverse_pass()
+
+    def reliability_all(self, k="total"):
+        """``reliability`` for ALL n individuals from one selected inverse instead of one sweep column each: the same dict
+        (``u``, ``pev``, ``reliability``, ``self_rel``) in the matrices' row order, for the total genetic value (``"total"``; with
+        one relationship matrix also ``k = 0``, which is the total).  Exact: ``PEV_i = e_i - e_i^2 (V^-1)_ii + |T_i.|^2``.  A
+        single component among several (K >= 3 and an index) is not exact from a selected inverse: ValueError, use
+        ``reliability``.  The last matrix must be diagonal.  The first of ``reliability_all`` / ``prediction_error_covariance``
+        / ``leave_one_out`` costs one inversion plus one factorization (the factor is consumed and restored at this object's
+        sigma2; bit for bit on a deterministic handle); the others then cost nothing."""
+        k = check_all_component(k, self.sym.K)
+        inv = self._whole_cohort()
+        if k == "total":
+            scale, self_rel = 1.0, sum(s * d for s, d in zip(self._s2[:-1], inv["gdiag"]))
+        else:
+            scale, self_rel = float(self._s2[k]), inv["gdiag"][k].copy()
+        var = scale * self_rel
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = 1.0 - inv["pev"] / var
+        return {"u": inv["u"].copy(), "pev": inv["pev"].copy(), "reliability": rel, "self_rel": self_rel}
+
+    def prediction_error_covariance(self):
+        """The prediction error covariance of the total genetic values on V's pattern, as a symmetric SciPy CSR in the
+        matrices' row order: PEV on the diagonal, ``PEC_ij = -e_i e_j (V^-1)_ij + T_i. . T_j.`` for every pair of relatives.
+        The error variance of the difference of two relatives is ``PEV_i + PEV_j - 2 PEC_ij``.  Cost: see ``reliability_all``."""
+        inv = self._whole_cohort()
+        return self.factor.pattern_csr(inv["doff"].cpu().numpy(), inv["pev"])
+
+    def leave_one_out(self):
+        """Leave-one-out cross-validation of every record with the fixed effects re-estimated, without a refit: with
+        ``r = P_V y`` a dict of ``residual`` (``r_i / (P_V)_ii``: the record minus its prediction from all the others),
+        ``variance`` (``1 / (P_V)_ii``), ``studentized`` (``r_i / sqrt((P_V)_ii)``), ``prediction`` (``y - residual``) and
+        ``leverage`` (``(P_V)_ii = (V^-1)_ii - |H_i.|^2``).  Cost: see ``reliability_all``."""
+        inv = self._whole_cohort()
+        r, p = inv["r"], inv["pvd"]
+        res = r / p
+        return {"residual": res, "variance": 1.0 / p, "studentized": r / np.sqrt(p), "prediction": self._y - res,
+                "leverage": p.copy()}

@@ -470,6 +470,18 @@ int scilmm_inverse_traces(scilmm_factor* fac, double* out) {
   return inverse_traces(fac, out);
 }
 
+int scilmm_inverse_pattern_dev(scilmm_factor* fac, double alpha, const double* d_s, double beta, const double* d_T, int32_t c,
+                               double* d_diag, double* d_off) {
+  if (!fac || c < 0 || c > 32 || (!d_diag && !d_off)) return SCILMM_ERR_ARG;  // (before anything is dereferenced)
+  if (!fac->sym || !fac->sym->S) return SCILMM_ERR_ARG;
+  DevGuard guard(fac->sym);
+  if (!fac->inverted || !fac->sym->device) {
+    fac->sym->err = "scilmm_inverse_pattern_dev: call scilmm_selected_inverse first";
+    return SCILMM_ERR_STATE;
+  }
+  return inverse_pattern(fac, alpha, d_s, beta, d_T, c, d_diag, d_off);
+}
+
 int scilmm_sync(scilmm_symbolic* sym) {
   if (!sym || !sym->device) return SCILMM_ERR_ARG;
   DevGuard guard(sym);

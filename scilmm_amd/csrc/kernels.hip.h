@@ -3581,6 +3581,74 @@ __global__ __launch_bounds__(256) void k_sinv_trace_diag(int32_t n, const int64_
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Entries of M = alpha diag(s) Z diag(s) + beta T T' on V's own pattern, read off the inverted panels (scilmm_inverse_pattern_dev;
+// DESIGN.md section 17).  a, b: the pair's two individuals in the ORIGINAL order (perm of the permuted labels); s (may be null: 1)
+// and T (row-major n x c, c <= 32; c = 0: no low-rank term) are in that order.  One thread owns one entry: the dot product runs
+// over k ascending in explicit fmas and the three products are rounded one by one, so the bits depend on the inputs alone and the
+// diagonal slot of k_invpat_slots holds the bits of k_invpat_diag.  VEC: c is even and T 16-byte aligned, rows read as double2.
+template <bool VEC>
+__device__ __forceinline__ double invpat_entry(double alpha, const double* __restrict__ s, double beta, const double* __restrict__ T,
+                                               int32_t c, int32_t a, int32_t b, double z) {
+  double dot = 0.0;
+  const double* ta = T + (int64_t)a * c;
+  const double* tb = T + (int64_t)b * c;
+  if (VEC) {
+    for (int32_t k = 0; k < c; k += 2) {
+      const double2 x = *reinterpret_cast<const double2*>(ta + k), y = *reinterpret_cast<const double2*>(tb + k);
+      dot = fma(x.x, y.x, dot);
+      dot = fma(x.y, y.y, dot);
+    }
+  } else {
+    for (int32_t k = 0; k < c; ++k) dot = fma(ta[k], tb[k], dot);
+  }
+  const double sa = s ? s[a] : 1.0, sb = s ? s[b] : 1.0;
+  return fma(beta, dot, __dmul_rn(alpha, __dmul_rn(__dmul_rn(sa, z), sb)));
+}
+
+// diag[perm[j]] = M_jj for the n permuted columns: 8 (diag_dst) + 4 (perm) + 8 (the gathered Z entry) + 8 (s) + 8 c (one row of
+// T) bytes read and 8 stored per individual
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_invpat_diag(int32_t n, const int32_t* __restrict__ perm, const int64_t* __restrict__ diag_dst,
+                                                     const double* __restrict__ Z, double alpha, const double* __restrict__ s,
+                                                     double beta, const double* __restrict__ T, int32_t c, double* __restrict__ diag) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int32_t a = perm[j];
+  diag[a] = invpat_entry<VEC>(alpha, s, beta, T, c, a, a, Z[diag_dst[j]]);
+}
+
+// off[e] = M_ij for the 256 consecutive pattern slots of a workgroup (slot order of pat_colptr / pat_row: diagonal slot first in
+// each column).  Every column holds at least its diagonal slot, so the slots e0 .. e0 + 255 lie in the columns j0 .. j0 + 255,
+// j0 the column of e0: j0 by a bisection of pat_colptr that is uniform in the workgroup (scalar loads), the 256 column ends behind
+// it in LDS (one coalesced read), and a thread finds its own column in at most 8 LDS steps -- instead of a 20-step bisection
+// through global memory per slot, or a thread per column (2 to 209 slots each on a pedigree).  Per slot 8 (asm_dst) + 4
+// (pat_row) + 8 (the gathered Z entry) + 8 (two perm entries) + 16 (two s) + 16 c (two rows of T) bytes read, 8 stored, and 8 per
+// column of the workgroup for the column ends.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_invpat_slots(DevSym S, int64_t nnz, const double* __restrict__ Z, double alpha,
+                                                      const double* __restrict__ s, double beta, const double* __restrict__ T,
+                                                      int32_t c, double* __restrict__ off) {
+  __shared__ int64_t cend[256];  // cend[d] = pat_colptr[j0 + d + 1]: one past the last slot of column j0 + d
+  const int t = threadIdx.x;
+  const int64_t e0 = (int64_t)blockIdx.x * 256, e = e0 + t;
+  int32_t lo = 0, hi = S.n;  // j0: the first column whose end lies behind e0
+  while (lo < hi) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (S.pat_colptr[mid + 1] <= e0) lo = mid + 1; else hi = mid;
+  }
+  const int32_t j0 = lo;
+  cend[t] = (int64_t)j0 + t < S.n ? S.pat_colptr[(int64_t)j0 + t + 1] : INT64_MAX;
+  __syncthreads();
+  if (e >= nnz) return;
+  int dl = 0, dh = t;  // the column of slot e0 + t is one of j0 .. j0 + t
+  while (dl < dh) {
+    const int mid = (dl + dh) >> 1;
+    if (cend[mid] <= e) dl = mid + 1; else dh = mid;
+  }
+  const int32_t a = S.perm[j0 + dl], b = S.perm[S.pat_row[e]];
+  off[e] = invpat_entry<VEC>(alpha, s, beta, T, c, a, b, Z[S.asm_dst[e]]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // IBD (numerator relationship) values ON THE DEVICE, straight into the value slots of the engine (SURVEY 8f rank 1;
 // reference scilmm/Matrices/Numerator.py:5-38 computes A = L D L^T in interpreted Python).  Tabular recursion on the

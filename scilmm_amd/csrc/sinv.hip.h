@@ -87,4 +87,29 @@ int inverse_traces(scilmm_factor* fac, double* out) {
   return SCILMM_OK;
 }
 
+// M = alpha diag(s) Z diag(s) + beta T T' on V's pattern from the inverted panels: two streaming kernels on the handle's stream,
+// nothing waited for, no work buffer touched (the panels, the plan's maps and the caller's arrays are all they read).
+int inverse_pattern(scilmm_factor* fac, double alpha, const double* d_s, double beta, const double* d_T, int32_t c, double* d_diag,
+                    double* d_off) {
+  scilmm_symbolic* sym = fac->sym;
+  Dev* D = (Dev*)sym->device;
+  const Symbolic& S = *sym->S;
+  hipStream_t st = D->stream;
+  if (!d_T) c = 0;
+  const double* Z = (const double*)fac->L;
+  const bool vec = c > 0 && c % 2 == 0 && ((uintptr_t)d_T & 15) == 0;  // rows of T as double2
+  if (d_diag && S.n > 0) {
+    const dim3 grid((unsigned)((S.n + 255) / 256));
+    if (vec) hipLaunchKernelGGL(k_invpat_diag<true>, grid, dim3(256), 0, st, S.n, D->v.perm, D->v.diag_dst, Z, alpha, d_s, beta, d_T, c, d_diag);
+    else hipLaunchKernelGGL(k_invpat_diag<false>, grid, dim3(256), 0, st, S.n, D->v.perm, D->v.diag_dst, Z, alpha, d_s, beta, d_T, c, d_diag);
+  }
+  if (d_off && S.nnz_pattern > 0) {
+    const dim3 grid((unsigned)((S.nnz_pattern + 255) / 256));
+    if (vec) hipLaunchKernelGGL(k_invpat_slots<true>, grid, dim3(256), 0, st, D->v, S.nnz_pattern, Z, alpha, d_s, beta, d_T, c, d_off);
+    else hipLaunchKernelGGL(k_invpat_slots<false>, grid, dim3(256), 0, st, D->v, S.nnz_pattern, Z, alpha, d_s, beta, d_T, c, d_off);
+  }
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
 }  // namespace

@@ -493,13 +493,61 @@ class Factor(object):
         recursion on the device, in place) followed by one pass over each A_k's pattern.  CONSUMES the factor: it must be
         refactorized before the next solve.  On a deterministic handle the inverse is summed in a fixed order (no
         floating-point atomics): the same factor gives the same bits, entries and traces."""
+        self.selected_inverse()
+        out = np.empty(self.sym.K)
+        check(lib().scilmm_inverse_traces(self._h, ptr(out)), self.sym._h)
+        return out
+
+    def selected_inverse(self):
+        """The selected inverse alone (``scilmm_selected_inverse``): every stored entry of the factor is replaced, in place, by
+        the entry of ``(V[P][:, P])^-1`` at its position.  CONSUMES the factor like ``inverse_traces``, which is this call
+        followed by the traces; ``inverse_pattern_dev`` / ``inverse_on_pattern`` read the entries on V's pattern."""
         if getattr(self, "_pending", None) is not None:
             self.wait()
         check(lib().scilmm_selected_inverse(self._h), self.sym._h)  # (a refusal leaves the factor, and its sigma2, as they were)
         self._s2, self._pending = None, None  # (the panels hold entries of the inverse from here on)
-        out = np.empty(self.sym.K)
-        check(lib().scilmm_inverse_traces(self._h, ptr(out)), self.sym._h)
-        return out
+        return self
+
+    def inverse_pattern_dev(self, ddiag_ptr, doff_ptr, alpha=1.0, ds_ptr=None, beta=0.0, dT_ptr=None, c=0):
+        """``M = alpha diag(s) V^-1 diag(s) + beta T T'`` on V's pattern from an inverted factor (``scilmm_inverse_pattern_dev``):
+        ``ddiag_ptr`` n doubles in the matrices' row order, ``doff_ptr`` one double per pattern slot (``Symbolic.get`` of
+        ``pat_colptr`` / ``pat_row``), either None to skip it; ``ds_ptr`` (n, None = ones) and ``dT_ptr`` (n x c row-major,
+        c <= 32) in the matrices' row order.  Device pointers; enqueues without synchronising; the factor stays inverted."""
+        check(lib().scilmm_inverse_pattern_dev(self._h, float(alpha), ds_ptr, float(beta), dT_ptr, int(c), ddiag_ptr, doff_ptr),
+              self.sym._h)
+
+    def pattern_csr(self, off, diag=None):
+        """The symmetric SciPy CSR, in the matrices' row order, of one value per pattern slot (``off``, the slot order of
+        ``inverse_pattern_dev``); ``diag`` (row order) replaces the diagonal slots' values when given.  Needs the host copy of
+        the pattern (``ScilmmError`` after ``release_host_maps``)."""
+        sym, n = self.sym, self.n
+        colptr, rows, P = sym.get("pat_colptr"), sym.get("pat_row"), self.P()
+        if rows.size != colptr[-1]:
+            raise _lib.ScilmmError("the host copy of the pattern was released (release_host_maps): no CSR can be built")
+        off = np.asarray(off, dtype=np.float64)
+        if off.shape != rows.shape:
+            raise ValueError("one value per pattern slot is expected")
+        i, j = P[np.repeat(np.arange(n), np.diff(colptr))], P[rows]
+        lower = i != j
+        d = off[colptr[:-1]] if diag is None else np.asarray(diag, dtype=np.float64)[P]
+        M = sp.coo_matrix((np.concatenate([off[lower], off[lower], d]),
+                           (np.concatenate([i[lower], j[lower], P]), np.concatenate([j[lower], i[lower], P]))), shape=(n, n)).tocsr()
+        M.sort_indices()
+        return M
+
+    def inverse_on_pattern(self):
+        """``(diag, M)``: the diagonal of ``V^-1`` (row order of the matrices) and the symmetric SciPy CSR of ``V^-1`` on V's
+        pattern, both read off this factor after ``selected_inverse`` / ``inverse_traces`` (tests, and callers who want the
+        entries; device buffers through torch)."""
+        import torch
+        vp = C.c_void_p
+        dd = torch.empty((self.n,), dtype=torch.float64, device="cuda")
+        do = torch.empty((max(1, int(self.sym.info().nnz_pattern)),), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        self.inverse_pattern_dev(vp(dd.data_ptr()), vp(do.data_ptr()))
+        self.sym.sync()
+        diag, off = dd.cpu().numpy(), do.cpu().numpy()[:int(self.sym.info().nnz_pattern)]
+        return diag, self.pattern_csr(off, diag)
 
     def logdet(self):
         out = C.c_double(0.0)
