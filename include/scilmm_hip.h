@@ -368,6 +368,48 @@ int scilmm_scan_panel_dev(scilmm_factor* fac, int32_t r, const double* d_Y, int6
  * follows it: ms[0] k_scan_panel, ms[1] k_panel_fold (tools/panel_timing.py).  No counterpart in the reference. */
 int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Binary traits: the saddlepoint (SPA) p-value of the score test for the r markers of a plain scan block, queued BEHIND that
+ * block (scilmm_scan_block_dev, _bed_dev or _dosage_dev with the same marker arguments and the same r) on the handle's stream.
+ * With the working vector y~ of a logistic mixed model in the place of y (scilmm_amd.glmm), the block's statistics hold the
+ * score b = g~' P y~ and its variance a = g~' P g~; the call reads them where the block wrote them and re-reads the marker rows.
+ *   d_stats : the block's (q + 4) x r statistics, q = c + 1.
+ *   d_R, d_u: c x c upper triangular R with R'R = w(C)'w(C), row-major, and u = R^-T w(C)'w(y~) (c numbers).
+ *   d_mu    : n fitted probabilities in the ORIGINAL order of the individuals, each in (0, 1).
+ *   d_C     : n x c covariates, row-major, original order.   c: 1 .. 31.
+ *   d_Minv  : (C' W C)^-1, c x c, W = diag(mu (1 - mu)).
+ *   cutoff  : >= 0; a marker with |b / sqrt(a)| <= cutoff is not saddlepointed (flag 0).
+ *   d_spa   : 7 x r row-major, rows  log_p | a_w | s | zeta_hi | zeta_lo | iters | flag:
+ *             g^ = g~ - C Minv C'W g~,  a_w = sum w_i g^_i^2,  s = b sqrt(a_w / a);  zeta_hi > 0 > zeta_lo are the roots of
+ *             K'(zeta) = +-|s| for the cumulant generating function K of sum g^_i (y_i - mu_i) under independent Bernoulli(mu_i)
+ *             draws (safeguarded Newton from 0, |step| <= 1e-13 max(1, |zeta|), at most 64 steps per root; iters = the larger
+ *             count); log_p = log of the sum of the two Lugannani-Rice tails, taken in logarithms (finite far beyond where p
+ *             underflows).  flag 1: both roots converged and both tail arguments are finite and positive.  flag 2: anything
+ *             else (|s| outside the support of the statistic, the step limit, a non-positive argument): log_p is the normal
+ *             value log(2 Phi(-|b| / sqrt(a))).  flag 0: not attempted (no observed value, no variation, a <= 0, or within the
+ *             cutoff): the other six rows are NaN.
+ * One workgroup per marker, fixed thread stride and fixed reduction trees, no atomics: a marker's seven numbers depend on its
+ * inputs alone, in either mode of the handle, and the three input forms of the same hard calls give the same bits;
+ * scilmm_timing.n_float_atomic_launches is not touched.  Nothing of the work buffers is written (a scilmm_scan_panel_dev may
+ * still follow the block).  The call keeps g^ in a scratch of 128 x n doubles that the first call on a handle allocates (the
+ * stream is synchronised before that) and no later call reallocates.  Enqueued without synchronising.
+ * SCILMM_ERR_ARG before anything is dereferenced: a null pointer, r outside 1 .. 128, c outside 1 .. 31, cutoff negative or
+ * NaN, and whatever the plain entry point of the form rejects in the marker arguments.  Refusals as for the half-solves
+ * (SCILMM_ERR_STATE, the handle left usable): a distributed handle, fp32-product fronts, a factor consumed by the selected
+ * inverse.  scilmm_amd.glmm.BinaryScan is the interface.  No counterpart in the reference. */
+int scilmm_scan_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_R,
+                        const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff,
+                        double* d_spa);
+int scilmm_scan_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                            int32_t flags, int32_t r, const double* d_stats, const double* d_R, const double* d_u, const double* d_mu,
+                            const double* d_C, int32_t c, const double* d_Minv, double cutoff, double* d_spa);
+int scilmm_scan_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                               const int32_t* d_sample, int32_t r, const double* d_stats, const double* d_R, const double* d_u,
+                               const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff, double* d_spa);
+
+/* HIP-event time of the last scilmm_scan_spa*_dev on the handle, in milliseconds, valid after the scilmm_sync that follows it:
+ * ms[0] k_scan_spa (tools/spa_timing.py).  No counterpart in the reference. */
+int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms);
+
 /* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
  * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y
  * (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1) per column by the scan's algebra: predicted value, prediction error variance

@@ -505,6 +505,33 @@ def estimate_var_comps(cholesky_func, mats, covariates, y, reml=True, sim_num=10
     return np.exp(optObj.x)
 
 
+def _ai_information(fac, mats, covariates, y):
+    """The average-information matrix ``AI_kl = 1/2 y' P A_k P A_l P y`` (K x K, symmetrised) at the resident factor ``fac`` of
+    ``sum_k sigma2_k mats[k]``: what ``_ai_reml`` iterates on and ``scilmm_amd.glmm`` takes its upper-left block of."""
+    # P y and P A_k P y through the resident factor: 1 + K multi-column solves
+    hip = _hip_factor_of(fac, mats)
+    if hip is not None:
+        # ... in HBM: V^-1 [C | y] (one sweep), K SpMMs on one column, one K-column sweep
+        torch, sym = hip
+        pr = _DeviceProjector(torch, sym, fac, covariates, y)
+        Py_d = pr.project_solved(pr.Viy[:, None])
+        APy_d = torch.cat([_spmm_on_device(torch, sym, k, Py_d) for k in range(len(mats))], dim=1)
+        AI_d = 0.5 * (APy_d.T @ pr.project(APy_d)).cpu().numpy()
+        return 0.5 * (AI_d + AI_d.T)
+    ViC = fac(covariates)
+    G = la.cho_factor(covariates.T.dot(ViC))
+
+    def proj(Z):
+        ViZ = fac(Z)
+        return ViZ - ViC.dot(la.cho_solve(G, covariates.T.dot(ViZ)))
+
+    Py = proj(y)
+    APy = np.stack([m.dot(Py) for m in mats], axis=1)          # n x K
+    PAPy = proj(APy)
+    AI = 0.5 * APy.T.dot(PAPy)
+    return 0.5 * (AI + AI.T)
+
+
 def _ai_reml(cholesky_func, mats, covariates, y, x0, reml, sim_num, verbose, max_iter=50, tol=1e-8, ftol=1e-7):
     """Average-information REML: the branch the reference leaves as a stub (``raise NotImplementedError('AI-REML is
     broken')``, SparseCholesky.py:128-130).  Newton-type iteration on sigma2 itself,
@@ -526,28 +553,7 @@ def _ai_reml(cholesky_func, mats, covariates, y, x0, reml, sim_num, verbose, max
     rng_state = np.random.get_state()
 
     def information(fac):
-        # P y and P A_k P y through the resident factor: 1 + K multi-column solves
-        hip = _hip_factor_of(fac, mats)
-        if hip is not None:
-            # ... in HBM: V^-1 [C | y] (one sweep), K SpMMs on one column, one K-column sweep
-            torch, sym = hip
-            pr = _DeviceProjector(torch, sym, fac, covariates, y)
-            Py_d = pr.project_solved(pr.Viy[:, None])
-            APy_d = torch.cat([_spmm_on_device(torch, sym, k, Py_d) for k in range(len(mats))], dim=1)
-            AI_d = 0.5 * (APy_d.T @ pr.project(APy_d)).cpu().numpy()
-            return 0.5 * (AI_d + AI_d.T)
-        ViC = fac(covariates)
-        G = la.cho_factor(covariates.T.dot(ViC))
-
-        def proj(Z):
-            ViZ = fac(Z)
-            return ViZ - ViC.dot(la.cho_solve(G, covariates.T.dot(ViZ)))
-
-        Py = proj(y)
-        APy = np.stack([m.dot(Py) for m in mats], axis=1)          # n x K
-        PAPy = proj(APy)
-        AI = 0.5 * APy.T.dot(PAPy)
-        return 0.5 * (AI + AI.T)
+        return _ai_information(fac, mats, covariates, y)
 
     exact_hip = _is_hip(cholesky_func) and bool(getattr(cholesky_func, 'exact_trace', False))
 

@@ -80,6 +80,7 @@ SYMBOLS = [
     "scilmm_scan_block_dosage_dev", "scilmm_scan_block_dosage_gram_dev",
     "scilmm_scan_block_gxe_dev", "scilmm_scan_block_bed_gxe_dev", "scilmm_scan_block_dosage_gxe_dev", "scilmm_gxe_timing",
     "scilmm_scan_panel_dev", "scilmm_panel_timing",
+    "scilmm_scan_spa_dev", "scilmm_scan_spa_bed_dev", "scilmm_scan_spa_dosage_dev", "scilmm_spa_timing",
 ]
 
 _lib = None
@@ -184,6 +185,11 @@ def lib():
     L.scilmm_gxe_timing.argtypes = [vp, P(dbl)]
     L.scilmm_scan_panel_dev.argtypes = [vp, i32, vp, i64, i32, vp, i64]
     L.scilmm_panel_timing.argtypes = [vp, P(dbl)]
+    spa = [vp, vp, vp, vp, vp, i32, vp, dbl, vp]   # d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa
+    L.scilmm_scan_spa_dev.argtypes = [vp, vp, i64, i32] + spa
+    L.scilmm_scan_spa_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32] + spa
+    L.scilmm_scan_spa_dosage_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32] + spa
+    L.scilmm_spa_timing.argtypes = [vp, P(dbl)]
     L.scilmm_rel_block_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_rows_block_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_order.argtypes = [i32, vp, vp, i32, vp]

@@ -209,6 +209,47 @@ int scan_panel(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, i
   return SCILMM_OK;
 }
 
+// What the three saddlepoint entry points share beside their form's marker arguments (scilmm_scan_spa*_dev).
+struct SpaArgs {
+  const double *d_stats, *d_R, *d_u, *d_mu, *d_C;
+  int32_t c;
+  const double* d_Minv;
+  double cutoff;
+  double* d_spa;
+  // before anything of the handle is read (a NaN cutoff fails the comparison)
+  static bool args_ok(const scilmm_factor* fac, int32_t r, const SpaArgs& a) {
+    return fac && a.d_stats && a.d_R && a.d_u && a.d_mu && a.d_C && a.d_Minv && a.d_spa && r >= 1 && r <= RPMAX && a.c >= 1 &&
+           a.c <= SPA_CMAX && a.cutoff >= 0.0 && fac->sym && fac->sym->S;
+  }
+};
+
+// The saddlepoint p-values of the r markers of the plain block queued before this call (scilmm_scan_spa*_dev): the refusals of
+// the half-solves, the scratch of g^ rows (RPMAX x n doubles, allocated by the first call on the handle after a stream
+// synchronise, never again), k_scan_spa between the call's own events.  Nothing of the work buffers is touched: the block stays
+// available to scilmm_scan_panel_dev.
+template <class Reader>
+int scan_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const SpaArgs& a) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const int32_t n = sym->S->n;
+  const size_t need = (size_t)RPMAX * (size_t)std::max(n, 1);
+  if (D->spa_scratch_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  TRY(grow(sym, &D->spa_scratch, &D->spa_scratch_cap, need));
+  if (!D->spa_ev[0])
+    for (auto& e : D->spa_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->spa_ev[0], s0));
+  hipLaunchKernelGGL(k_scan_spa<Reader>, dim3((unsigned)r), dim3(256), 0, s0, n, r, a.c, rd, a.d_stats, a.d_R, a.d_u, a.d_mu, a.d_C, a.d_Minv, a.cutoff,
+                     D->spa_scratch, a.d_spa);
+  HIPCHK(hipEventRecord(D->spa_ev[1], s0));
+  D->spa_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
 // One block of columns `ids` of sum_k weights[k] A_k, built from the resident values (scilmm_rel_block_dev).
 int rel_block(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
   BlockCall b(fac);

@@ -314,6 +314,12 @@ struct Dev {
   hipEvent_t panel_ev[3] = {nullptr, nullptr, nullptr};  // panel begin | k_scan_panel done | k_panel_fold done (the first panel call creates them)
   bool panel_pending = false;           // a panel call whose events have not been read yet (scilmm_sync)
   double panel_ms[2] = {0.0, 0.0};      // the last call's k_scan_panel | k_panel_fold (scilmm_panel_timing)
+  // saddlepoint score scan (scilmm_scan_spa*_dev): the covariate-adjusted marker rows of one block
+  double* spa_scratch = nullptr;        // [RPMAX][n] (the first SPA call on the handle allocates it; never reallocated)
+  size_t spa_scratch_cap = 0;           // doubles
+  hipEvent_t spa_ev[2] = {nullptr, nullptr};  // k_scan_spa begin | done (the first SPA call creates them)
+  bool spa_pending = false;             // an SPA call whose events have not been read yet (scilmm_sync)
+  double spa_ms = 0.0;                  // the last call's k_scan_spa (scilmm_spa_timing)
   void clear_block() { block_r = block_rp = 0; }
 };
 

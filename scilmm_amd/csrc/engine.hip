@@ -35,6 +35,7 @@
 #include "panel.hip.h"
 #include "bed.hip.h"
 #include "dosage.hip.h"
+#include "spa.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
@@ -314,6 +315,37 @@ int scilmm_scan_panel_dev(scilmm_factor* fac, int32_t r, const double* d_Y, int6
   return scan_panel(fac, r, d_Y, ld_y, t, d_xty, ld_out);
 }
 
+// The saddlepoint p-values behind a plain block: the form's marker arguments are checked as its plain entry point checks them
+int scilmm_scan_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_R,
+                        const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff,
+                        double* d_spa) {
+  const SpaArgs a{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa};
+  if (!d_geno || !SpaArgs::args_ok(fac, r, a) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
+  return scan_spa(fac, __func__, r, SpaInt8{d_geno, ld_geno}, a);
+}
+
+int scilmm_scan_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                            int32_t flags, int32_t r, const double* d_stats, const double* d_R, const double* d_u, const double* d_mu,
+                            const double* d_C, int32_t c, const double* d_Minv, double cutoff, double* d_spa) {
+  const SpaArgs a{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa};
+  if (!d_bed || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) || !SpaArgs::args_ok(fac, r, a) ||
+      (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return scan_spa(fac, __func__, r, SpaBed{d_bed, ld_bed, n_samples, d_sample, flags}, a);
+}
+
+int scilmm_scan_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                               const int32_t* d_sample, int32_t r, const double* d_stats, const double* d_R, const double* d_u,
+                               const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff, double* d_spa) {
+  const SpaArgs a{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa};
+  if (!d_dos || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
+      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
+      !SpaArgs::args_ok(fac, r, a) || (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return dtype == SCILMM_DOSAGE_U16 ? scan_spa(fac, __func__, r, SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}, a)
+                                    : scan_spa(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
+}
+
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
                          double* d_stats) {
   if (!weights || !ids || !BlockCall::args_ok(fac, r, d_Q, q, d_stats)) return SCILMM_ERR_ARG;
@@ -514,6 +546,12 @@ int scilmm_sync(scilmm_symbolic* sym) {
     D->panel_ms[0] = a;
     D->panel_ms[1] = b;
   }
+  if (D->spa_pending) {
+    D->spa_pending = false;
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->spa_ev[0], D->spa_ev[1]));
+    D->spa_ms = a;
+  }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
 }
@@ -552,6 +590,12 @@ int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   const Dev* D = (const Dev*)sym->device;
   for (int i = 0; i < 2; ++i) ms[i] = D->panel_ms[i];
+  return SCILMM_OK;
+}
+
+int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  ms[0] = ((const Dev*)sym->device)->spa_ms;
   return SCILMM_OK;
 }
 

@@ -35,6 +35,9 @@ void dev_free(void* p) {
   if (D->scan_partial) (void)hipFree(D->scan_partial);
   if (D->gram_partial) (void)hipFree(D->gram_partial);
   if (D->panel_partial) (void)hipFree(D->panel_partial);
+  if (D->spa_scratch) (void)hipFree(D->spa_scratch);
+  for (auto& e : D->spa_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->gxe_ev)

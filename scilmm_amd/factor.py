@@ -271,6 +271,12 @@ class Symbolic(object):
         check(lib().scilmm_panel_timing(self._h, ms), self._h)
         return tuple(ms)
 
+    def spa_timing(self):
+        """``k_scan_spa`` of the last ``Factor.scan_spa*_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 1)()
+        check(lib().scilmm_spa_timing(self._h, ms), self._h)
+        return float(ms[0])
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -473,6 +479,24 @@ class Factor(object):
         of ``Q``, 16-byte aligned, ``ld_y`` a multiple of 16); enqueues without synchronising (``scilmm_scan_panel_dev``;
         ``scilmm_amd.panel.TraitPanel`` is the interface).  ``ScilmmError`` when no block was left behind or ``r`` is not its."""
         check(lib().scilmm_scan_panel_dev(self._h, r, dY_ptr, ld_y, t, dxty_ptr, ld_out), self.sym._h)
+
+    def scan_spa_dev(self, dG_ptr, ld, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr):
+        """The saddlepoint p-values of the ``r`` markers of the plain block queued before it (``scilmm_scan_spa_dev``: 7 x r
+        numbers to ``dspa_ptr``; ``scilmm_amd.glmm.BinaryScan`` is the interface); enqueues without synchronising."""
+        check(lib().scilmm_scan_spa_dev(self._h, dG_ptr, ld, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff,
+                                        dspa_ptr), self.sym._h)
+
+    def scan_spa_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c,
+                         dMinv_ptr, cutoff, dspa_ptr):
+        """``scan_spa_dev`` behind a block of packed PLINK rows (``scilmm_scan_spa_bed_dev``)."""
+        check(lib().scilmm_scan_spa_bed_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr,
+                                            dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr), self.sym._h)
+
+    def scan_spa_dosage_dev(self, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c,
+                            dMinv_ptr, cutoff, dspa_ptr):
+        """``scan_spa_dev`` behind a block of dosage rows (``scilmm_scan_spa_dosage_dev``)."""
+        check(lib().scilmm_scan_spa_dosage_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dstats_ptr, dR_ptr, du_ptr,
+                                               dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr), self.sym._h)
 
     def rel_block_dev(self, weights, ids, dQ_ptr, q, dstats_ptr):
         """One block of BLUP statistics for columns ``ids`` of ``sum_k weights[k] A_k`` (``scilmm_rel_block_dev``; host

@@ -6,6 +6,8 @@ input form.  A source has ``m`` (its markers), ``row_bytes`` (host bytes of one 
     enqueue(k0, rb, pS, pK)    queue block (k0, rb) of the loaded rows: statistics to ``pS``; with ``pK`` the Gram matrix as well
                                (the ``_gram_dev`` twin of the form's entry point); with ``env=(pE, m)`` the marker x environment
                                block of ``m`` environment columns at ``pE`` (the ``_gxe_dev`` twin)
+    spa(k0, rb, tail)          queue the saddlepoint p-values of block (k0, rb) behind its plain block (the ``scilmm_scan_spa*_dev``
+                               twin; ``tail``: what follows ``r`` in its arguments -- ``scilmm_amd.glmm``)
 
 Everything else -- chunks, blocks, the synchronisation, the host algebra -- is the callers' and does not depend on the form.
 """
@@ -70,8 +72,13 @@ class Int8Rows(MarkerSource):
 
     def enqueue(self, k0, rb, pS, pK=None, env=None):
         f = self.model.factor
-        self._call(f.scan_block_dev, f.scan_block_gram_dev, f.scan_block_gxe_dev, (vp(self.dG.data_ptr() + k0 * self.ld), self.ld),
-                   rb, pS, pK, env)
+        self._call(f.scan_block_dev, f.scan_block_gram_dev, f.scan_block_gxe_dev, self._head(k0), rb, pS, pK, env)
+
+    def _head(self, k0):
+        return (vp(self.dG.data_ptr() + k0 * self.ld), self.ld)
+
+    def spa(self, k0, rb, tail):
+        self.model.factor.scan_spa_dev(*(self._head(k0) + (rb,) + tuple(tail)))
 
 
 class BedRows(MarkerSource):
@@ -104,9 +111,15 @@ class BedRows(MarkerSource):
         self.t_read, self.t_copy = self.t_read + t2 - t1, self.t_copy + time.perf_counter() - t2
 
     def enqueue(self, k0, rb, pS, pK=None, env=None):
-        f, nb = self.model.factor, self.row_bytes
-        self._call(f.scan_block_bed_dev, f.scan_block_bed_gram_dev, f.scan_block_bed_gxe_dev,
-                   (vp(self.dB.data_ptr() + k0 * nb), nb, self.bed.n_samples, self._map(), self.flag), rb, pS, pK, env)
+        f = self.model.factor
+        self._call(f.scan_block_bed_dev, f.scan_block_bed_gram_dev, f.scan_block_bed_gxe_dev, self._head(k0), rb, pS, pK, env)
+
+    def _head(self, k0):
+        nb = self.row_bytes
+        return (vp(self.dB.data_ptr() + k0 * nb), nb, self.bed.n_samples, self._map(), self.flag)
+
+    def spa(self, k0, rb, tail):
+        self.model.factor.scan_spa_bed_dev(*(self._head(k0) + (rb,) + tuple(tail)))
 
 
 class DosageRows(MarkerSource):
@@ -133,6 +146,10 @@ class DosageRows(MarkerSource):
 
     def enqueue(self, k0, rb, pS, pK=None, env=None):
         f = self.model.factor
-        self._call(f.scan_block_dosage_dev, f.scan_block_dosage_gram_dev, f.scan_block_dosage_gxe_dev,
-                   (vp(self.dB.data_ptr() + k0 * self.ldb), self.dtype, self.ldb // self.d.dtype.itemsize, self.d.shape[1], self._map()),
-                   rb, pS, pK, env)
+        self._call(f.scan_block_dosage_dev, f.scan_block_dosage_gram_dev, f.scan_block_dosage_gxe_dev, self._head(k0), rb, pS, pK, env)
+
+    def _head(self, k0):
+        return (vp(self.dB.data_ptr() + k0 * self.ldb), self.dtype, self.ldb // self.d.dtype.itemsize, self.d.shape[1], self._map())
+
+    def spa(self, k0, rb, tail):
+        self.model.factor.scan_spa_dosage_dev(*(self._head(k0) + (rb,) + tuple(tail)))
