@@ -23,6 +23,12 @@ namespace scilmm {
 // rounding (parity-tested); switches that would change RESULTS (the timing ablations) exist only in builds with
 // -DSCILMM_DIAG.  A std::optional member is a switch whose default is decided from the matrix: unset -> decide.
 // (INTEGRATION.md section 3 has the table; keep the two in step.)
+// Parity-tested means: a case of tests/test_gpu_factor_schedules.py or of test_gpu_parity.py's schedule table sets the switch,
+// factors with it and compares L, log-det, solves and L*R with the oracle -- the factor schedules there (dense tail, k_outside,
+// item and slab counts, panel solve, side streams, fp32 fronts), the cell path, chain plan and look-ahead in test_gpu_parity;
+// the chain sweeps' per-call switches in test_gpu_chain_pipeline.py, the selected inverse's in test_gpu_selected_inverse.py and
+// test_gpu_sinv_deterministic.py, the distributed tail's in test_zz_gpu_dist.py.  tests/test_factor_shapes.py reads the names
+// out of read_tuning() below and fails when one of them is set by no case and not exempted there with a reason.
 struct Tuning {
   // -- read when the device plan of a handle is built (Dev::tune)
   int reserve_cus = 0;                 // SCILMM_RESERVE_CUS     CUs the look-ahead side streams leave free (CU mask); 0: none

@@ -89,6 +89,8 @@ struct Factorization : FactorLaunch {
       (void)hipFree(fac->L32);
       fac->L32 = nullptr;
     }
+    if (verbose() && D->front_bits == 32 && D->dense_on)
+      fprintf(stderr, "[scilmm plan] fp32 fronts: %s\n", fac->L32 ? "k_dense_h (fp32 shadow)" : "k_dense32 (fp64 operands rounded while staged)");
     return SCILMM_OK;
   }
 

@@ -579,7 +579,11 @@ int plan_outside(scilmm_symbolic* sym, Dev* D, PlanBuild& pb) {
     D->ochunk_ptr.assign(1, 0);
     std::vector<int32_t> chunk_lo;  // first panel of the chunk's first item
     {
-      const size_t N = ord.size(), per = std::max<size_t>(1, (N + want_chunks - 1) / want_chunks);
+      const size_t N = ord.size();
+      size_t panels = N ? 1 : 0;  // distinct first panels
+      for (size_t k = 1; k < N; ++k) panels += ffront[ord[k]] != ffront[ord[k - 1]];
+      // (as many chunks as there are first panels, or more, were asked for: one chunk per panel, however few items it holds)
+      const size_t per = (size_t)want_chunks >= panels ? 1 : std::max<size_t>(1, (N + want_chunks - 1) / want_chunks);
       size_t i = 0;
       while (i < N) {
         chunk_lo.push_back(ffront[ord[i]]);
@@ -631,6 +635,7 @@ int plan_outside(scilmm_symbolic* sym, Dev* D, PlanBuild& pb) {
               (long long)D->n_owork, D->tail_level, c0_tail, nch);
       for (int32_t g = 0; g < nch; ++g) fprintf(stderr, " [%d..: %lld]", chunk_lo[g] - S.dense_first, (long long)(D->ochunk_ptr[g + 1] - D->ochunk_ptr[g]));
       fprintf(stderr, "\n");
+      fprintf(stderr, "[scilmm plan] k_outside: on a stream of %s priority\n", D->tune.outside_prio ? "the chain's" : "the look-ahead streams'");
     }
   }
   return SCILMM_OK;
@@ -1498,8 +1503,29 @@ struct WorkCut {
     return SCILMM_OK;
   }
 
+  // one line per launch class: explicit items, and the partial slabs per tile that k_reduce (early) and k_potrf / k_trsm (late) fold
+  void report_slabs(const char* cls, int64_t items, const std::vector<int32_t>& tiles, const std::vector<int32_t>& nseg) const {
+    int64_t slabs = 0, odd = 0;
+    int32_t lo = 0, hi = 0;
+    for (int32_t g : tiles) {
+      const int32_t c = nseg[(size_t)g];
+      slabs += c;
+      odd += c & 1;
+      lo = lo == 0 ? c : std::min(lo, c);
+      hi = std::max(hi, c);
+    }
+    fprintf(stderr, "[scilmm plan] %s: %lld explicit items, %lld partial slabs on %zu tiles, %d .. %d per tile, %lld tiles with an odd count, %lld with an even one\n",
+            cls, (long long)items, (long long)slabs, tiles.size(), lo, hi, (long long)odd, (long long)((int64_t)tiles.size() - odd));
+  }
+
   int upload_items(scilmm_symbolic* sym) {
     int st;
+    if (pb.verbose) {
+      report_slabs("early launches", (int64_t)work_early.size(), red_tiles_e, pnseg_e);
+      report_slabs("late launches", (int64_t)work.size(), red_tiles, pnseg);
+      fprintf(stderr, "[scilmm plan] split-K %s, panel solve %s, %d side streams\n", allow_split ? "on" : "off",
+              !D->use_mfma ? "k_trsm<false>" : D->trsm_lite ? "k_trsm_lite" : "k_trsm<true>", D->nside);
+    }
     {
       if (dwork_e.empty()) dwork_e.push_back(DenseWork{});
       if (dwork_l.empty()) dwork_l.push_back(DenseWork{});

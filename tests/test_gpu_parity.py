@@ -18,14 +18,17 @@ def _engine(mats, **kw):
     return Symbolic(mats, **kw)
 
 
-def _check_factor(mats, sigma2, sym, rs=(1, 5, 103)):
+def _check_factor(mats, sigma2, sym, rs=(1, 5, 103), oracle=None):
+    """`oracle`: the oracle's factor of the same V under the handle's permutation, where the caller keeps one for several
+    handles (tests/test_gpu_factor_schedules.py); built here otherwise."""
     from oracle import oracle as O
     V = sum(s * m for s, m in zip(sigma2, mats)).tocsr()
     n = V.shape[0]
     f = sym.factorize(sigma2)
     perm = f.P()
     assert sorted(perm.tolist()) == list(range(n))
-    o = O.OracleFactor(V, perm)
+    o = O.OracleFactor(V, perm) if oracle is None else oracle
+    assert np.array_equal(o.P(), perm)
     assert abs(f.logdet() - o.logdet()) <= TOL * max(1.0, abs(o.logdet()))
     rng = np.random.default_rng(n)
     for r in rs:
