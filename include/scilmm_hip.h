@@ -410,6 +410,54 @@ int scilmm_scan_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dt
  * ms[0] k_scan_spa (tools/spa_timing.py).  No counterpart in the reference. */
 int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Variant-set tests: everything AFTER a Gram block (scilmm_scan_block_gram_dev or a twin of it), for the sets the block holds --
+ * burden, SKAT and SKAT-O (Lee, Wu, Lin 2012) -- on the device, queued behind the block on the handle's stream.  A pure function
+ * of what the block left behind: nothing of the factor is read, no work buffer is written, nothing is allocated.
+ *   r, q, d_stats, d_gram: the block's markers, its q = c + 1, its (q + 4) x r statistics and its r x r Gram matrix.
+ *            Of d_gram the sets' diagonal blocks are read, both triangles: entry (i, j) is taken as the mean of [i][j] and [j][i]
+ *            (the Gram entry points write a bitwise symmetric matrix, so nothing changes for them).
+ *   d_R, d_u, c: as for scilmm_scan_spa_dev (R'R = w(C)'w(C) upper triangular row-major, u = R^-T w(C)'w(y)); c: 1 .. 31.
+ *   n_sets, set_start: HOST, n_sets + 1 int32 offsets into the block's columns, rising from 0 to at most r: set i is columns
+ *            set_start[i] .. set_start[i + 1] - 1 (sets are contiguous and disjoint, in the order scilmm_amd.sets.pack_sets lays
+ *            them out); 1 <= n_sets <= r.  Read before the call returns, like the ids of scilmm_rel_block_dev.
+ *   weight_mode: 0 = the Beta(1, 25) density at the minor allele frequency from the `mean` row, 25 (1 - maf)^24,
+ *            maf = min(mean / 2, 1 - mean / 2); 1 = ones; 2 = d_weights, r doubles on the device, one per column of the block
+ *            (d_weights is not read in the other modes and may be null).
+ *   method : the mixtures' tail, 0 = saddlepoint (Lugannani-Rice, with the seam of the host form), 1 = modified Liu.
+ *   rho, n_rho: HOST, the SKAT-O grid, 0 .. 16 values in [0, 1] (a value above 0.999 is computed as 0.999); n_rho = 0: no
+ *            SKAT-O (rho may then be null).
+ *   d_out  : n_sets rows of ld_out >= 10 + n_rho doubles; row i:  n_used | burden_beta | burden_se | burden_chi2 | skat_q |
+ *            skat_p | skato_p | skato_pmin | skato_rho | flags | the n_rho per-rho p-values.  A marker without an observed value
+ *            or without variation is dropped from its set; a set with nothing left: n_used = 0, flags = 0, the rest NaN.
+ *            Without SKAT-O the three skato numbers are NaN.  flags: bit 0 the degenerate rule answered (one marker, 1'A1 = 0
+ *            or A of rank one: skato_p = skato_pmin, skato_rho = the first grid value; or skato_pmin = 0), bit 1 the Jacobi
+ *            iteration ran out of sweeps, bit 2 a root ran out of steps, bit 3 SKAT-O was computed.  Exactly 10 + n_rho doubles
+ *            of every row are written.
+ *   d_lam  : null, or r doubles: the columns of a set's kept markers receive the eigenvalues of A = diag(w) K diag(w) in
+ *            descending order, the columns of its dropped markers NaN; columns outside every set are not written.
+ * With s, K as in scilmm_scan_block_gram_dev's contract, t = w o s and A = diag(w) K diag(w): Q_rho = (1 - rho) t't +
+ * rho (1't)^2 has the null law sum lambda_i chi2_1 with the eigenvalues of A R_rho, R_rho = (1 - rho) I + rho 11'; skato_pmin is
+ * the smallest of their p-values, skato_rho the first grid value that attains it, and skato_p the integral of DESIGN.md
+ * section 19 in survival form, bounded by n_rho skato_pmin.  One workgroup per set with the set in LDS (sized by the block's
+ * largest set: the call raises the kernel's dynamic-LDS limit once per device): one Jacobi eigendecomposition A = U Lambda U',
+ * the other spectra as roots of secular equations on (Lambda, U'1).  No atomics, fixed strides and fixed reduction trees: a
+ * set's numbers depend on its own inputs alone -- not on its place in the block, its neighbours or the mode of the handle --
+ * and scilmm_timing.n_float_atomic_launches is not touched.  burden_p is left to the caller (F(1, n - 1) of burden_chi2).
+ * Enqueued without synchronising.  SCILMM_ERR_ARG before anything of the handle or of the device is read: a null fac, d_stats,
+ * d_gram, d_R, d_u, set_start or d_out (rho with n_rho > 0, d_weights in mode 2), r outside 1 .. 128, c outside 1 .. 31,
+ * q != c + 1, n_sets outside 1 .. r, n_rho outside 0 .. 16, a rho outside [0, 1] or NaN, offsets that do not start at 0, do not
+ * rise strictly or end beyond r, ld_out < 10 + n_rho, an unknown weight mode or method.  Refusals as for the scan blocks
+ * (SCILMM_ERR_STATE, the handle left usable): a distributed handle, fp32-product fronts, a factor consumed by the selected
+ * inverse.  scilmm_amd.VariantSetTest with finish="device" is the interface.  No counterpart in the reference. */
+int scilmm_sets_finish_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram, const double* d_R,
+                           const double* d_u, int32_t c, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                           const double* d_weights, int32_t method, const double* rho, int32_t n_rho, double* d_out, int64_t ld_out,
+                           double* d_lam);
+
+/* HIP-event time of the last scilmm_sets_finish_dev on the handle, in milliseconds, valid after the scilmm_sync that follows
+ * it: ms[0] k_sets_finish (tools/sets_timing.py --finish).  No counterpart in the reference. */
+int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms);
+
 /* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
  * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y
  * (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1) per column by the scan's algebra: predicted value, prediction error variance

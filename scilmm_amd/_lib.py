@@ -81,6 +81,7 @@ SYMBOLS = [
     "scilmm_scan_block_gxe_dev", "scilmm_scan_block_bed_gxe_dev", "scilmm_scan_block_dosage_gxe_dev", "scilmm_gxe_timing",
     "scilmm_scan_panel_dev", "scilmm_panel_timing",
     "scilmm_scan_spa_dev", "scilmm_scan_spa_bed_dev", "scilmm_scan_spa_dosage_dev", "scilmm_spa_timing",
+    "scilmm_sets_finish_dev", "scilmm_sets_finish_timing",
 ]
 
 _lib = None
@@ -190,6 +191,9 @@ def lib():
     L.scilmm_scan_spa_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32] + spa
     L.scilmm_scan_spa_dosage_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32] + spa
     L.scilmm_spa_timing.argtypes = [vp, P(dbl)]
+    # r, q, d_stats, d_gram, d_R, d_u, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_out, ld_out, d_lam
+    L.scilmm_sets_finish_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i64, vp]
+    L.scilmm_sets_finish_timing.argtypes = [vp, P(dbl)]
     L.scilmm_rel_block_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_rows_block_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_order.argtypes = [i32, vp, vp, i32, vp]

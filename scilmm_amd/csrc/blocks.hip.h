@@ -250,6 +250,69 @@ int scan_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const Sp
   return SCILMM_OK;
 }
 
+// What scilmm_sets_finish_dev takes beside the factor.
+struct FinishArgs {
+  int32_t r, q;
+  const double *d_stats, *d_gram, *d_R, *d_u;
+  int32_t c, n_sets;
+  const int32_t* set_start;
+  int32_t weight_mode;
+  const double* d_weights;
+  int32_t method;
+  const double* rho;
+  int32_t n_rho;
+  double* d_out;
+  int64_t ld_out;
+  double* d_lam;
+  // before anything of the handle is read; the offsets and the grid are HOST arrays and are read here (a NaN fails its comparison)
+  static bool args_ok(const scilmm_factor* fac, const FinishArgs& a) {
+    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.set_start || !a.d_out || a.r < 1 || a.r > RPMAX || a.c < 1 ||
+        a.c > FIN_CMAX || a.q != a.c + 1 || a.n_sets < 1 || a.n_sets > a.r || a.n_rho < 0 || a.n_rho > FIN_RHO_MAX ||
+        (a.n_rho > 0 && !a.rho) || a.ld_out < FIN_HEAD + a.n_rho ||
+        (a.weight_mode != FIN_BETA && a.weight_mode != FIN_ONES && a.weight_mode != FIN_GIVEN) ||
+        (a.weight_mode == FIN_GIVEN && !a.d_weights) || (a.method != FIN_SADDLE && a.method != FIN_LIU))
+      return false;
+    for (int32_t j = 0; j < a.n_rho; ++j)
+      if (!(a.rho[j] >= 0.0 && a.rho[j] <= 1.0)) return false;
+    if (a.set_start[0] != 0 || a.set_start[a.n_sets] > a.r) return false;
+    for (int32_t i = 0; i < a.n_sets; ++i)
+      if (a.set_start[i + 1] <= a.set_start[i]) return false;
+    return fac->sym && fac->sym->S;  // (what needs no handle has been checked: with it wrong, nothing of the handle is read)
+  }
+};
+
+// Everything after a Gram block, for the sets of the block (scilmm_sets_finish_dev): the refusals of the scan blocks, then
+// k_sets_finish between the call's own events, one workgroup per set, its LDS sized by the block's largest set.  Nothing of the
+// factor is read and nothing of the work buffers is touched; nothing is allocated.
+int sets_finish(scilmm_factor* fac, const FinishArgs& a) {
+  const char* who = "scilmm_sets_finish_dev";
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  FinSets sets{};
+  int32_t widest = 0;
+  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
+  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
+  for (int32_t j = 0; j < a.n_rho; ++j) sets.rho[j] = a.rho[j];
+  const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
+  const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
+  // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
+  HIPCHK(hipFuncSetAttribute((const void*)k_sets_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
+  if (!D->fin_ev[0])
+    for (auto& e : D->fin_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->fin_ev[0], s0));
+  hipLaunchKernelGGL(k_sets_finish, dim3((unsigned)a.n_sets), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, a.d_u, sets,
+                     a.weight_mode, a.d_weights, a.method, a.n_rho, cap, a.d_out, a.ld_out, a.d_lam);
+  HIPCHK(hipEventRecord(D->fin_ev[1], s0));
+  D->fin_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
 // One block of columns `ids` of sum_k weights[k] A_k, built from the resident values (scilmm_rel_block_dev).
 int rel_block(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
   BlockCall b(fac);

@@ -326,6 +326,9 @@ struct Dev {
   hipEvent_t spa_ev[2] = {nullptr, nullptr};  // k_scan_spa begin | done (the first SPA call creates them)
   bool spa_pending = false;             // an SPA call whose events have not been read yet (scilmm_sync)
   double spa_ms = 0.0;                  // the last call's k_scan_spa (scilmm_spa_timing)
+  hipEvent_t fin_ev[2] = {nullptr, nullptr};  // k_sets_finish begin | done (the first finish call creates them)
+  bool fin_pending = false;             // a finish call whose events have not been read yet (scilmm_sync)
+  double fin_ms = 0.0;                  // the last call's k_sets_finish (scilmm_sets_finish_timing)
   void clear_block() { block_r = block_rp = 0; }
 };
 

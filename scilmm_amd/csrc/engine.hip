@@ -1,5 +1,5 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setfinish.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
@@ -36,6 +36,7 @@
 #include "bed.hip.h"
 #include "dosage.hip.h"
 #include "spa.hip.h"
+#include "setfinish.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
@@ -346,6 +347,16 @@ int scilmm_scan_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dt
                                     : scan_spa(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
 }
 
+// The variant-set finish behind a Gram block: a pure function of what the block left behind
+int scilmm_sets_finish_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram, const double* d_R,
+                           const double* d_u, int32_t c, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                           const double* d_weights, int32_t method, const double* rho, int32_t n_rho, double* d_out, int64_t ld_out,
+                           double* d_lam) {
+  const FinishArgs a{r, q, d_stats, d_gram, d_R, d_u, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_out, ld_out, d_lam};
+  if (!FinishArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_finish(fac, a);
+}
+
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
                          double* d_stats) {
   if (!weights || !ids || !BlockCall::args_ok(fac, r, d_Q, q, d_stats)) return SCILMM_ERR_ARG;
@@ -552,6 +563,12 @@ int scilmm_sync(scilmm_symbolic* sym) {
     HIPCHK(hipEventElapsedTime(&a, D->spa_ev[0], D->spa_ev[1]));
     D->spa_ms = a;
   }
+  if (D->fin_pending) {
+    D->fin_pending = false;
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->fin_ev[0], D->fin_ev[1]));
+    D->fin_ms = a;
+  }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
 }
@@ -596,6 +613,12 @@ int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms) {
 int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   ms[0] = ((const Dev*)sym->device)->spa_ms;
+  return SCILMM_OK;
+}
+
+int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  ms[0] = ((const Dev*)sym->device)->fin_ms;
   return SCILMM_OK;
 }
 

@@ -38,6 +38,8 @@ void dev_free(void* p) {
   if (D->spa_scratch) (void)hipFree(D->spa_scratch);
   for (auto& e : D->spa_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->fin_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->gxe_ev)

@@ -277,6 +277,12 @@ class Symbolic(object):
         check(lib().scilmm_spa_timing(self._h, ms), self._h)
         return float(ms[0])
 
+    def sets_finish_timing(self):
+        """``k_sets_finish`` of the last ``Factor.sets_finish_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 1)()
+        check(lib().scilmm_sets_finish_timing(self._h, ms), self._h)
+        return float(ms[0])
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -485,6 +491,17 @@ class Factor(object):
         numbers to ``dspa_ptr``; ``scilmm_amd.glmm.BinaryScan`` is the interface); enqueues without synchronising."""
         check(lib().scilmm_scan_spa_dev(self._h, dG_ptr, ld, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff,
                                         dspa_ptr), self.sym._h)
+
+    def sets_finish_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method, rho,
+                        dout_ptr, ld_out, dlam_ptr):
+        """Everything after a Gram block, one workgroup per set (``scilmm_sets_finish_dev``): ``set_start`` (host int32,
+        ``n_sets + 1`` offsets into the block's columns) and ``rho`` (host float64, possibly empty: no SKAT-O) are read before the
+        call returns; ``n_sets`` rows of ``10 + len(rho)`` doubles go to ``dout_ptr``; enqueues without synchronising
+        (``scilmm_amd.sets.VariantSetTest`` with ``finish="device"`` is the interface)."""
+        set_start = np.ascontiguousarray(set_start, dtype=np.int32)
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        check(lib().scilmm_sets_finish_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, ptr(set_start), weight_mode,
+                                           dweights_ptr, method, ptr(rho), rho.size, dout_ptr, ld_out, dlam_ptr), self.sym._h)
 
     def scan_spa_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c,
                          dMinv_ptr, cutoff, dspa_ptr):

@@ -19,14 +19,27 @@ after that is host algebra on at most 128 x 128 matrices.
 Burden: ``beta = w's / w'Kw``, ``se = (w'Kw)^-1/2``, ``chi2 = (w's)^2 / w'Kw``, p from F(1, n - 1) as the scan's.  SKAT:
 ``Q = sum_j w_j^2 s_j^2``, null distribution ``sum_i lam_i chi2_1`` with ``lam`` the eigenvalues of ``diag(w) K diag(w)``
 (Chen, Meigs, Dupuis 2013), tail probability by the saddlepoint approximation of Kuonen (1999) or by the modified Liu
-moment matching of the SKAT package.  Davies' method and SKAT-O are not here: ``return_kernel=True`` hands out
-``(s, K, w)`` per set for a caller who wants them.  There is no CPU form.
+moment matching of the SKAT package.  Davies' method is not here: ``return_kernel=True`` hands out ``(s, K, w)`` per set
+for a caller who wants it.  There is no CPU form.
+
+SKAT-O (Lee, Wu, Lin 2012; ``skato=True``): with ``t = w o s`` and ``A = diag(w) K diag(w)``, the statistic of the grid value
+``rho`` is ``Q_rho = (1 - rho) t't + rho (1't)^2``, its null law the mixture with the eigenvalues of ``A R_rho``,
+``R_rho = (1 - rho) I + rho 11'``; the test statistic is the smallest of their p-values, and its own p-value is a
+one-dimensional integral over the component of the score along ``A 1`` (``skato_pvalue``, which needs ``(t, A)`` alone;
+DESIGN.md section 19).
+
+``finish="host"`` does everything after the Gram block in NumPy / SciPy, set by set.  ``finish="device"`` queues
+``scilmm_sets_finish_dev`` behind the block instead: one workgroup per set does the projection, a Jacobi
+eigendecomposition, the tails and the SKAT-O quadrature in LDS, and one copy of a few doubles per set comes back (``burden_p``
+alone stays on the host).  The two agree to the accuracy of the tails (1e-6 relative), not bit for bit.
 """
 import ctypes as C
 
 import numpy as np
+import scipy.integrate as integ
 import scipy.linalg as la
 import scipy.optimize as opt
+import scipy.special as special
 import scipy.stats as stats
 
 from .assoc import AssociationScan, check_genotypes
@@ -36,6 +49,13 @@ LAMBDA_FLOOR = 1e-10      # eigenvalues below this fraction of the largest are d
 SADDLE_SEAM = 0.05        # |q - mean| below this many standard deviations: the saddlepoint formula is singular, Liu instead
 METHODS = ("saddlepoint", "liu")
 KEYS = ("n_used", "burden_beta", "burden_se", "burden_chi2", "burden_p", "skat_q", "skat_p")
+SKATO_KEYS = ("skato_p", "skato_pmin", "skato_rho", "skato_p_rho")
+RHO_DEFAULT = (0.0, 0.01, 0.04, 0.09, 0.16, 0.25, 0.5, 1.0)
+RHO_MAX, RHO_CAP = 16, 0.999      # grid values at most; a value above RHO_CAP is computed as RHO_CAP (R_rho stays definite)
+Z_END = 40.0              # the SKAT-O integral stops here: 2 Phi(-40) is zero in double precision
+FINISHES = ("host", "device")
+WEIGHT_BETA, WEIGHT_ONES, WEIGHT_GIVEN = 0, 1, 2       # weight modes of scilmm_sets_finish_dev
+FINISH_HEAD = 10          # doubles of a set's row before its per-rho p-values
 
 
 def _lam(lam):
@@ -43,13 +63,10 @@ def _lam(lam):
     return lam[lam > 0]
 
 
-def mixture_sf_liu(q, lam):
-    """P(sum_i lam_i chi2_1 > q) by the modified Liu moment matching (mean, variance, and kurtosis -- skewness as well where
-    the two can be matched together), as the SKAT package does it.  Exact for equal ``lam``."""
-    lam = _lam(lam)
-    q = float(q)
-    if np.isnan(q) or lam.size == 0:
-        return np.nan
+def liu_params(lam):
+    """The modified Liu matching of ``sum_i lam_i chi2_1`` (``lam`` positive): ``(c1, c2, a, d, l)`` with ``c_k = sum lam^k`` (mean
+    ``c1``, variance ``2 c2``), and the matched non-central chi-square's scale ``a``, non-centrality ``d`` and degrees of freedom
+    ``l``."""
     c1, c2, c3, c4 = (float(np.sum(lam ** k)) for k in (1, 2, 3, 4))
     s1, s2 = c3 / c2 ** 1.5, c4 / (c2 * c2)
     # (equal lam give s1^2 == s2 in exact arithmetic: a difference of rounding size is not a skewness to match)
@@ -61,6 +78,17 @@ def mixture_sf_liu(q, lam):
         l = 1.0 / s2
         a = np.sqrt(l)
         d = 0.0
+    return c1, c2, a, d, l
+
+
+def mixture_sf_liu(q, lam):
+    """P(sum_i lam_i chi2_1 > q) by the modified Liu moment matching (mean, variance, and kurtosis -- skewness as well where
+    the two can be matched together), as the SKAT package does it.  Exact for equal ``lam``."""
+    lam = _lam(lam)
+    q = float(q)
+    if np.isnan(q) or lam.size == 0:
+        return np.nan
+    c1, c2, a, d, l = liu_params(lam)
     x = (q - c1) / np.sqrt(2.0 * c2) * (np.sqrt(2.0) * a) + (l + d)
     if x <= 0:
         return 1.0
@@ -115,6 +143,127 @@ def mixture_sf_saddlepoint(q, lam):
 
 
 _MIXTURE = {"saddlepoint": mixture_sf_saddlepoint, "liu": mixture_sf_liu}
+
+
+def check_rho(rho):
+    """The SKAT-O grid as a float64 array: None = ``RHO_DEFAULT``, else 1 .. 16 values in [0, 1]."""
+    rho = np.asarray(RHO_DEFAULT if rho is None else rho, dtype=np.float64).ravel()
+    if not 1 <= rho.size <= RHO_MAX:
+        raise ValueError("rho must hold 1 .. %d values, got %d" % (RHO_MAX, rho.size))
+    if not np.all((rho >= 0.0) & (rho <= 1.0)):           # (a NaN fails both comparisons)
+        raise ValueError("every rho must lie in [0, 1]")
+    return rho
+
+
+def _floor(lam, scale=0.0):
+    """The eigenvalues above ``LAMBDA_FLOOR`` times the largest; none where the largest is not above ``scale``."""
+    lam = np.asarray(lam, dtype=np.float64)
+    if not lam.size or not lam.max() > scale:
+        return lam[:0]
+    return lam[lam > LAMBDA_FLOOR * lam.max()]
+
+
+def skato_lines(T, lams, rho, tau):
+    """The lines whose lower envelope is SKAT-O's ``delta(x) = min_rho (q_min(rho) - tau(rho) x) / (1 - rho)``: intercepts and
+    slopes, with ``q_min(rho)`` the ``1 - T`` quantile of the modified Liu matching of the spectrum ``lams[rho]``."""
+    al, be = np.empty(rho.size), np.empty(rho.size)
+    for j, (r, lam) in enumerate(zip(rho, lams)):
+        c1, c2, _, _, l = liu_params(lam)
+        qmin = (stats.chi2.isf(T, l) - l) / np.sqrt(2.0 * l) * np.sqrt(2.0 * c2) + c1
+        al[j], be[j] = qmin / (1.0 - r), tau[j] / (1.0 - r)
+    return al, be
+
+
+def skato_breaks(al, be, level):
+    """``(z0, breaks)``: ``z0`` where the envelope of the lines ``al - be x`` (x = z^2) comes down to ``level`` (0 where it starts
+    below), and the sorted ends of the pieces of [0, min(z0, Z_END)] between the pairwise intersections of the lines."""
+    x0 = float(np.min((al - level) / be))
+    if not x0 > 0.0:
+        return 0.0, np.zeros(1)
+    z0 = float(np.sqrt(x0))
+    end = min(z0, Z_END)
+    pts = [0.0, end]
+    for i in range(al.size):
+        for j in range(i + 1, al.size):
+            if be[i] != be[j]:
+                x = (al[i] - al[j]) / (be[i] - be[j])
+                if x > 0.0 and np.sqrt(x) < end:
+                    pts.append(float(np.sqrt(x)))
+    return z0, np.unique(pts)
+
+
+def skato_pvalue(t, A, rho=RHO_DEFAULT, method="saddlepoint"):
+    """SKAT-O from ``t = w o s`` and ``A = diag(w) K diag(w)`` (r x r, positive semidefinite): ``(p, pmin, rho_at_min, p_rho)``.
+
+    Per grid value: ``Q_rho = (1 - rho) t't + rho (1't)^2`` against the mixture with the eigenvalues of ``L_rho' A L_rho``
+    (``L_rho L_rho' = R_rho``; those below ``LAMBDA_FLOOR`` times the largest dropped) by ``method``; ``pmin = T`` is the smallest
+    ``p_rho`` and ``rho_at_min`` the first grid value that attains it.  With ``a = A 1``, ``s11 = 1'A1`` and
+    ``B = A - a a' / s11``, the part of ``Q_rho`` beside the component along ``a`` has mean ``sum lam_B``, variance
+    ``2 sum lam_B^2 + 4 a'Ba / s11`` and ``df = (sum lam_B^2)^2 / sum lam_B^4``; ``tau(rho) = rho s11 + (1 - rho) a'a / s11``
+    multiplies the chi2_1 of that component, and
+
+        p = int_0^inf S_df((delta(z^2) - mu) / sigma sqrt(2 df) + df) 2 phi(z) dz,
+
+    in survival form (the package's ``1 - int F`` cancels to nothing below 1e-12), integrated piece by piece between the kinks
+    of ``delta`` and up to ``z0``, where the argument reaches 0 and the rest is ``2 Phi(-z0)``; then ``p <- min(p, n_rho T)``.
+    A value of ``rho`` above 0.999 is computed as 0.999.  One marker, ``s11 <= LAMBDA_FLOOR trace(A)`` or no eigenvalue of ``B``
+    above ``LAMBDA_FLOOR trace(A)`` (rank one: what is left of ``B`` is rounding): every ``p_rho`` is the same up to rounding,
+    ``p = T`` and ``rho_at_min`` is the first grid value."""
+    t = np.asarray(t, dtype=np.float64).ravel()
+    A = np.asarray(A, dtype=np.float64).reshape(t.size, t.size)
+    rho, sf = check_rho(rho), check_method(method)
+    r, nr = t.size, rho.size
+    rc = np.minimum(rho, RHO_CAP)
+    tt, t1 = float(t.dot(t)), float(t.sum())
+    p_rho, lams = np.full(nr, np.nan), []
+    one = np.ones((r, r))
+    for j, x in enumerate(rc):
+        if r == 1:
+            q, lam = tt, _floor(A.ravel())                  # ((1 - rho) q + rho q is not q bit for bit)
+        else:
+            L = la.cholesky((1.0 - x) * np.eye(r) + x * one, lower=True)
+            M = L.T.dot(A).dot(L)
+            q, lam = (1.0 - x) * tt + x * t1 * t1, _floor(la.eigvalsh(0.5 * (M + M.T)))
+        lams.append(lam)
+        if lam.size:
+            p_rho[j] = sf(q, lam)
+    if np.any(np.isnan(p_rho)):
+        return np.nan, np.nan, np.nan, p_rho
+    j0 = int(np.argmin(p_rho))
+    T = float(p_rho[j0])
+    tr = float(np.trace(A))
+    a = A.sum(axis=1)
+    s11 = float(a.sum())
+    lamB = np.empty(0)
+    if r > 1 and s11 > LAMBDA_FLOOR * tr:
+        B = A - np.outer(a, a) / s11
+        B = 0.5 * (B + B.T)
+        lamB = _floor(la.eigvalsh(B), LAMBDA_FLOOR * tr)
+    if not lamB.size:                  # every p_rho is the same up to rounding: the first grid value stands for the minimiser
+        return T, T, float(rho[0]), p_rho
+    if T == 0.0:                       # (T has underflowed: so has p, and the quantile of 0 is infinite)
+        return T, T, float(rho[j0]), p_rho
+    l2 = float(np.sum(lamB ** 2))
+    mu, var, df = float(lamB.sum()), 2.0 * l2 + 4.0 * max(float(a.dot(B).dot(a)), 0.0) / s11, l2 * l2 / float(np.sum(lamB ** 4))
+    sd = np.sqrt(var)
+    al, be = skato_lines(T, lams, rc, rc * s11 + (1.0 - rc) * float(a.dot(a)) / s11)
+    z0, pts = skato_breaks(al, be, mu - sd * np.sqrt(0.5 * df))
+
+    p = 2.0 * float(stats.norm.sf(z0))
+    k1, k2 = np.sqrt(2.0 * df) / sd, np.sqrt(2.0 / np.pi)
+    for lo, hi in zip(pts[:-1], pts[1:]):
+        # between two break points one line is the lowest: the one that is at the middle.  z = hi - (hi - lo) v^2 puts the
+        # square-root singularity that S_df has at z0 for df = 1 (at, or close behind, the piece's upper end) out of quad's way
+        mid = 0.5 * (lo + hi)
+        j = int(np.argmin(al - be * (mid * mid)))
+        a_j, b_j, h = float(al[j]), float(be[j]), hi - lo
+
+        def f(v):
+            z = hi - h * v * v
+            return special.chdtrc(df, (a_j - b_j * z * z - mu) * k1 + df) * k2 * np.exp(-0.5 * z * z) * 2.0 * h * v
+
+        p += integ.quad(f, 0.0, 1.0, epsabs=0.0, epsrel=1e-12, limit=200)[0]
+    return min(p, nr * T), T, float(rho[j0]), p_rho
 
 
 def check_sets(sets, m, block):
@@ -178,38 +327,68 @@ def pack_sets(sizes, block):
     return blocks
 
 
+def set_kernel(S, G, R, u, weights):
+    """``(s, K, w, keep)`` of one set from its columns ``S`` of a block's statistics ((c + 5) x r) and its sub-block ``G`` of X'X,
+    with the model's ``R`` and ``u``: the markers with an observed value and with variation are kept, ``z = R^-T S[4:4+c]``,
+    ``s = S[4+c] - u'z``, ``K = G - z'z`` symmetrised; ``weights``: "beta", None or one weight per marker of the set."""
+    c = R.shape[0]
+    n_obs, mean, css = S[0], S[1], S[2]
+    keep = ~((n_obs == 0) | (css == 0))
+    z = la.solve_triangular(R, S[4:4 + c], trans='T', lower=False)[:, keep]
+    s = S[4 + c][keep] - u.dot(z)
+    K = G[np.ix_(keep, keep)] - z.T.dot(z)
+    K = 0.5 * (K + K.T)
+    if weights is None:
+        w = np.ones(s.size)
+    elif isinstance(weights, str):
+        maf = np.minimum(0.5 * mean[keep], 1.0 - 0.5 * mean[keep])
+        w = stats.beta.pdf(maf, 1, 25)
+    else:
+        w = weights[keep]
+    return s, K, w, keep
+
+
 class VariantSetTest(AssociationScan):
     """Burden and SKAT tests of marker sets next to ``covariates`` under V = sum_k sigma2[k] mats[k].  The constructor is
     ``AssociationScan``'s; ``block`` bounds the markers of a set as well as of a device block."""
 
-    def __call__(self, genotypes, sets, weights="beta", method="saddlepoint", return_kernel=False):
+    def __call__(self, genotypes, sets, weights="beta", method="saddlepoint", return_kernel=False, skato=False, rho=None,
+                 finish="host"):
         """``genotypes``: m x n int8 as ``AssociationScan`` takes them; ``sets``: a sequence of 1-D integer arrays, the marker
         rows of each set (1 .. ``block`` distinct rows; a marker may belong to several sets); ``weights``: "beta" =
         Beta(1, 25) density at the marker's minor allele frequency, None = ones, or a sequence of arrays aligned with
         ``sets``; ``method``: "saddlepoint" or "liu" for ``skat_p``.  Returns a dict of length-``len(sets)`` arrays ``n_used``,
         ``burden_beta``, ``burden_se``, ``burden_chi2``, ``burden_p``, ``skat_q``, ``skat_p``; with ``return_kernel`` also
         ``kernel``, a list of ``(s, K, w)`` per set.  A marker without an observed value or without variation is dropped
-        from its set (``n_used`` counts the rest); a set with nothing left gets NaN."""
-        return self._run(Int8Rows(self, check_genotypes(genotypes, self.n)), sets, weights, method, return_kernel)
+        from its set (``n_used`` counts the rest); a set with nothing left gets NaN.
+
+        ``skato=True`` adds SKAT-O over the grid ``rho`` (None = ``RHO_DEFAULT``; 1 .. 16 values in [0, 1]): ``skato_p``,
+        ``skato_pmin`` (the smallest per-rho p-value), ``skato_rho`` (the first grid value that attains it) and ``skato_p_rho``
+        (n_sets x n_rho), the per-rho tails by ``method``.  ``finish="device"`` does everything after the Gram block on the
+        device (``scilmm_sets_finish_dev``) and brings back the sets' numbers alone; it excludes ``return_kernel``, and its
+        p-values agree with the host's to 1e-6 relative, not bit for bit.  With the three at their defaults the call is what it
+        was: the same keys, the same bits."""
+        return self._run(Int8Rows(self, check_genotypes(genotypes, self.n)), sets, weights, method, return_kernel, skato, rho, finish)
 
     def test_bed(self, bed, sets, sample_index=None, count="A1", chunk_bytes=None, weights="beta", method="saddlepoint",
-                 return_kernel=False):
+                 return_kernel=False, skato=False, rho=None, finish="host"):
         """``__call__`` on the markers of a PLINK 1 fileset, decoded on the device (``scilmm_scan_block_bed_gram_dev``):
         ``sets`` index the file's markers; ``bed``, ``sample_index`` and ``count`` as for ``AssociationScan.scan_bed``.  A
         block's packed rows are uploaded as they lie in the file, so ``chunk_bytes`` has nothing to bound and is accepted
         for symmetry only.  Returns the bits of ``__call__`` on ``bed.read(None, sample_index, count)`` in deterministic
-        mode."""
+        mode.  ``skato``, ``rho``, ``finish``: as for ``__call__``."""
         src = self._bed_source(bed, sample_index, count)
         if chunk_bytes is not None and int(chunk_bytes) < 1:
             raise ValueError("chunk_bytes must be positive")
-        return self._run(src, sets, weights, method, return_kernel)
+        return self._run(src, sets, weights, method, return_kernel, skato, rho, finish)
 
-    def test_dosages(self, dosages, sets, sample_index=None, weights="beta", method="saddlepoint", return_kernel=False):
+    def test_dosages(self, dosages, sets, sample_index=None, weights="beta", method="saddlepoint", return_kernel=False, skato=False,
+                     rho=None, finish="host"):
         """``__call__`` on imputed dosages (``scilmm_scan_block_dosage_gram_dev``): ``sets`` index the rows of ``dosages``;
         ``dosages`` and ``sample_index`` as for ``AssociationScan.scan_dosages``.  The "beta" weights take half the mean
         dosage for the allele frequency.  For uint16 codes of hard calls it returns the bits of ``__call__`` on the int8
-        markers in deterministic mode."""
-        return self._run(self._dosage_source(dosages, sample_index), sets, weights, method, return_kernel)
+        markers in deterministic mode.  ``skato``, ``rho``, ``finish``: as for ``__call__``."""
+        return self._run(self._dosage_source(dosages, sample_index), sets, weights, method, return_kernel, skato, rho, finish)
 
     def _block(self, src):
         """rows -> ((q + 4) x r statistics, r x r Gram matrix) of one block of the marker source ``src``, on the host: the rows
@@ -227,45 +406,89 @@ class VariantSetTest(AssociationScan):
             return dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb), dK[:rb * rb].cpu().numpy().reshape(rb, rb)
         return run
 
-    def _run(self, src, sets, weights, method, return_kernel):
+    def _block_device(self, src, mode, method, rho):
+        """(rows, offsets, weights) -> the block's per-set rows of ``scilmm_sets_finish_dev`` (n_sets x (10 + n_rho)), on the host:
+        the rows and the weights are brought to the device, the form's Gram entry point and the finish are queued one behind the
+        other, one wait, one device-to-host copy of the sets' rows."""
+        torch, q, blk = self.torch, self.q, self.block
+        src.stage(blk)
+        vp = C.c_void_p
+        dS = torch.empty(((q + 4) * blk,), dtype=torch.float64, device="cuda")
+        dK = torch.empty((blk * blk,), dtype=torch.float64, device="cuda")
+        dR = torch.from_numpy(np.ascontiguousarray(self.R)).cuda()
+        du = torch.from_numpy(np.ascontiguousarray(self.u)).cuda()
+        dW = torch.empty((blk,), dtype=torch.float64, device="cuda")
+        ld = FINISH_HEAD + rho.size
+        dO = torch.empty((blk * ld,), dtype=torch.float64, device="cuda")
+        meth = METHODS.index(method)
+
+        def run(rows, start, w):
+            rb, ns = rows.size, start.size - 1
+            src.load(rows)
+            if w is not None:
+                dW[:rb].copy_(torch.from_numpy(w))
+            src.enqueue(0, rb, vp(dS.data_ptr()), vp(dK.data_ptr()))
+            self.factor.sets_finish_dev(rb, q, vp(dS.data_ptr()), vp(dK.data_ptr()), vp(dR.data_ptr()), vp(du.data_ptr()), self.c, ns,
+                                        start, mode, vp(dW.data_ptr()) if w is not None else None, meth, rho, vp(dO.data_ptr()), ld, None)
+            self.sym.sync()
+            return dO[:ns * ld].cpu().numpy().reshape(ns, ld)
+        return run
+
+    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host"):
         """The checks of the sets (before any launch), then block by block: gather the block's marker rows, one device call, the
-        statistics and the Gram matrix (``_block``), the host algebra set by set."""
+        statistics and the Gram matrix (``_block``), the host algebra set by set -- or, with ``finish="device"``, the finish
+        queued behind the block and the sets' rows alone brought back (``_block_device``)."""
         sets = check_sets(sets, src.m, self.block)
         weights, sf = check_weights(weights, sets), check_method(method)
+        if finish not in FINISHES:
+            raise ValueError("finish must be one of %s, got %r" % (", ".join(FINISHES), finish))
+        if finish == "device" and return_kernel:
+            raise ValueError('return_kernel=True needs finish="host": the device finish does not bring K back')
+        rho = check_rho(rho) if skato else None
         self._check_factor()
-        block = self._block(src) if sets else None
         ns = len(sets)
         out = {k: np.full(ns, np.nan) for k in KEYS}
         out["n_used"] = np.zeros(ns, dtype=np.int64)
+        if skato:
+            out.update({k: np.full(ns, np.nan) for k in SKATO_KEYS[:3]})
+            out["skato_p_rho"] = np.full((ns, rho.size), np.nan)
+        packed = pack_sets([s.size for s in sets], self.block)
+        if finish == "device":
+            given = not (weights is None or isinstance(weights, str))
+            mode = WEIGHT_GIVEN if given else WEIGHT_ONES if weights is None else WEIGHT_BETA
+            grid = rho if skato else np.empty(0)
+            block = self._block_device(src, mode, method, grid) if sets else None
+            for members in packed:
+                start = np.concatenate([[0], np.cumsum([sets[i].size for i in members])]).astype(np.int32)
+                w = np.ascontiguousarray(np.concatenate([weights[i] for i in members])) if given else None
+                O = block(np.concatenate([sets[i] for i in members]), start, w)
+                out["n_used"][members] = O[:, 0].astype(np.int64)
+                for col, k in ((1, "burden_beta"), (2, "burden_se"), (3, "burden_chi2"), (4, "skat_q"), (5, "skat_p")):
+                    out[k][members] = O[:, col]
+                if skato:
+                    for col, k in ((6, "skato_p"), (7, "skato_pmin"), (8, "skato_rho")):
+                        out[k][members] = O[:, col]
+                    out["skato_p_rho"][members] = O[:, FINISH_HEAD:]
+            used = out["n_used"] > 0
+            out["burden_p"][used] = self._f.sf(out["burden_chi2"][used])     # (one vectorised call over the sets)
+            return out
+        block = self._block(src) if sets else None
         kernel = [None] * ns
-        for members in pack_sets([s.size for s in sets], self.block):
+        for members in packed:
             S, G = block(np.concatenate([sets[i] for i in members]))
             a = 0
             for i in members:
                 b = a + sets[i].size
                 w = weights if weights is None or isinstance(weights, str) else weights[i]
-                kernel[i] = self._one_set(out, i, S[:, a:b], G[a:b, a:b], w, sf)
+                kernel[i] = self._one_set(out, i, S[:, a:b], G[a:b, a:b], w, sf, rho, method)
                 a = b
         if return_kernel:
             out["kernel"] = kernel
         return out
 
-    def _one_set(self, out, i, S, G, weights, sf):
+    def _one_set(self, out, i, S, G, weights, sf, rho=None, method="saddlepoint"):
         """The host algebra of set ``i`` on its columns of the statistics and its sub-block of X'X; returns (s, K, w)."""
-        c = self.c
-        n_obs, mean, css = S[0], S[1], S[2]
-        keep = ~((n_obs == 0) | (css == 0))
-        z = la.solve_triangular(self.R, S[4:4 + c], trans='T', lower=False)[:, keep]
-        s = S[4 + c][keep] - self.u.dot(z)
-        K = G[np.ix_(keep, keep)] - z.T.dot(z)
-        K = 0.5 * (K + K.T)
-        if weights is None:
-            w = np.ones(s.size)
-        elif isinstance(weights, str):
-            maf = np.minimum(0.5 * mean[keep], 1.0 - 0.5 * mean[keep])
-            w = stats.beta.pdf(maf, 1, 25)
-        else:
-            w = weights[keep]
+        s, K, w, keep = set_kernel(S, G, self.R, self.u, weights)
         out["n_used"][i] = k = int(keep.sum())
         if k:
             ws, wKw = float(w.dot(s)), float(w.dot(K.dot(w)))
@@ -275,7 +498,10 @@ class VariantSetTest(AssociationScan):
                 out["burden_chi2"][i] = chi2 = ws * ws / wKw
             out["burden_p"][i] = self._f.sf(chi2)
             out["skat_q"][i] = qs = float(np.sum(w * w * s * s))
-            lam = la.eigvalsh(w[:, None] * K * w[None, :])
+            A = w[:, None] * K * w[None, :]
+            lam = la.eigvalsh(A)
             if lam.size and lam.max() > 0:
                 out["skat_p"][i] = sf(qs, lam[lam > LAMBDA_FLOOR * lam.max()])
+                if rho is not None:
+                    out["skato_p"][i], out["skato_pmin"][i], out["skato_rho"][i], out["skato_p_rho"][i] = skato_pvalue(w * s, A, rho, method)
         return s, K, w

@@ -7,7 +7,12 @@ run inside the statistics interval, so their time is the paired difference of th
 side in the same run; it needs a library built with `make DIAG=1` (SCILMM_HIP_LIB), which reads SCILMM_GRAM_SHAPE per call.
 Reported per shape: Gram + fold time, its ratio to k_scan_stats + k_scan_fold on the same X, the bandwidth n * rp * 8 bytes /
 time implies (against the 6.3 TB/s a streaming read achieves on this part), the block's total as a fraction of the plain
-block's, and the agreement of X'X with the gg row and between shapes."""
+block's, and the agreement of X'X with the gg row and between shapes.
+  usage: sets_timing.py 100k --finish [--out profiles/sets_finish_100k.json]
+--finish times the finish of a block instead (scilmm_sets_finish_dev): 512 markers in consecutive sets of 2 .. 17 markers, packed
+into 128-wide blocks, and a block that is one 128-marker set.  Per block: k_sets_finish by HIP events, with and without SKAT-O
+(three warm-up rounds, 20 rounds, median and IQR), next to the block's forward sweep; and the wall time per set of the whole
+call with finish="device" and finish="host", with and without skato, on the same packed sets (the median of three calls)."""
 import argparse, ctypes, json, os, sys
 import numpy as np
 import scipy.sparse as sp
@@ -16,6 +21,7 @@ import bench
 ap = argparse.ArgumentParser()
 ap.add_argument("workload"); ap.add_argument("--blocks", type=int, default=20); ap.add_argument("--out", default=None)
 ap.add_argument("--shapes", default=None)
+ap.add_argument("--finish", action="store_true")
 args = ap.parse_args()
 import torch
 from scilmm_amd import SparseCholesky, VariantSetTest
@@ -36,6 +42,72 @@ torch.cuda.synchronize()
 shapes = ["default"] + ([s for s in args.shapes.split(",") if s] if args.shapes else [])
 
 
+def summary(v):
+    v = np.asarray(v, dtype=float)
+    return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()),
+            "iqr": float(np.percentile(v, 75) - np.percentile(v, 25))}
+
+
+def finish_leg():
+    import time
+    from scilmm_amd.sets import FINISH_HEAD, RHO_DEFAULT, pack_sets
+    M = 512
+    Gm = rng.binomial(2, rng.uniform(0.005, 0.05, M)[:, None], size=(M, n)).astype(np.int8)
+    Gm[rng.random(Gm.shape) < 0.02] = -1
+    sets, at = [], 0
+    while at < M:
+        k = min(int(rng.integers(2, 18)), M - at)
+        sets.append(np.arange(at, at + k))
+        at += k
+    packed = pack_sets([s.size for s in sets], R)
+    rho = np.asarray(RHO_DEFAULT)
+    dR = torch.from_numpy(np.ascontiguousarray(tester.R)).cuda()
+    du = torch.from_numpy(np.ascontiguousarray(tester.u)).cuda()
+    dO = torch.zeros((R * (FINISH_HEAD + rho.size),), dtype=torch.float64, device="cuda")
+    rec = {"workload": args.workload, "n": int(n), "r": R, "markers": M, "n_sets": len(sets), "set_sizes": [int(s.size) for s in sets],
+           "blocks": [], "timer": "HIP events around k_sets_finish, one call per synchronise; three warm-up rounds, then %d rounds" % args.blocks}
+    shapes_ = [("packed block %d" % b, np.concatenate([sets[i] for i in mem]), [sets[i].size for i in mem]) for b, mem in enumerate(packed)]
+    shapes_.append(("one set of 128", np.arange(R), [R]))
+    for name, rows, sizes in shapes_:
+        rb = rows.size
+        dG[:rb, :n].copy_(torch.from_numpy(np.ascontiguousarray(Gm[rows])))
+        torch.cuda.synchronize()
+        start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        fac.scan_block_gram_dev(vp(dG.data_ptr()), ld, rb, vp(tester.dQ.data_ptr()), q, vp(dS.data_ptr()), vp(dK.data_ptr())); sym.sync()
+        block_ms = sym.scan_timing()
+        t = {"skato": [], "burden_skat": []}
+        for it in range(3 + args.blocks):
+            for key, grid in (("skato", rho), ("burden_skat", rho[:0])):
+                fac.sets_finish_dev(rb, q, vp(dS.data_ptr()), vp(dK.data_ptr()), vp(dR.data_ptr()), vp(du.data_ptr()), q - 1, len(sizes), start,
+                                    0, None, 0, grid, vp(dO.data_ptr()), FINISH_HEAD + rho.size, None)
+                sym.sync()
+                if it >= 3: t[key].append(sym.sets_finish_timing())
+        rec["blocks"].append({"block": name, "markers": int(rb), "sets": len(sizes), "largest_set": int(max(sizes)),
+                              "gram_block_ms": {"prep": block_ms[0], "sweep": block_ms[1], "stats_gram": block_ms[2]},
+                              "finish_skato_ms": summary(t["skato"]), "finish_burden_skat_ms": summary(t["burden_skat"])})
+    wall = {}
+    for fin in ("device", "host"):
+        for sk in (False, True):
+            ts = []
+            for it in range(4):
+                t0 = time.perf_counter()
+                tester(Gm, sets, skato=sk, finish=fin)
+                ts.append(time.perf_counter() - t0)
+            wall["%s%s" % (fin, "+skato" if sk else "")] = {"ms_per_set_median_of_3": 1e3 * float(np.median(ts[1:])) / len(sets),
+                                                               "ms_per_call": [1e3 * v for v in ts[1:]]}
+    rec["wall"] = wall
+    return rec
+
+
+if args.finish:
+    rec = finish_leg()
+    print(json.dumps(rec))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        json.dump(rec, open(args.out, "w"), indent=1)
+    sys.exit(0)
+
+
 def scan():
     fac.scan_block_dev(vp(dG.data_ptr()), ld, R, vp(tester.dQ.data_ptr()), q, vp(dS.data_ptr())); sym.sync()
     return sym.scan_timing()
@@ -48,12 +120,6 @@ def gram(shape):
         os.environ["SCILMM_GRAM_SHAPE"] = shape
     fac.scan_block_gram_dev(vp(dG.data_ptr()), ld, R, vp(tester.dQ.data_ptr()), q, vp(dS.data_ptr()), vp(dK.data_ptr())); sym.sync()
     return sym.scan_timing()
-
-
-def summary(v):
-    v = np.asarray(v, dtype=float)
-    return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()),
-            "iqr": float(np.percentile(v, 75) - np.percentile(v, 25))}
 
 
 t_scan, t_gram = [], {s: [] for s in shapes}
