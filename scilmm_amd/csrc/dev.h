@@ -62,6 +62,8 @@ struct Tuning {
   int64_t push_slice = 512;            // SCILMM_PUSH_SLICE      rows per slice of a long backward push group (>= 256)
   // -- read per call (the parity tests force each value on one handle)
   bool shadow = true;                  // SCILMM_SHADOW=0        run_factorize: k_dense32 instead of the fp32 shadow (k_dense_h)
+  bool dense_feed = true;              // SCILMM_DENSE_FEED=0    run_factorize: k_dense_b's chunk loop before the hand-counted waits
+                                       //                        (k_dense_b<0>; same bits: tests/test_gpu_dense_feed.py)
   int chain_wide_t = 160;              // SCILMM_CHAIN_WIDE_T    run_rhs: chains from this length on sweep 64-column windows (pipelined pair loop)
   int chain_full_t = 768;              // SCILMM_CHAIN_FULL_T    run_rhs: ... and from this length on one 112-column window
   bool chain_pipe = true;              // SCILMM_CHAIN_PIPE=0    run_rhs: k_chain's pair loop without the software pipeline
@@ -74,9 +76,20 @@ struct Tuning {
   int sinv_cc_tiles = 2;               // SCILMM_SINV_CC_TILES   deterministic mode: 128-row tiles per segment of k_sinv_cc_ordered (>= 1)
 };
 
+// SCILMM_DENSE_FEED=0 (under SCILMM_TUNING=1, read per factorization) runs k_dense_b's chunk loop as it was before the
+// hand-counted waits (k_dense_b<0>).  It changes no schedule, no item and no bit of the factor -- its cases are
+// tests/test_gpu_dense_feed.py and test_gpu_dense_reach.py, which compare L bit for bit -- so it is read here and not among
+// the schedule switches whose every value the parity tables of test_gpu_factor_schedules.py factor against the oracle.
+inline bool read_dense_feed() {
+  const char* gate = getenv("SCILMM_TUNING");
+  const char* e = getenv("SCILMM_DENSE_FEED");
+  return !(gate && gate[0] == '1' && e && e[0] == '0');
+}
+
 // The environment is read on every call: tests switch SCILMM_TUNING and a switch on and off inside one process.
 inline Tuning read_tuning() {
   Tuning t;
+  t.dense_feed = read_dense_feed();
   const char* gate = getenv("SCILMM_TUNING");
   if (!(gate && gate[0] == '1')) return t;
   auto env = [](const char* name) { return getenv(name); };

@@ -411,7 +411,8 @@ constexpr int KBA = 64;            // depth of a B buffer of the dense-tail kern
 constexpr int LDA2 = DTR + 16;     // == 16 mod 32 doubles: conflict-free b64 fragment reads
 
 #ifdef SCILMM_DENSE_CLK
-__device__ unsigned long long g_dense_clk[2];  // tuning harness only: summed wall-clock (100 MHz) / shader-clock ticks of wave 0
+__device__ unsigned long long g_dense_clk[2];  // tuning harness only (k_dense_b, wave 0 of every workgroup, s_memtime ticks): [0] the chunk
+                                               // loop, [1] of it from reaching a chunk boundary's wait to leaving its barrier
 #endif
 
 // a wave-uniform pointer / integer moved to scalar registers (lets loads use the SGPR-base + 32-bit lane offset form)
@@ -447,9 +448,52 @@ typedef const __attribute__((address_space(1))) void* gl_vptr;
 //    its last 4-deep block (their B rows are the zero page's), at most 3 columns past the panel -- inside the slack the
 //    factor storage keeps behind every panel for exactly this kind of over-read.
 //  (Measured and dropped: a lane owning two ADJACENT rows, one 16-byte load per k -- 59.6 instead of 62.2 TFLOP/s.)
+//  * FEED (what waits where; the products, the sums and their order are the same in all three, the slabs bit-identical):
+//    0  the loop as it was (SCILMM_TUNING=1 SCILMM_DENSE_FEED=0): `s_waitcnt vmcnt(0) lgkmcnt(0)` before the barrier of a chunk
+//       boundary, A fragments by ordinary loads, the descendant's symbolic entries read at the boundary where it starts.  Its
+//       disassembly shows what the source does not: an LDS-DMA copy counts as a vector-memory AND an LDS operation, and while
+//       one is pending the compiler makes every wait for a loaded register a FULL one -- so behind the eight copies of the
+//       chunk after next, right in front of the last k-step's MFMAs, stands a second `vmcnt(0) lgkmcnt(0)`: all eight waves sit
+//       out the round trip of copies they need a whole chunk later, once per chunk, both waves of every SIMD at the same time.
+//       (And once per descendant, at the same place, the round trip of its symbolic entries.)
+//    1  0 with a counted wait, vmcnt(8), at the boundary (tuning harness only: the compiler's full wait behind it remains).
+//    2  the default.  The A fragments are loaded by inline assembly and every wait for them is counted by hand, so the loop
+//       holds no load the compiler knows of and no wait of its own.  A wave's vector-memory operations between two boundaries
+//       are, in program order, the 8 copies (right behind the barrier) and 4 x 8 A loads (k-steps 0, 4, 8, 12); they retire in
+//       order for vmcnt.  The fragments of a sub-chunk are waited for with the loads of the next one behind them (vmcnt(8); at
+//       k-step 0 also the copies: vmcnt(16)), the copies of the NEXT chunk -- one chunk old -- at the boundary with only
+//       load_A(nxt, 0) behind them (vmcnt(8)).  The waits name the fragment registers as in/out operands: no MFMA can be
+//       scheduled in front of its wait.  The next descendant's symbolic entries come by scalar loads in the MIDDLE of the chunk
+//       before (k-step 8), where the other wave of the SIMD covers their latency, instead of behind the barrier.
 #ifndef SCILMM_DENSE_B_SG
 #define SCILMM_DENSE_B_SG 1   // 1: interleave one LDS read with four MFMAs (sched_group_barrier); 0: leave it to the scheduler
 #endif
+// A dense item whose K range the plan trimmed to nothing (no descendant of its segment reaches its rows) still owns its
+// partial slabs -- k_reduce / k_potrf / k_trsm fold them by count -- so it stores zeros there; with slot < 0 it has nothing to do.
+// (tile = -1: both tiles of the item, else that tile alone; every thread of the workgroup calls it)
+__device__ __forceinline__ void dense_empty_item(const DenseWork& wk, double* __restrict__ scratch, int tile) {
+  for (int h = 0; h < wk.ntiles; ++h) {
+    const int32_t slot = h ? wk.slot1 : wk.slot0;
+    if (slot < 0 || (tile >= 0 && tile != h)) continue;
+    double* sl = scratch + (int64_t)slot * (TM * NB);
+    for (int i = threadIdx.x; i < TM * NB; i += blockDim.x) sl[i] = 0.0;
+  }
+}
+// the in/out operands tie the wait to the eight fragment registers it is for
+#define SCILMM_WAIT_A(a, N)                                                                                                \
+  asm volatile("s_waitcnt vmcnt(" #N ")"                                                                                   \
+               : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]), "+v"(a[3][1]))
+// ... with one of two counts, chosen by a wave-uniform flag INSIDE the statement: two statements in the arms of a branch would
+// meet in a phi, and the register copies of a phi may be placed in front of the wait -- copies of registers whose loads are
+// still in flight.  (A load by inline assembly is complete only behind its wait; the compiler does not know that.  The
+// disassembly of k_dense_b<2> must show no instruction that reads a fragment register between its load and its wait.)
+#define SCILMM_WAIT_A2(a, flag, N1, N0)                                                                                    \
+  asm volatile("s_cmp_eq_u32 %8, 0\n\ts_cbranch_scc1 .Lwa0_%=\n\ts_waitcnt vmcnt(" #N1 ")\n\ts_branch .Lwa1_%=\n"            \
+               ".Lwa0_%=:\n\ts_waitcnt vmcnt(" #N0 ")\n.Lwa1_%=:"                                                          \
+               : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]), "+v"(a[3][1])  \
+               : "s"(uniform_int((int)(flag)))                                                                                       \
+               : "scc")
+template <int FEED>
 __global__ __launch_bounds__(512, 1) void k_dense_b(DevSym S, int32_t dense_first, const DenseWork* __restrict__ work,
                                                     double* __restrict__ L, double* __restrict__ scratch,
                                                     const double* __restrict__ zeros) {
@@ -475,8 +519,27 @@ __global__ __launch_bounds__(512, 1) void k_dense_b(DevSym S, int32_t dense_firs
   //  chunk boundary from fresh loads stalls every wave for their latency right before the last k-step's MFMAs)
   int32_t d_wd = 0, d_md = 0;
   const double* d_P0 = nullptr;  // column 0 of the current descendant's panel, at the target's first column's row
+  // FEED == 2: descendant kd's entries, fetched ahead by scalar loads (the wait is part of the statement: its results are
+  // valid where the compiler believes them to be)
+  int32_t n_wd = 0, n_md = 0;
+  const double* n_P0 = nullptr;
+  auto fetch_desc = [&]() {
+    const int32_t d = uniform_int(dense_first + kd);
+    uint64_t c01;
+    int64_t lo;
+    asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(c01), "=&s"(lo)
+                 : "s"(S.sn_start + d), "s"(S.sn_loff + d)
+                 : "memory");
+    const int32_t c0d = (int32_t)(uint32_t)c01;
+    n_wd = (int32_t)(uint32_t)(c01 >> 32) - c0d;
+    n_md = S.n - c0d;
+    n_P0 = L + (lo + (c0j - c0d));
+  };
   auto next_chunk = [&]() {
-    if (kk0 == 0) {
+    if (FEED == 2) {
+      if (kk0 == 0) { d_wd = n_wd; d_md = n_md; d_P0 = n_P0; }
+    } else if (kk0 == 0) {
       const int32_t d = dense_first + kd;
       const int32_t c0d = S.sn_start[d];
       d_wd = __builtin_amdgcn_readfirstlane(S.sn_start[d + 1] - c0d);
@@ -516,14 +579,19 @@ __global__ __launch_bounds__(512, 1) void k_dense_b(DevSym S, int32_t dense_firs
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const double* sp = c.Pd + (int64_t)min(16 * s + 4 * q, klast) * c.md;  // wave-uniform
-      ra[q][0] = ld_off(sp, c.v0);
-      ra[q][1] = ld_off(sp, c.v1);
+      if (FEED == 2) {
+        asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(ra[q][0]) : "v"(c.v0), "s"(sp));
+        asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(ra[q][1]) : "v"(c.v1), "s"(sp));
+      } else {
+        ra[q][0] = ld_off(sp, c.v0);
+        ra[q][1] = ld_off(sp, c.v1);
+      }
     }
   };
   d4 acc16[NJB][2];
 #pragma unroll
   for (int a = 0; a < NJB; ++a) { acc16[a][0] = (d4){0.0, 0.0, 0.0, 0.0}; acc16[a][1] = (d4){0.0, 0.0, 0.0, 0.0}; }
-  if (wk.k0 >= wk.k1) return;
+  if (wk.k0 >= wk.k1) { dense_empty_item(wk, scratch, -1); return; }
   double rA[2][4][2];
   double bf[2][NJB];
   auto ldB = [&](const double* Bc, int k4, double (&b)[NJB]) {
@@ -537,19 +605,26 @@ __global__ __launch_bounds__(512, 1) void k_dense_b(DevSym S, int32_t dense_firs
       acc16[jb][1] = mfma_f64(b[jb], a1, acc16[jb][1]);
     }
   };
+  if (FEED == 2) fetch_desc();
   Chunk cur = next_chunk();
   issue_B(cur, 0);
   load_A(cur, 0, rA[0]);
   bool more = kd < wk.k1;
   Chunk nxt = cur;
   if (more) {
+    if (FEED == 2 && kk0 == 0) fetch_desc();
     nxt = next_chunk();
     issue_B(nxt, 1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (FEED == 2) SCILMM_WAIT_A(rA[0], 0);
   __syncthreads();
   int buf = 0;
   ldB(smem, 0, bf[0]);
+#ifdef SCILMM_DENSE_CLK
+  uint64_t clk_wait = 0;
+  const uint64_t clk_0 = __builtin_amdgcn_s_memtime();
+#endif
   while (true) {
     const double* Bc = smem + buf * KBA * LDB;
     const double* Bn = smem + (buf ^ 1) * KBA * LDB;
@@ -562,14 +637,31 @@ __global__ __launch_bounds__(512, 1) void k_dense_b(DevSym S, int32_t dense_firs
         // the A fragments of the next sub-chunk (or of the next chunk's first one): one sub-chunk of MFMA time ahead
         if (s < 3) load_A(cur, s + 1, rA[(s + 1) & 1]);
         else if (more) load_A(nxt, 0, rA[0]);
+        if (FEED == 2) {
+          // the fragments of sub-chunk s, with the loads just issued (and at s == 0 the boundary's copies) still in flight
+          // (without a next chunk -- the item's last one -- the boundary before issued no copies and k-step 12 issues no loads)
+          if (s == 0) SCILMM_WAIT_A2(rA[0], more, 16, 8);
+          else if (s < 3) SCILMM_WAIT_A(rA[s & 1], 8);
+          else SCILMM_WAIT_A2(rA[1], more, 8, 0);
+          // the boundary of this chunk starts a descendant: its entries now, while the SIMD's other wave multiplies
+          if (s == 2 && more && kk0 == 0 && kd < wk.k1) fetch_desc();
+        }
       }
       if (t < 15) {
         ldB(Bc, 4 * (t + 1), bf[(t + 1) & 1]);
       } else if (more) {
         // chunk boundary: every wave has READ its last fragments of Bc (they are in registers) and the copy of the next
         // chunk has landed -- after this barrier Bn may be read and Bc overwritten
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+#ifdef SCILMM_DENSE_CLK
+        const uint64_t clk_b = __builtin_amdgcn_s_memtime();
+#endif
+        // (lgkmcnt(0): this wave's last LDS reads of Bc are done before the buffer is overwritten)
+        if (FEED != 0) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
+#ifdef SCILMM_DENSE_CLK
+        clk_wait += __builtin_amdgcn_s_memtime() - clk_b;
+#endif
         ldB(Bn, 0, bf[0]);
         more2 = kd < wk.k1;
         if (more2) {
@@ -595,6 +687,12 @@ __global__ __launch_bounds__(512, 1) void k_dense_b(DevSym S, int32_t dense_firs
     more = more2;
     buf ^= 1;
   }
+#ifdef SCILMM_DENSE_CLK
+  if (tid == 0) {
+    atomicAdd(&g_dense_clk[0], (unsigned long long)(__builtin_amdgcn_s_memtime() - clk_0));
+    atomicAdd(&g_dense_clk[1], (unsigned long long)clk_wait);
+  }
+#endif
   double* P = L + S.sn_loff[j];
 #pragma unroll
   for (int jb = 0; jb < NJB; ++jb)
@@ -682,7 +780,7 @@ __global__ __launch_bounds__(512, 1) void k_dense32(DevSym S, int32_t dense_firs
 #pragma unroll
   for (int a = 0; a < NJB; ++a) { acc[a][0] = (d4){0.0, 0.0, 0.0, 0.0}; acc[a][1] = (d4){0.0, 0.0, 0.0, 0.0}; }
   const int li = lane & 15, lk = lane >> 4;
-  if (wk.k0 >= wk.k1) return;
+  if (wk.k0 >= wk.k1) { dense_empty_item(wk, scratch, -1); return; }
   load_chunk();
   int kc_cur = kc_ld;
   store_chunk(0);
@@ -788,7 +886,8 @@ __global__ __launch_bounds__(512, SCILMM_DENSE_H_WGS) void k_dense_h(DevSym S, i
   const int li = lane & 15, lk = lane >> 4;
   const DenseWork wk = work[blockIdx.x >> 1];
   const int th = blockIdx.x & 1;        // which of the item's two 128-row tiles
-  if (th >= wk.ntiles || wk.k0 >= wk.k1) return;
+  if (th >= wk.ntiles) return;
+  if (wk.k0 >= wk.k1) { dense_empty_item(wk, scratch, th); return; }
   const int32_t j = wk.front;
   const int32_t c0j = S.sn_start[j], wj = S.sn_start[j + 1] - c0j;
   const int32_t mj = S.n - c0j;

@@ -22,7 +22,8 @@ int set_attrs(scilmm_symbolic* sym, Dev* D) {
   HIPCHK(hipFuncSetAttribute((const void*)k_fwd<false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_dense32, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_dense_h, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-  HIPCHK(hipFuncSetAttribute((const void*)k_dense_b, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+  HIPCHK(hipFuncSetAttribute((const void*)k_dense_b<2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+  HIPCHK(hipFuncSetAttribute((const void*)k_dense_b<0>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_update2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_update2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   D->attrs_set = true;
@@ -39,6 +40,7 @@ struct FactorLaunch {
   Dev* const D;
   scilmm_factor* const fac;
   int64_t launches = 0;  // scilmm_timing.n_launches
+  const bool dense_feed = read_dense_feed();  // read per factorization, like SCILMM_SHADOW
 
   void update(hipStream_t stream, const UpdWork* work, int64_t cnt, double* scratch_half) {
 #ifdef SCILMM_DIAG
@@ -65,8 +67,9 @@ struct FactorLaunch {
         hipLaunchKernelGGL(k_dense32, dim3(c), dim3(512), sizeof(float) * (size_t)(2 * KC * LDA2F + 2 * KC * LDBF), stream, D->v,
                            dense_first, dw + o, fac->L, scratch_half);
       else
-        hipLaunchKernelGGL(k_dense_b, dim3(c), dim3(512), sizeof(double) * (size_t)(2 * KBA * LDB), stream, D->v, dense_first, dw + o,
-                           fac->L, scratch_half, (const double*)D->d_zeros);
+        hipLaunchKernelGGL(dense_feed ? k_dense_b<2> : k_dense_b<0>, dim3(c), dim3(512),
+                           sizeof(double) * (size_t)(2 * KBA * LDB), stream, D->v, dense_first, dw + o, fac->L, scratch_half,
+                           (const double*)D->d_zeros);
       launches++;
     }
   }

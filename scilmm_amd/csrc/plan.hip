@@ -1108,6 +1108,7 @@ struct WorkCut {
   const int32_t Wg = D->dist_Wg;
   std::vector<std::vector<uint8_t>> own_pair_on;  // [own tail front (relative)] -> mask, dist mode only
   int64_t dense_pairs_all = 0, dense_pairs_kept = 0, dense_tiles_all = 0, dense_tiles_kept = 0;
+  int64_t dense_prod_all = 0, dense_prod_kept = 0, dense_items_empty = 0;  // (tile pair, descendant) products of the items; items trimmed to nothing
 
   WorkCut(const Symbolic& S_, Dev* D_, const PlanBuild& pb_) : S(S_), D(D_), pb(pb_), dptr(pb_.dptr), dmid(pb_.dmid) {
     const int64_t ntiles = (int64_t)S.tile_front.size();
@@ -1421,11 +1422,42 @@ struct WorkCut {
     if (dj >= 0) {
       // K-segment major, tile-pair minor (same reason as above); a pair = two vertically adjacent tiles of the front
       const int32_t ntl = (int32_t)(S.tile_base[dj + 1] - S.tile_base[dj]);
+      // PER-PAIR REACH: the K segments are the same for every tile pair of the target, but a descendant whose true rows do not
+      // reach a pair's 256 rows holds only padding (zeros) there.  The pair's rows lie in the tail fronts f_lo..f_hi; descendant d
+      // reaches the pair if f_lo <= jj (the target's own columns: every active descendant has rows there) or if its row blocks
+      // (tail_blk) hold one of the fronts max(f_lo, jj + 1)..f_hi.  Every item's K range is trimmed to its first and last
+      // reaching descendant (zero products dropped from both ends: the sums keep their values and their order); an item that
+      // no descendant of its segment reaches is still emitted, with k0 == k1 -- slab numbering, the fitted item counts and the
+      // taper stay as they are, and the kernels store zeros to such an item's slabs.
+      const int32_t jj = dj - S.dense_first;
+      const bool reach_known = !tail_src.empty() && jj > 0;
+      const int32_t c0t = S.sn_start[S.dense_first], c0j = S.sn_start[dj];
+      auto trim = [&](int32_t q, int32_t& k0, int32_t& k1) {
+        if (!reach_known || k1 <= k0) return;
+        const int64_t lo = (int64_t)c0j + (int64_t)TM * q, hi = std::min<int64_t>(lo + 2 * TM, S.n);
+        const int32_t f_lo = tail_col_front[(size_t)(lo - c0t)], f_hi = tail_col_front[(size_t)(hi - 1 - c0t)];
+        if (f_lo <= jj) return;
+        int32_t first = k1, last = k0 - 1;
+        for (int32_t f = f_lo; f <= f_hi; ++f) {
+          const std::vector<int32_t>& sf = tail_src[(size_t)f];
+          const auto a = std::lower_bound(sf.begin(), sf.end(), k0), b = std::lower_bound(sf.begin(), sf.end(), k1);
+          if (a != b) {
+            first = std::min(first, *a);
+            last = std::max(last, *(b - 1));
+          }
+        }
+        if (first > last) k1 = k0;
+        else { k0 = first; k1 = last + 1; }
+      };
       auto emit = [&](std::vector<DenseWork>& out, const std::vector<std::pair<int32_t, int32_t>>& segs, const std::vector<int32_t>& base) {
         for (size_t sg = 0; sg < segs.size(); ++sg) {
-          const int32_t k0 = segs[sg].first, k1 = segs[sg].second;
           for (int32_t q = 0; q < ntl; q += 2) {
             if (!pair_on[(size_t)(q / 2)]) continue;
+            int32_t k0 = segs[sg].first, k1 = segs[sg].second;
+            dense_prod_all += k1 - k0;
+            trim(q, k0, k1);
+            dense_prod_kept += k1 - k0;
+            dense_items_empty += k1 <= k0 ? 1 : 0;
             const int32_t nt2 = std::min<int32_t>(2, ntl - q);
             DenseWork wk{dj, q, nt2, k0, k1, base[(size_t)q] < 0 ? -1 : base[(size_t)q] + (int32_t)sg,
                          (nt2 == 2 && base[(size_t)q + 1] >= 0) ? base[(size_t)q + 1] + (int32_t)sg : -1, 0};
@@ -1536,6 +1568,9 @@ struct WorkCut {
       if (pb.verbose && dense_pairs_all > 0)
         fprintf(stderr, "[scilmm plan] dense tail: %lld of %lld (target, descendant) panel pairs carry true entries, %lld of %lld target tile pairs are reached by a descendant (the others are padding only and skipped)\n",
                 (long long)dense_pairs_kept, (long long)dense_pairs_all, (long long)dense_tiles_kept, (long long)dense_tiles_all);
+      if (pb.verbose && dense_prod_all > 0)
+        fprintf(stderr, "[scilmm plan] dense tail: per-pair reach keeps %lld of %lld (tile pair, descendant) products, %lld empty items (zero slabs)\n",
+                (long long)dense_prod_kept, (long long)dense_prod_all, (long long)dense_items_empty);
       if (pb.verbose)
         fprintf(stderr, "[scilmm plan] dense tail: fronts %d..%d (%d wide), %lld early + %lld late implicit items (k_dense_b)\n",
                 S.dense_first, S.nsuper - 1, tail_w,

@@ -4,10 +4,14 @@
 // operands (zeros read HIGH: zero MFMA operands raise the clock) and checks that both kernels write the same bits.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DSCILMM_DENSE_B_SG=0] [-DSCILMM_DENSE_B_X4=1] dense_bench2.hip -o dense_bench2
 //   ./dense_bench2 [T] [j] [panels per item]
+// k_dense_b's three chunk-boundary forms (FEED 0 / 1 / 2, see the kernel) are timed side by side and must write the same bits.
+// With -DSCILMM_DENSE_CLK the kernel stamps wave 0 of every workgroup: the share of the chunk loop's time spent between
+// reaching a chunk boundary's wait and leaving its barrier is printed per form.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <cstring>
 #include <vector>
 #include "retired_kernels.hip.h"
 using namespace scilmm;
@@ -62,7 +66,9 @@ int main(int argc, char** argv) {
   double* scratch;
   CK(hipMalloc(&scratch, sizeof(double) * (size_t)slot * TM * NB));
   CK(hipFuncSetAttribute((const void*)k_dense_a, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  CK(hipFuncSetAttribute((const void*)k_dense_b, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  CK(hipFuncSetAttribute((const void*)k_dense_b<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  CK(hipFuncSetAttribute((const void*)k_dense_b<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  CK(hipFuncSetAttribute((const void*)k_dense_b<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   CK(hipFuncSetAttribute((const void*)k_dense_f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   CK(hipFuncSetAttribute((const void*)k_dense32, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   // tile-major fp32 shadow (k_dense_t): per panel ceil-blocks of 128 tail rows x w columns
@@ -98,12 +104,18 @@ int main(int argc, char** argv) {
          work.size(), per, flops / 1e12, SCILMM_DENSE_B_SG, 0);
   const size_t smb = sizeof(double) * 2 * KBA * LDB;
   for (int fill : {0, 1})
-  for (int which : {1, 8, 3, 7}) {
+  for (int which : {1, 9, 10, 1, 10, 8, 3, 7}) {
     hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, L, nL, fill);
     for (int rep = 0; rep < 4; ++rep) {
+#ifdef SCILMM_DENSE_CLK
+      unsigned long long clk0[2] = {0, 0};
+      CK(hipMemcpyToSymbol(HIP_SYMBOL(g_dense_clk), clk0, sizeof(clk0)));
+#endif
       hipEventRecord(e0);
       if (which == 0) hipLaunchKernelGGL(k_dense_a, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
-      else if (which == 1) hipLaunchKernelGGL(k_dense_b, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
+      else if (which == 1) hipLaunchKernelGGL(k_dense_b<0>, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
+      else if (which == 9) hipLaunchKernelGGL(k_dense_b<1>, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
+      else if (which == 10) hipLaunchKernelGGL(k_dense_b<2>, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
       else if (which == 2) hipLaunchKernelGGL(k_dense_f, dim3((unsigned)work.size()), dim3(512), dense_f_lds, 0, S, 0, d_work, L, scratch, (const double*)zeros);
       else if (which == 8) hipLaunchKernelGGL(k_dense_q, dim3(2 * (unsigned)work.size()), dim3(512), dense_q_lds, 0, S, 0, d_work, L, scratch, (const double*)zeros);
       else if (which == 7) {
@@ -134,7 +146,14 @@ int main(int argc, char** argv) {
       float ms;
       hipEventElapsedTime(&ms, e0, e1);
       CK(hipGetLastError());
-      if (rep) printf("%s, %s operands: %.3f ms -> %.2f TFLOP/s\n", which == 0 ? "k_dense_a" : which == 1 ? "k_dense_b" : which == 2 ? "k_dense_f (fp32 products)" : which == 4 ? "k_dense_s (fp32 shadow operands)" : which == 5 ? "k_dense_t (tile-major fp32 shadow)" : which == 6 ? "k_dense_w (one wave per SIMD, fp32 shadow)" : which == 7 ? "k_dense_h (32 x 64 wave tiles, fp32 shadow)" : which == 8 ? "k_dense_q (fp64, 32 x 64 wave tiles, two workgroups per CU)" : "k_dense32 (round 2)", fill ? "random" : "zero", ms, flops / ms / 1e9);
+#ifdef SCILMM_DENSE_CLK
+      if (rep == 3 && (which == 1 || which == 9 || which == 10)) {
+        unsigned long long clk[2];
+        CK(hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_dense_clk), sizeof(clk)));
+        printf("  wave 0 of %zu workgroups: %.1f %% of the chunk loop between a boundary's wait and the end of its barrier\n", work.size(), 100.0 * (double)clk[1] / (double)clk[0]);
+      }
+#endif
+      if (rep) printf("%s, %s operands: %.3f ms -> %.2f TFLOP/s\n", which == 0 ? "k_dense_a" : which == 1 ? "k_dense_b<0> (vmcnt(0) at the boundary)" : which == 9 ? "k_dense_b<1> (counted wait)" : which == 10 ? "k_dense_b<2> (asm A loads, hand-counted waits, descriptors ahead)" : which == 2 ? "k_dense_f (fp32 products)" : which == 4 ? "k_dense_s (fp32 shadow operands)" : which == 5 ? "k_dense_t (tile-major fp32 shadow)" : which == 6 ? "k_dense_w (one wave per SIMD, fp32 shadow)" : which == 7 ? "k_dense_h (32 x 64 wave tiles, fp32 shadow)" : which == 8 ? "k_dense_q (fp64, 32 x 64 wave tiles, two workgroups per CU)" : "k_dense32 (round 2)", fill ? "random" : "zero", ms, flops / ms / 1e9);
     }
   }
   {
@@ -154,11 +173,22 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_dense_a, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
     CK(hipMemcpy(r0.data(), scratch, sizeof(double) * ns, hipMemcpyDeviceToHost));
     CK(hipMemset(scratch, 0, sizeof(double) * ns));
-    hipLaunchKernelGGL(k_dense_b, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
+    hipLaunchKernelGGL(k_dense_b<0>, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
     CK(hipMemcpy(r1.data(), scratch, sizeof(double) * ns, hipMemcpyDeviceToHost));
     double mx = 0, ref = 0;
     for (size_t i = 0; i < ns; ++i) if (live[i]) { mx = std::max(mx, std::fabs(r0[i] - r1[i])); ref = std::max(ref, std::fabs(r0[i])); }
-    printf("k_dense_b vs k_dense_a: max |difference| of the slabs %.3g (largest entry %.3g)\n", mx, ref);
+    printf("k_dense_b<0> vs k_dense_a: max |difference| of the slabs %.3g (largest entry %.3g)\n", mx, ref);
+    for (int feed : {1, 2}) {
+      std::vector<double> r2(ns);
+      CK(hipMemset(scratch, 0, sizeof(double) * ns));
+      if (feed == 1) hipLaunchKernelGGL(k_dense_b<1>, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
+      else hipLaunchKernelGGL(k_dense_b<2>, dim3((unsigned)work.size()), dim3(512), smb, 0, S, 0, d_work, L, scratch, (const double*)zeros);
+      CK(hipMemcpy(r2.data(), scratch, sizeof(double) * ns, hipMemcpyDeviceToHost));
+      double m2 = 0;
+      size_t nbits = 0;
+      for (size_t i = 0; i < ns; ++i) if (live[i]) { m2 = std::max(m2, std::fabs(r2[i] - r1[i])); nbits += memcmp(&r2[i], &r1[i], 8) != 0; }
+      printf("k_dense_b<%d> vs k_dense_b<0>: max |difference| of the slabs %.3g, %zu entries with other bits\n", feed, m2, nbits);
+    }
     for (int v = 0; v < 7; ++v) {
       CK(hipMemset(scratch, 0, sizeof(double) * ns));
       if (v == 6) {

@@ -4,6 +4,12 @@
 //   k_dense_a       -> k_dense_b   (A from registers, B by LDS-DMA, without the in-wave software pipeline of round 3)
 //   k_dense_f / _s / _t (+ k_shadow_t) / _w   the forms that located what bounds the fp32-product fronts (-> k_dense_h)
 //   k_dense_q                      k_dense_h's 32 x 64 wave tiling for the fp64 kernel (63.6 vs k_dense_b's 68.0)
+// Retired inside k_dense_b itself (template forms the library does not instantiate; dense_bench2 times them):
+//   k_dense_b<1>                   the counted wait vmcnt(8) at the chunk boundary with compiler-known A loads: 68.3 against 68.1
+//                                  TFLOP/s on the 1M-shaped launch, inside the run-to-run spread (67.9 - 68.3) -- the compiler's
+//                                  full wait behind the LDS-DMA copies remains; k_dense_b<2>, which has no such wait: 69.1.
+//   (a third set of A fragments, two sub-chunks ahead, was tried in csrc/tools/mfma_f64_feed only: it spills there -- 180 bytes of
+//    scratch at 256 registers -- and runs at 61.6 against 72.5 TFLOP/s; with hand-counted waits a fragment already has four k-steps.)
 // Pruned in round 4 (their numbers stay in DESIGN.md section 4.2, their code in the history before commit "prune the harness"):
 // k_update, k_update3, k_dense<>, k_dense_g, k_update_compact, k_trsm4 and the round-2 harness dense_bench.hip.
 // Include AFTER ../kernels.hip.h.
