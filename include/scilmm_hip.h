@@ -458,6 +458,71 @@ int scilmm_sets_finish_dev(scilmm_factor* fac, int32_t r, int32_t q, const doubl
  * it: ms[0] k_sets_finish (tools/sets_timing.py --finish).  No counterpart in the reference. */
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms);
 
+/* scilmm_sets_finish_dev with a variance scale per column of the block: in A alone a column's weight is multiplied by its
+ * scale, A = diag(w o scale) K diag(w o scale), while t = w o s keeps w; everything else -- arguments, checks, refusals, the
+ * layout of a row -- is scilmm_sets_finish_dev's (burden_chi2 = (1't)^2 / 1'A1 is then a chi-square with ONE degree of freedom
+ * under the rescaled covariance: burden_p = chi2_1's tail, the caller's).
+ *   d_vscale: r doubles on the device, what scilmm_sets_spa*_dev wrote; null is SCILMM_ERR_ARG.
+ * flags: bit 4 (16) is set where a kept column's scale is not 1.  With every scale 1.0 the rows are the bits of
+ * scilmm_sets_finish_dev (w * 1.0 = w).  scilmm_sets_finish_timing reports either.  scilmm_amd.glmm.BinarySetTest with
+ * finish="device" is the interface.  No counterpart in the reference. */
+int scilmm_sets_finish_scaled_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram,
+                                  const double* d_R, const double* d_u, int32_t c, int32_t n_sets, const int32_t* set_start,
+                                  int32_t weight_mode, const double* d_weights, int32_t method, const double* rho, int32_t n_rho,
+                                  double* d_out, int64_t ld_out, double* d_lam, const double* d_vscale);
+
+/* Binary traits, variant sets (SAIGE-GENE / SMMAT with the exact K): per set of a Gram block the
+ * saddlepoint-implied variance scale of every marker and the saddlepoint p-value of the burden -- the collapsed genotype
+ * g_B = sum_j w_j g~_j -- queued BEHIND the block's Gram entry point and the scilmm_scan_spa*_dev of the same markers, on the
+ * handle's stream; scilmm_sets_finish_scaled_dev follows it.
+ *   the form's marker arguments, r, d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff: as for the scilmm_scan_spa*_dev twin.
+ *   d_gram  : the block's r x r Gram matrix; entry (i, j) is the mean of [i][j] and [j][i], as the finish reads it.
+ *   d_spa   : INPUT, the block's 7 x r rows of scilmm_scan_spa*_dev.
+ *   n_sets, set_start, weight_mode, d_weights: as for scilmm_sets_finish_dev (set_start is a HOST array, read before the
+ *             call returns).
+ *   d_bspa  : n_sets rows of 13 doubles:  log_p_B | a_w | s_B | zeta_hi | zeta_lo | iters | flag | a_B | b_B | v~_B | V_Q | phi |
+ *             n_adj.  Exactly 13 doubles per set are written.
+ *   d_vscale: r doubles; the columns of a set receive rho_j sqrt(phi) (kept markers) or 1.0 (dropped ones); columns outside
+ *             every set are not written.
+ * With the kept markers, s, K = G - z'z and w as in scilmm_sets_finish_dev, a_j = K_jj and zs_j = s_j / sqrt(a_j):
+ *   rho_j   : where the marker's saddlepoint row has flag 1 and log_p_j < 0, v_j >= 0 solves log erfc(v / sqrt 2) = log_p_j (in
+ *             logarithms: finite far beyond where p underflows), x_j = v_j^2 and rho_j^2 = zs_j^2 / x_j; rho_j = 1 exactly where
+ *             the flag is 0 or 2, log_p_j is NaN or >= 0, x_j is not finite and positive, or a_j is not > 0.
+ *   a_B = w'Kw, b_B = w's, V_Q = (w o rho)'K(w o rho): fixed-order sums over the pairs (i, j).
+ *   Where a_B > 0 and |b_B| / sqrt(a_B) > cutoff, g_B goes through the steps of scilmm_scan_spa_dev with (a, b) = (a_B, b_B):
+ *             log_p_B, a_w, s_B, the roots, iters and flag (0 / 1 / 2) are that call's seven numbers for g_B.  flag 0: the six
+ *             numbers before it are NaN.
+ *   v~_B = b_B^2 / x_B with x_B from log_p_B as x_j from log_p_j, where flag is 1 and x_B is valid; NaN otherwise.
+ *   phi = v~_B / V_Q where v~_B exists, v~_B > V_Q and V_Q > 0, else 1: the burden only ever inflates the covariance.
+ *   n_adj   : the kept markers with rho_j != 1.
+ * A set with nothing kept: flag 0, n_adj 0, the other eleven numbers NaN.  One workgroup per set, 256 threads, fixed strides and
+ * fixed reduction trees, no atomics: a set's numbers depend on its own inputs alone -- not on its place in the block, its
+ * neighbours or the mode of the handle -- the three input forms of the same hard calls give the same bits, and
+ * scilmm_timing.n_float_atomic_launches is not touched.  g^_B is kept in row `set` of the scratch of scilmm_scan_spa_dev
+ * (allocated by the first saddlepoint call of either kind on the handle, never again).  Enqueued without synchronising.
+ * SCILMM_ERR_ARG before anything is dereferenced: what scilmm_scan_spa*_dev rejects, a null d_gram, d_bspa, d_vscale or
+ * set_start, n_sets outside 1 .. r, offsets that do not start at 0, do not rise strictly or end beyond r, an unknown weight
+ * mode, mode 2 without d_weights.  Refusals as for the scan blocks (SCILMM_ERR_STATE, the handle left usable).
+ * scilmm_amd.glmm.BinarySetTest is the interface.  No counterpart in the reference. */
+int scilmm_sets_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_gram,
+                        const double* d_R, const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv,
+                        double cutoff, const double* d_spa, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                        const double* d_weights, double* d_bspa, double* d_vscale);
+int scilmm_sets_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                            int32_t flags, int32_t r, const double* d_stats, const double* d_gram, const double* d_R, const double* d_u,
+                            const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff, const double* d_spa,
+                            int32_t n_sets, const int32_t* set_start, int32_t weight_mode, const double* d_weights, double* d_bspa,
+                            double* d_vscale);
+int scilmm_sets_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                               const int32_t* d_sample, int32_t r, const double* d_stats, const double* d_gram, const double* d_R,
+                               const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff,
+                               const double* d_spa, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                               const double* d_weights, double* d_bspa, double* d_vscale);
+
+/* HIP-event time of the last scilmm_sets_spa*_dev on the handle, in milliseconds, valid after the scilmm_sync that follows it:
+ * ms[0] k_sets_spa (tools/sets_timing.py --binary).  No counterpart in the reference. */
+int scilmm_sets_spa_timing(const scilmm_symbolic* sym, double* ms);
+
 /* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
  * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y
  * (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1) per column by the scan's algebra: predicted value, prediction error variance

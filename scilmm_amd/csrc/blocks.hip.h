@@ -223,10 +223,17 @@ struct SpaArgs {
   }
 };
 
+// The scratch of g^ rows both saddlepoint kernels write (RPMAX x n doubles): allocated by the first call on the handle after a
+// stream synchronise, never again.
+int spa_scratch(scilmm_symbolic* sym, Dev* D) {
+  const size_t need = (size_t)RPMAX * (size_t)std::max(sym->S->n, 1);
+  if (D->spa_scratch_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  return grow(sym, &D->spa_scratch, &D->spa_scratch_cap, need);
+}
+
 // The saddlepoint p-values of the r markers of the plain block queued before this call (scilmm_scan_spa*_dev): the refusals of
-// the half-solves, the scratch of g^ rows (RPMAX x n doubles, allocated by the first call on the handle after a stream
-// synchronise, never again), k_scan_spa between the call's own events.  Nothing of the work buffers is touched: the block stays
-// available to scilmm_scan_panel_dev.
+// the half-solves, the scratch of g^ rows (spa_scratch), k_scan_spa between the call's own events.  Nothing of the work buffers
+// is touched: the block stays available to scilmm_scan_panel_dev.
 template <class Reader>
 int scan_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const SpaArgs& a) {
   scilmm_symbolic* sym = fac->sym;
@@ -235,9 +242,7 @@ int scan_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const Sp
   TRY(settle(fac, who));
   Dev* D = (Dev*)sym->device;
   const int32_t n = sym->S->n;
-  const size_t need = (size_t)RPMAX * (size_t)std::max(n, 1);
-  if (D->spa_scratch_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-  TRY(grow(sym, &D->spa_scratch, &D->spa_scratch_cap, need));
+  TRY(spa_scratch(sym, D));
   if (!D->spa_ev[0])
     for (auto& e : D->spa_ev) HIPCHK(hipEventCreate(&e));
   hipStream_t s0 = D->stream;
@@ -264,28 +269,34 @@ struct FinishArgs {
   double* d_out;
   int64_t ld_out;
   double* d_lam;
+  const double* d_vscale = nullptr;   // the columns' variance scales (scilmm_sets_finish_scaled_dev), or null: all 1
+  // what the set SPA entry points check as well: the offsets (a HOST array, read here) and the weights
+  static bool sets_ok(int32_t r, int32_t n_sets, const int32_t* set_start, int32_t weight_mode, const double* d_weights) {
+    if (!set_start || n_sets < 1 || n_sets > r || (weight_mode != FIN_BETA && weight_mode != FIN_ONES && weight_mode != FIN_GIVEN) ||
+        (weight_mode == FIN_GIVEN && !d_weights))
+      return false;
+    if (set_start[0] != 0 || set_start[n_sets] > r) return false;
+    for (int32_t i = 0; i < n_sets; ++i)
+      if (set_start[i + 1] <= set_start[i]) return false;
+    return true;
+  }
   // before anything of the handle is read; the offsets and the grid are HOST arrays and are read here (a NaN fails its comparison)
   static bool args_ok(const scilmm_factor* fac, const FinishArgs& a) {
-    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.set_start || !a.d_out || a.r < 1 || a.r > RPMAX || a.c < 1 ||
-        a.c > FIN_CMAX || a.q != a.c + 1 || a.n_sets < 1 || a.n_sets > a.r || a.n_rho < 0 || a.n_rho > FIN_RHO_MAX ||
-        (a.n_rho > 0 && !a.rho) || a.ld_out < FIN_HEAD + a.n_rho ||
-        (a.weight_mode != FIN_BETA && a.weight_mode != FIN_ONES && a.weight_mode != FIN_GIVEN) ||
-        (a.weight_mode == FIN_GIVEN && !a.d_weights) || (a.method != FIN_SADDLE && a.method != FIN_LIU))
+    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.d_out || a.r < 1 || a.r > RPMAX || a.c < 1 || a.c > FIN_CMAX ||
+        a.q != a.c + 1 || a.n_rho < 0 || a.n_rho > FIN_RHO_MAX || (a.n_rho > 0 && !a.rho) || a.ld_out < FIN_HEAD + a.n_rho ||
+        (a.method != FIN_SADDLE && a.method != FIN_LIU))
       return false;
     for (int32_t j = 0; j < a.n_rho; ++j)
       if (!(a.rho[j] >= 0.0 && a.rho[j] <= 1.0)) return false;
-    if (a.set_start[0] != 0 || a.set_start[a.n_sets] > a.r) return false;
-    for (int32_t i = 0; i < a.n_sets; ++i)
-      if (a.set_start[i + 1] <= a.set_start[i]) return false;
+    if (!sets_ok(a.r, a.n_sets, a.set_start, a.weight_mode, a.d_weights)) return false;
     return fac->sym && fac->sym->S;  // (what needs no handle has been checked: with it wrong, nothing of the handle is read)
   }
 };
 
-// Everything after a Gram block, for the sets of the block (scilmm_sets_finish_dev): the refusals of the scan blocks, then
-// k_sets_finish between the call's own events, one workgroup per set, its LDS sized by the block's largest set.  Nothing of the
-// factor is read and nothing of the work buffers is touched; nothing is allocated.
-int sets_finish(scilmm_factor* fac, const FinishArgs& a) {
-  const char* who = "scilmm_sets_finish_dev";
+// Everything after a Gram block, for the sets of the block (scilmm_sets_finish_dev, scilmm_sets_finish_scaled_dev): the
+// refusals of the scan blocks, then k_sets_finish between the call's own events, one workgroup per set, its LDS sized by the
+// block's largest set.  Nothing of the factor is read and nothing of the work buffers is touched; nothing is allocated.
+int sets_finish(scilmm_factor* fac, const FinishArgs& a, const char* who) {
   scilmm_symbolic* sym = fac->sym;
   const DevGuard guard(sym);
   TRY(check_half(fac, who));
@@ -306,9 +317,53 @@ int sets_finish(scilmm_factor* fac, const FinishArgs& a) {
   hipStream_t s0 = D->stream;
   HIPCHK(hipEventRecord(D->fin_ev[0], s0));
   hipLaunchKernelGGL(k_sets_finish, dim3((unsigned)a.n_sets), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, a.d_u, sets,
-                     a.weight_mode, a.d_weights, a.method, a.n_rho, cap, a.d_out, a.ld_out, a.d_lam);
+                     a.weight_mode, a.d_weights, a.method, a.n_rho, cap, a.d_out, a.ld_out, a.d_lam, a.d_vscale);
   HIPCHK(hipEventRecord(D->fin_ev[1], s0));
   D->fin_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
+// What the three set SPA entry points take beside their form's marker arguments and the common part of the marker calls
+// (scilmm_sets_spa*_dev): the Gram matrix, the markers' saddlepoint rows, the sets and the two outputs.
+struct SetSpaArgs {
+  SpaArgs spa;                 // d_spa: the block's SPA_ROWS x r rows, an INPUT here
+  const double* d_gram;
+  int32_t n_sets;
+  const int32_t* set_start;
+  int32_t weight_mode;
+  const double* d_weights;
+  double *d_bspa, *d_vscale;
+  // before anything of the handle is read
+  static bool args_ok(const scilmm_factor* fac, int32_t r, const SetSpaArgs& a) {
+    return a.d_gram && a.d_bspa && a.d_vscale && FinishArgs::sets_ok(r, a.n_sets, a.set_start, a.weight_mode, a.d_weights) &&
+           SpaArgs::args_ok(fac, r, a.spa);   // (the handle is looked at last)
+  }
+};
+
+// The variance scales and the burden's saddlepoint p-value of the sets of the Gram block queued before this call, behind the
+// saddlepoint call of its markers (scilmm_sets_spa*_dev): the refusals of the scan blocks, the scratch of scan_spa (row `set` is
+// the set's), k_sets_spa between the call's own events, one workgroup per set.  Nothing of the work buffers is touched.
+template <class Reader>
+int sets_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const SetSpaArgs& a) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const int32_t n = sym->S->n;
+  TRY(spa_scratch(sym, D));
+  SpaSets sets{};
+  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
+  if (!D->sspa_ev[0])
+    for (auto& e : D->sspa_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->sspa_ev[0], s0));
+  hipLaunchKernelGGL(k_sets_spa<Reader>, dim3((unsigned)a.n_sets), dim3(256), 0, s0, n, r, a.spa.c, rd, a.spa.d_stats, a.d_gram, a.spa.d_R,
+                     a.spa.d_u, a.spa.d_mu, a.spa.d_C, a.spa.d_Minv, a.spa.cutoff, (const double*)a.spa.d_spa, sets, a.weight_mode,
+                     a.d_weights, D->spa_scratch, a.d_bspa, a.d_vscale);
+  HIPCHK(hipEventRecord(D->sspa_ev[1], s0));
+  D->sspa_pending = true;
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }

@@ -342,6 +342,9 @@ struct Dev {
   hipEvent_t fin_ev[2] = {nullptr, nullptr};  // k_sets_finish begin | done (the first finish call creates them)
   bool fin_pending = false;             // a finish call whose events have not been read yet (scilmm_sync)
   double fin_ms = 0.0;                  // the last call's k_sets_finish (scilmm_sets_finish_timing)
+  hipEvent_t sspa_ev[2] = {nullptr, nullptr};  // k_sets_spa begin | done (the first set SPA call creates them)
+  bool sspa_pending = false;            // a set SPA call whose events have not been read yet (scilmm_sync)
+  double sspa_ms = 0.0;                 // the last call's k_sets_spa (scilmm_sets_spa_timing)
   void clear_block() { block_r = block_rp = 0; }
 };
 

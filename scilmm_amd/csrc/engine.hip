@@ -1,9 +1,9 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setfinish.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setfinish.hip.h, setspa.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_spa, rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
@@ -37,6 +37,7 @@
 #include "dosage.hip.h"
 #include "spa.hip.h"
 #include "setfinish.hip.h"
+#include "setspa.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
@@ -354,7 +355,58 @@ int scilmm_sets_finish_dev(scilmm_factor* fac, int32_t r, int32_t q, const doubl
                            double* d_lam) {
   const FinishArgs a{r, q, d_stats, d_gram, d_R, d_u, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_out, ld_out, d_lam};
   if (!FinishArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
-  return sets_finish(fac, a);
+  return sets_finish(fac, a, __func__);
+}
+
+// ... with the variance scales of the block's columns (scilmm_sets_spa*_dev) in the weights of A
+int scilmm_sets_finish_scaled_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram,
+                                  const double* d_R, const double* d_u, int32_t c, int32_t n_sets, const int32_t* set_start,
+                                  int32_t weight_mode, const double* d_weights, int32_t method, const double* rho, int32_t n_rho,
+                                  double* d_out, int64_t ld_out, double* d_lam, const double* d_vscale) {
+  const FinishArgs a{r, q, d_stats, d_gram, d_R, d_u, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_out, ld_out, d_lam,
+                     d_vscale};
+  if (!d_vscale || !FinishArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_finish(fac, a, __func__);
+}
+
+// The sets' variance scales and burden saddlepoint p-values behind a Gram block and its markers' saddlepoint call: the form's
+// marker arguments are checked as its scan_spa twin checks them
+int scilmm_sets_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_gram,
+                        const double* d_R, const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv,
+                        double cutoff, const double* d_spa, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                        const double* d_weights, double* d_bspa, double* d_vscale) {
+  const SetSpaArgs a{{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, const_cast<double*>(d_spa)}, d_gram, n_sets, set_start, weight_mode,
+                     d_weights, d_bspa, d_vscale};
+  if (!d_geno || !SetSpaArgs::args_ok(fac, r, a) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
+  return sets_spa(fac, __func__, r, SpaInt8{d_geno, ld_geno}, a);
+}
+
+int scilmm_sets_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                            int32_t flags, int32_t r, const double* d_stats, const double* d_gram, const double* d_R, const double* d_u,
+                            const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff, const double* d_spa,
+                            int32_t n_sets, const int32_t* set_start, int32_t weight_mode, const double* d_weights, double* d_bspa,
+                            double* d_vscale) {
+  const SetSpaArgs a{{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, const_cast<double*>(d_spa)}, d_gram, n_sets, set_start, weight_mode,
+                     d_weights, d_bspa, d_vscale};
+  if (!d_bed || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) || !SetSpaArgs::args_ok(fac, r, a) ||
+      (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return sets_spa(fac, __func__, r, SpaBed{d_bed, ld_bed, n_samples, d_sample, flags}, a);
+}
+
+int scilmm_sets_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                               const int32_t* d_sample, int32_t r, const double* d_stats, const double* d_gram, const double* d_R,
+                               const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff,
+                               const double* d_spa, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                               const double* d_weights, double* d_bspa, double* d_vscale) {
+  const SetSpaArgs a{{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, const_cast<double*>(d_spa)}, d_gram, n_sets, set_start, weight_mode,
+                     d_weights, d_bspa, d_vscale};
+  if (!d_dos || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
+      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
+      !SetSpaArgs::args_ok(fac, r, a) || (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return dtype == SCILMM_DOSAGE_U16 ? sets_spa(fac, __func__, r, SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}, a)
+                                    : sets_spa(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
 }
 
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
@@ -569,6 +621,12 @@ int scilmm_sync(scilmm_symbolic* sym) {
     HIPCHK(hipEventElapsedTime(&a, D->fin_ev[0], D->fin_ev[1]));
     D->fin_ms = a;
   }
+  if (D->sspa_pending) {
+    D->sspa_pending = false;
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->sspa_ev[0], D->sspa_ev[1]));
+    D->sspa_ms = a;
+  }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
 }
@@ -619,6 +677,12 @@ int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms) {
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   ms[0] = ((const Dev*)sym->device)->fin_ms;
+  return SCILMM_OK;
+}
+
+int scilmm_sets_spa_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  ms[0] = ((const Dev*)sym->device)->sspa_ms;
   return SCILMM_OK;
 }
 

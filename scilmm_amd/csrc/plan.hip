@@ -40,6 +40,8 @@ void dev_free(void* p) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->fin_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->sspa_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->gxe_ev)

@@ -6,7 +6,8 @@
 // The steps, each between barriers that every thread reaches (every branch around a barrier is on a value all threads read from LDS):
 //   0. the markers with an observed value and with variation are kept (k of the set's m);
 //   1. z = R^-T w(C)'x by forward substitution (a thread per marker), s = w(y)'x - u'z, the weights, t = w o s;
-//   2. A = diag(w) (G_SS - z'z) diag(w) (every thread forms its entries in registers, then the image of z is overwritten);
+//   2. A = diag(w) (G_SS - z'z) diag(w) (every thread forms its entries in registers, then the image of z is overwritten); with
+//      variance scales (scilmm_sets_finish_scaled_dev) diag(w o scale) takes the place of diag(w), in A alone;
 //   3. the burden numbers and Q = t't;
 //   4. A = U Lambda U' by the two-sided Jacobi iteration, disjoint pairs in round-robin order, with c = U'1 carried through the
 //      rotations; Lambda sorted in descending order;
@@ -43,8 +44,9 @@ constexpr double FIN_Z_END = 40.0;     // the integral stops here
 enum { FIN_BETA = 0, FIN_ONES = 1, FIN_GIVEN = 2 };         // weight modes
 enum { FIN_SADDLE = 0, FIN_LIU = 1 };                       // tail methods
 // the flag word: bit 0 the degenerate rule answered (p = T); bit 1 the Jacobi iteration ran out of sweeps; bit 2 a root
-// (secular equation, saddlepoint, quantile) ran out of steps; bit 3 SKAT-O was asked for and computed
-enum { FIN_F_DEGENERATE = 1, FIN_F_SWEEPS = 2, FIN_F_ROOT = 4, FIN_F_SKATO = 8 };
+// (secular equation, saddlepoint, quantile) ran out of steps; bit 3 SKAT-O was asked for and computed; bit 4 a kept column's
+// variance scale is not 1 (scilmm_sets_finish_scaled_dev)
+enum { FIN_F_DEGENERATE = 1, FIN_F_SWEEPS = 2, FIN_F_ROOT = 4, FIN_F_SKATO = 8, FIN_F_SCALED = 16 };
 
 struct FinSets {
   int32_t start[RPMAX + 1];     // offsets of the sets into the block's columns
@@ -264,6 +266,16 @@ __device__ __forceinline__ double fin_fold(double v, double* red) {
   return out;
 }
 
+// a marker's weight by the mode: the Beta(1, 25) density at its minor allele frequency (half its mean), 1, or the caller's
+__device__ __forceinline__ double fin_weight(int32_t wmode, double mean, const double* __restrict__ weights, int col) {
+  if (wmode == FIN_BETA) {
+    const double maf = fmin(0.5 * mean, 1.0 - 0.5 * mean), x = 1.0 - maf;
+    const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
+    return 25.0 * (x8 * x8 * x8);                            // 25 (1 - maf)^24
+  }
+  return wmode == FIN_GIVEN ? weights[col] : 1.0;
+}
+
 // doubles of dynamic LDS for a block whose largest set has `cap` markers (cap even, >= 2): the matrix image (or the image of z, or
 // the secular work space: three rows of cap per task), nine vectors, the fold, the pairs' rotations, the per-rho numbers and the
 // break points, the kept markers' columns and the pairs' indices (int32, two to a double)
@@ -276,14 +288,14 @@ __host__ __device__ constexpr int fin_lds_doubles(int cap, int nt) {
 }
 
 // stats: the block's (q + 4) x r statistics, q = c + 1; gram: r x r; R: c x c upper; u: c; sets: the offsets and the grid, by
-// value; out: n_sets rows of ld_out >= FIN_HEAD + n_rho doubles; lam_out: r doubles or null.  cap: the largest set, rounded up
-// to an even number.
+// value; out: n_sets rows of ld_out >= FIN_HEAD + n_rho doubles; lam_out: r doubles or null; vscale: r variance scales of the
+// columns or null (all 1).  cap: the largest set, rounded up to an even number.
 __global__ __launch_bounds__(FIN_NT_MAX) void k_sets_finish(int32_t r, int32_t c, const double* __restrict__ stats,
                                                             const double* __restrict__ gram, const double* __restrict__ R,
                                                             const double* __restrict__ u, FinSets sets, int32_t wmode,
                                                             const double* __restrict__ weights, int32_t method, int32_t n_rho,
                                                             int32_t cap, double* __restrict__ out, int64_t ld_out,
-                                                            double* __restrict__ lam_out) {
+                                                            double* __restrict__ lam_out, const double* __restrict__ vscale) {
   extern __shared__ double fin_lds[];
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
   const int set = blockIdx.x;
@@ -292,8 +304,8 @@ __global__ __launch_bounds__(FIN_NT_MAX) void k_sets_finish(int32_t r, int32_t c
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
 
   double* M = fin_lds;                         // the matrix, ld = cap + 1 (odd: a column is read without bank conflicts)
-  double* sv = M + fin_image(cap);             // s | w | t | lambda (sorted) | c = U'1 (sorted) | c (unsorted) | lambda above the floor | 2 spare
-  double *wv_ = sv + cap, *tv = wv_ + cap, *lam = tv + cap, *cs = lam + cap, *cu = cs + cap, *lamf = cu + cap;
+  double* sv = M + fin_image(cap);             // s | w | t | lambda (sorted) | c = U'1 (sorted) | c (unsorted) | lambda above the floor | w o scale | 1 spare
+  double *wv_ = sv + cap, *tv = wv_ + cap, *lam = tv + cap, *cs = lam + cap, *cu = cs + cap, *lamf = cu + cap, *wa = lamf + cap;
   double* red = sv + 9 * cap;                  // nt
   double* rot = red + nt;                      // cos | sin of the pairs of a step (cap / 2 each)
   double* prho = rot + cap;                    // p_rho | Q_rho | c1 | sd | l | alpha | beta | spare (FIN_RHO_MAX each)
@@ -314,13 +326,16 @@ __global__ __launch_bounds__(FIN_NT_MAX) void k_sets_finish(int32_t r, int32_t c
 
   // 0. the kept markers
   if (tid == 0) {
-    int k = 0;
+    int k = 0, scaled = 0;
     for (int j = 0; j < m; ++j) {
       const double n_obs = stats[c0 + j], css = stats[2 * (int64_t)r + c0 + j];
-      if (!(n_obs == 0.0 || css == 0.0)) idx[k++] = c0 + j;
+      if (!(n_obs == 0.0 || css == 0.0)) {
+        idx[k++] = c0 + j;
+        if (vscale && vscale[c0 + j] != 1.0) scaled = FIN_F_SCALED;
+      }
     }
     ic[I_K] = k;
-    ic[I_FLAG] = 0;
+    ic[I_FLAG] = scaled;
     ic[I_ROOT] = 0;
     for (int j = 0; j < FIN_RHO_MAX + 2; ++j) fm[j] = 0.0;
   }
@@ -349,17 +364,10 @@ __global__ __launch_bounds__(FIN_NT_MAX) void k_sets_finish(int32_t r, int32_t c
       uz += u[a] * v;
     }
     const double s = stats[(int64_t)(4 + c) * r + col] - uz;
-    double w = 1.0;
-    if (wmode == FIN_BETA) {
-      const double mean = stats[(int64_t)r + col];
-      const double maf = fmin(0.5 * mean, 1.0 - 0.5 * mean), x = 1.0 - maf;
-      const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-      w = 25.0 * (x8 * x8 * x8);                             // the Beta(1, 25) density: 25 (1 - maf)^24
-    } else if (wmode == FIN_GIVEN) {
-      w = weights[col];
-    }
+    const double w = fin_weight(wmode, stats[(int64_t)r + col], weights, col);
     sv[tid] = s;
     wv_[tid] = w;
+    wa[tid] = vscale ? w * vscale[col] : w;                   // (the weight in A alone: t keeps w)
     tv[tid] = w * s;
     cu[tid] = 1.0;
   }
@@ -376,7 +384,7 @@ __global__ __launch_bounds__(FIN_NT_MAX) void k_sets_finish(int32_t r, int32_t c
       double zz = 0.0;
       for (int l = 0; l < c; ++l) zz = fma(M[l * cap + i], M[l * cap + j], zz);
       const double kij = 0.5 * (gram[(int64_t)idx[i] * r + idx[j]] + gram[(int64_t)idx[j] * r + idx[i]]) - zz;   // (the host's 0.5 (K + K'))
-      acc[e] = wv_[i] * kij * wv_[j];
+      acc[e] = wa[i] * kij * wa[j];
     }
   }
   __syncthreads();

@@ -4,6 +4,8 @@
 // section 18).
 //   k_scan_spa<Reader>     : one workgroup per marker, 256 threads with a fixed stride over n   reads  n (c + 2) * 8 + the
 //                            marker's row twice; then 16 B per individual and one fp64 exp per Newton pass, from its scratch row
+// Steps 1 - 3 (the covariate adjustment, a_w and s, the two roots) are the device function spa_roots, which k_sets_spa
+// (setspa.hip.h) runs on a set's collapsed genotype as well.
 // Every sum is taken thread by thread in ascending order of i and folded by a fixed tree (shuffles inside a wave, then the four
 // waves in wave order; the covariate sums of step 1 in lane groups added in group order); no atomics, no sum across workgroups:
 // a marker's bits depend on its inputs alone, in either mode of the handle.  The kernel is templated on a row READER, the only part that knows the input form: reader(c, i) = individual i's
@@ -110,56 +112,25 @@ struct SpaFold {
   }
 };
 
-// stats: the (q + 4) x r statistics of the plain block (q = c + 1): rows n_obs | mean | css | |x|^2 | w(C)'x (c rows) | w(y~)'x.
-// R: c x c upper triangular, R'R = w(C)'w(C); u: R^-T w(C)'w(y~); mu: n fitted probabilities; Cv: n x c covariates, row-major;
-// Minv: (C' W C)^-1, W = diag(mu (1 - mu)); gs: the handle's scratch, row `marker` of n doubles holds g^ = g~ - C (Minv C' W g~).
-// out: SPA_ROWS x r.  Every branch on a sum is uniform over the workgroup (all
-// threads hold the same folded bits), so the barriers inside the root loop are reached by all of them.
-template <class Reader>
-__global__ __launch_bounds__(256) void k_scan_spa(int32_t n, int32_t r, int32_t c, Reader rd, const double* __restrict__ stats,
-                                                  const double* __restrict__ R, const double* __restrict__ u,
-                                                  const double* __restrict__ mu, const double* __restrict__ Cv,
-                                                  const double* __restrict__ Minv, double cutoff, double* __restrict__ gs,
-                                                  double* __restrict__ out) {
-  __shared__ double red[4 * 3];
-  __shared__ double tred[256];
-  __shared__ double tt[SPA_CMAX + 1], gam[SPA_CMAX + 1], head[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int j = blockIdx.x;
-  const SpaFold fold{red, lane, wv};
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  auto put = [&](int row, double v) { out[(int64_t)row * r + j] = v; };
+// What steps 1 - 3 leave behind: the numbers of a result row behind log_p (which `spa_log_p` makes of them on one thread).
+struct SpaRoots {
+  double aw, s, zeta_hi, zeta_lo, ltail_hi, ltail_lo;
+  int iters;
+  bool good;
+};
 
-  // 0. a, b, zs from the block's statistics: R' z = w(C)'x by forward substitution (thread 0; c <= 31)
-  if (tid == 0) {
-    const double* S = stats + j;
-    double zz = 0.0, uz = 0.0;
-    for (int k = 0; k < c; ++k) {
-      double v = S[(int64_t)(4 + k) * r];
-      for (int l = 0; l < k; ++l) v -= R[l * c + k] * tt[l];
-      v /= R[k * c + k];
-      tt[k] = v;
-      zz += v * v;
-      uz += u[k] * v;
-    }
-    const double a = S[3 * (int64_t)r] - zz, b = S[(int64_t)(4 + c) * r] - uz;
-    head[0] = a;
-    head[1] = b;
-    head[2] = S[0];
-    head[3] = S[2 * (int64_t)r];
-  }
-  __syncthreads();
-  const double a = head[0], b = head[1];
-  const double zs = b / sqrt(a);
-  if (head[2] == 0.0 || head[3] == 0.0 || !(a > 0.0) || !(fabs(zs) > cutoff)) {
-    if (tid == 0) {
-#pragma unroll
-      for (int row = 0; row < SPA_ROWS - 1; ++row) put(row, nan);
-      put(SPA_ROWS - 1, 0.0);
-    }
-    return;  // (the whole workgroup)
-  }
-  const double mean = stats[(int64_t)r + j];
+// Steps 1 - 3 of the saddlepoint call for ONE centred row `row(i)` with score b and variance a (a marker's in k_scan_spa, a
+// set's collapsed genotype in k_sets_spa: setspa.hip.h), by the 256 threads of a workgroup; every thread returns the same bits.
+// mu: n fitted probabilities; Cv: n x c covariates, row-major; Minv: (C' W C)^-1, W = diag(mu (1 - mu)); g: a scratch row of n
+// doubles, g^ = g~ - C (Minv C' W g~) when the call returns; tred: 256 doubles, tt and gam: SPA_CMAX + 1 doubles each, in LDS.
+// Every branch on a sum is uniform over the workgroup (all threads hold the same folded bits), so the barriers inside the root
+// loop are reached by all of them.
+template <class Row>
+__device__ __forceinline__ SpaRoots spa_roots(int32_t n, int32_t c, Row row, double a, double b, const double* __restrict__ mu,
+                                              const double* __restrict__ Cv, const double* __restrict__ Minv, double* g,
+                                              double* tred, double* tt, double* gam, const SpaFold& fold) {
+  const int tid = threadIdx.x;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
 
   // 1. t_k = sum_i w_i C_ik g~_i, gamma = Minv t.  Lanes run along the covariates (a row of C is read once, contiguously): groups
   // of LG = 8, 16 or 32 lanes (the least that holds c), group g takes individuals g, g + 256 / LG, ... in ascending order, and
@@ -170,7 +141,7 @@ __global__ __launch_bounds__(256) void k_scan_spa(int32_t n, int32_t r, int32_t 
     double acc = 0.0;
     for (int64_t i = grp; i < n; i += ng) {
       const double m = mu[i];
-      const double wg = (m * (1.0 - m)) * rd(j, i, mean);
+      const double wg = (m * (1.0 - m)) * row(i);
       if (k < c) acc = fma(Cv[i * c + k], wg, acc);
     }
     tred[tid] = acc;
@@ -190,14 +161,13 @@ __global__ __launch_bounds__(256) void k_scan_spa(int32_t n, int32_t r, int32_t 
   }
 
   // 2. g^_i = g~_i - C_i . gamma into the scratch row; a_w = sum w_i g^_i^2; s = b sqrt(a_w / a); the support of T
-  double* g = gs + (int64_t)j * n;
   double aw = 0.0, up = 0.0, dn = 0.0;   // up, -dn: the ends of T's support, K'(+inf) and K'(-inf)
   for (int64_t i = tid; i < n; i += 256) {
     const double m = mu[i];
-    const double* row = Cv + i * c;
+    const double* crow = Cv + i * c;
     double d = 0.0;
-    for (int k = 0; k < c; ++k) d = fma(row[k], gam[k], d);
-    const double gh = rd(j, i, mean) - d;
+    for (int k = 0; k < c; ++k) d = fma(crow[k], gam[k], d);
+    const double gh = row(i) - d;
     g[i] = gh;
     aw = fma((m * (1.0 - m)) * gh, gh, aw);
     up += gh > 0.0 ? gh * (1.0 - m) : -gh * m;
@@ -269,21 +239,76 @@ __global__ __launch_bounds__(256) void k_scan_spa(int32_t n, int32_t r, int32_t 
     if (v > 0.0 && v < INFINITY) ltail[side] = spa_log_tail(v);
     else good = false;
   }
+  return SpaRoots{aw, s, zeta[0], zeta[1], ltail[0], ltail[1], iters, good};
+}
+
+// log p of a call: the sum of the two tails, or the normal value log(2 upper tail(|zs|)) where the saddlepoint failed (a thread)
+__device__ __forceinline__ double spa_log_p(const SpaRoots& o, double zs) {
+  if (o.good) {
+    const double hi = fmax(o.ltail_hi, o.ltail_lo), lw = fmin(o.ltail_hi, o.ltail_lo);
+    return hi + log1p(exp(lw - hi));
+  }
+  return log(erfcx(fabs(zs) * 0.70710678118654752440)) - 0.5 * zs * zs;
+}
+
+// stats: the (q + 4) x r statistics of the plain block (q = c + 1): rows n_obs | mean | css | |x|^2 | w(C)'x (c rows) | w(y~)'x.
+// R: c x c upper triangular, R'R = w(C)'w(C); u: R^-T w(C)'w(y~); mu, Cv, Minv: as spa_roots takes them; gs: the handle's
+// scratch, row `marker` of n doubles holds g^.  out: SPA_ROWS x r.
+template <class Reader>
+__global__ __launch_bounds__(256) void k_scan_spa(int32_t n, int32_t r, int32_t c, Reader rd, const double* __restrict__ stats,
+                                                  const double* __restrict__ R, const double* __restrict__ u,
+                                                  const double* __restrict__ mu, const double* __restrict__ Cv,
+                                                  const double* __restrict__ Minv, double cutoff, double* __restrict__ gs,
+                                                  double* __restrict__ out) {
+  __shared__ double red[4 * 3];
+  __shared__ double tred[256];
+  __shared__ double tt[SPA_CMAX + 1], gam[SPA_CMAX + 1], head[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int j = blockIdx.x;
+  const SpaFold fold{red, lane, wv};
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  auto put = [&](int row, double v) { out[(int64_t)row * r + j] = v; };
+
+  // 0. a, b, zs from the block's statistics: R' z = w(C)'x by forward substitution (thread 0; c <= 31)
   if (tid == 0) {
-    double lp;
-    if (good) {
-      const double hi = fmax(ltail[0], ltail[1]), lw = fmin(ltail[0], ltail[1]);
-      lp = hi + log1p(exp(lw - hi));
-    } else {
-      lp = log(erfcx(fabs(zs) * 0.70710678118654752440)) - 0.5 * zs * zs;  // log(2 upper tail(|zs|)): the normal value
+    const double* S = stats + j;
+    double zz = 0.0, uz = 0.0;
+    for (int k = 0; k < c; ++k) {
+      double v = S[(int64_t)(4 + k) * r];
+      for (int l = 0; l < k; ++l) v -= R[l * c + k] * tt[l];
+      v /= R[k * c + k];
+      tt[k] = v;
+      zz += v * v;
+      uz += u[k] * v;
     }
-    put(0, lp);
-    put(1, aw);
-    put(2, s);
-    put(3, zeta[0]);
-    put(4, zeta[1]);
-    put(5, (double)iters);
-    put(6, good ? 1.0 : 2.0);
+    const double a = S[3 * (int64_t)r] - zz, b = S[(int64_t)(4 + c) * r] - uz;
+    head[0] = a;
+    head[1] = b;
+    head[2] = S[0];
+    head[3] = S[2 * (int64_t)r];
+  }
+  __syncthreads();
+  const double a = head[0], b = head[1];
+  const double zs = b / sqrt(a);
+  if (head[2] == 0.0 || head[3] == 0.0 || !(a > 0.0) || !(fabs(zs) > cutoff)) {
+    if (tid == 0) {
+#pragma unroll
+      for (int row = 0; row < SPA_ROWS - 1; ++row) put(row, nan);
+      put(SPA_ROWS - 1, 0.0);
+    }
+    return;  // (the whole workgroup)
+  }
+  const double mean = stats[(int64_t)r + j];
+  const SpaRoots o = spa_roots(n, c, [&](int64_t i) { return rd(j, i, mean); }, a, b, mu, Cv, Minv, gs + (int64_t)j * n, tred, tt,
+                               gam, fold);
+  if (tid == 0) {
+    put(0, spa_log_p(o, zs));
+    put(1, o.aw);
+    put(2, o.s);
+    put(3, o.zeta_hi);
+    put(4, o.zeta_lo);
+    put(5, (double)o.iters);
+    put(6, o.good ? 1.0 : 2.0);
   }
 }
 

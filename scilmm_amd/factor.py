@@ -283,6 +283,12 @@ class Symbolic(object):
         check(lib().scilmm_sets_finish_timing(self._h, ms), self._h)
         return float(ms[0])
 
+    def sets_spa_timing(self):
+        """``k_sets_spa`` of the last ``Factor.sets_spa*_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 1)()
+        check(lib().scilmm_sets_spa_timing(self._h, ms), self._h)
+        return float(ms[0])
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -502,6 +508,41 @@ class Factor(object):
         rho = np.ascontiguousarray(rho, dtype=np.float64)
         check(lib().scilmm_sets_finish_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, ptr(set_start), weight_mode,
                                            dweights_ptr, method, ptr(rho), rho.size, dout_ptr, ld_out, dlam_ptr), self.sym._h)
+
+    def sets_finish_scaled_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method,
+                               rho, dout_ptr, ld_out, dlam_ptr, dvscale_ptr):
+        """``sets_finish_dev`` with the columns' variance scales ``dvscale_ptr`` (``r`` doubles, what ``sets_spa*_dev`` wrote) in
+        the weights of ``A`` alone (``scilmm_sets_finish_scaled_dev``; ``scilmm_amd.glmm.BinarySetTest`` is the interface)."""
+        set_start = np.ascontiguousarray(set_start, dtype=np.int32)
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        check(lib().scilmm_sets_finish_scaled_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, ptr(set_start),
+                                                  weight_mode, dweights_ptr, method, ptr(rho), rho.size, dout_ptr, ld_out, dlam_ptr,
+                                                  dvscale_ptr), self.sym._h)
+
+    def _sets_spa(self, entry, head, r, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr, n_sets,
+                  set_start, weight_mode, dweights_ptr, dbspa_ptr, dvscale_ptr):
+        set_start = np.ascontiguousarray(set_start, dtype=np.int32)
+        check(entry(self._h, *(tuple(head) + (r, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr,
+                                             n_sets, ptr(set_start), weight_mode, dweights_ptr, dbspa_ptr, dvscale_ptr))), self.sym._h)
+
+    def sets_spa_dev(self, dG_ptr, ld, r, *tail):
+        """The sets' variance scales and burden saddlepoint rows behind a Gram block and its ``scan_spa_dev``
+        (``scilmm_sets_spa_dev``).  ``tail``: ``dstats, dgram, dR, du, dmu, dC, c, dMinv, cutoff, dspa, n_sets, set_start`` (host
+        int32 offsets), ``weight_mode, dweights, dbspa`` (``n_sets`` x 13 doubles out), ``dvscale`` (``r`` doubles out); enqueues
+        without synchronising (``scilmm_amd.glmm.BinarySetTest`` is the interface)."""
+        self._sets_spa(lib().scilmm_sets_spa_dev, (dG_ptr, ld), r, *tail)
+
+    def sets_spa_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, *tail):
+        """``sets_spa_dev`` behind a block of packed PLINK rows (``scilmm_sets_spa_bed_dev``)."""
+        self._sets_spa(lib().scilmm_sets_spa_bed_dev, (dbed_ptr, ld, n_samples, dsample_ptr, flags), r, *tail)
+
+    def sets_spa_dosage_dev(self, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, *tail):
+        """``sets_spa_dev`` behind a block of dosage rows (``scilmm_sets_spa_dosage_dev``)."""
+        self._sets_spa(lib().scilmm_sets_spa_dosage_dev, (ddos_ptr, dtype, ld, n_samples, dsample_ptr), r, *tail)
+
+    def sets_spa_timing(self):
+        """``k_sets_spa`` of the last ``sets_spa*_dev`` on the handle in ms, after ``sync()`` (``Symbolic.sets_spa_timing``)."""
+        return self.sym.sets_spa_timing()
 
     def scan_spa_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c,
                          dMinv_ptr, cutoff, dspa_ptr):

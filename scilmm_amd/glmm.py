@@ -20,7 +20,8 @@ the variance ratio ``a / a_w`` rescales the score to ``s = b sqrt(a_w / a)`` of 
 ``sum g^_i (y_i - mu_i)``, whose cumulant generating function is inverted on the device.
 
 There is no CPU form of the device side; the argument checks and ``binary_stats`` are pure NumPy.  Out of scope: other families,
-Firth correction, variant-set and G x E tests for binary traits, distributed handles.
+Firth correction, G x E tests for binary traits, distributed handles.  Variant-set tests at a fitted null: ``null.sets()``, a
+``BinarySetTest`` (the method: DESIGN.md section 20; its host algebra: ``scilmm_amd.binary_sets``).
 """
 import numpy as np
 import scipy.linalg as la
@@ -28,7 +29,8 @@ import scipy.sparse as sp
 import scipy.special as sc
 import scipy.stats as stats
 
-from . import _lib, assoc
+from . import _lib, assoc, binary_sets
+from . import sets as setmod
 from .markers import Int8Rows, as_run, vp
 
 SPA_ROWS = 7                # log_p | a_w | s | zeta_hi | zeta_lo | iters | flag (csrc/spa.hip.h)
@@ -61,6 +63,25 @@ def check_cutoff(cutoff):
     if not cutoff >= 0.0:
         raise ValueError("cutoff must be >= 0, got %r" % (cutoff,))
     return cutoff
+
+
+def check_null_covariates(null, covariates):
+    """``covariates`` as the contiguous n x c float64 matrix of a fitted null (1 <= c <= 31, one row per fitted probability)."""
+    covariates = np.ascontiguousarray(covariates, dtype=np.float64)
+    if covariates.ndim != 2 or covariates.shape[0] != np.size(null.mu) or not 1 <= covariates.shape[1] <= CMAX:
+        raise ValueError("covariates must be the n x c matrix (1 <= c <= %d) the null model was fitted with" % CMAX)
+    return covariates
+
+
+def upload_null(model, null, covariates):
+    """What the saddlepoint kernels read of a fitted null, once per model: ``mu``, ``C``, ``(C'WC)^-1``, ``R`` and ``u`` on the device."""
+    torch, model.null = model.torch, null
+    w = np.asarray(null.weights, dtype=np.float64)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+    model.dmu, model.dC = up(null.mu), up(covariates)
+    model.dMinv = up(la.inv((covariates.T * w).dot(covariates)))
+    model.dR, model.du = up(model.R), up(model.u)
+    torch.cuda.synchronize()
 
 
 def logistic_irls(C, y, tol=1e-12, max_iter=100):
@@ -112,6 +133,10 @@ class NullModel(object):
     def scan(self, block=None, cutoff=2.0):
         """The score scan with saddlepoint p-values at this null: a ``BinaryScan``."""
         return BinaryScan(self._model.cholesky_func, self, self._model.covariates, block=block, cutoff=cutoff)
+
+    def sets(self, block=None, cutoff=2.0):
+        """Burden, SKAT and SKAT-O of marker sets at this null, with saddlepoint-adjusted variances: a ``BinarySetTest``."""
+        return BinarySetTest(self._model.cholesky_func, self, self._model.covariates, block=block, cutoff=cutoff)
 
 
 class LogisticMixedModel(object):
@@ -260,18 +285,10 @@ class BinaryScan(assoc.AssociationScan):
 
     def __init__(self, cholesky_func, null, covariates, block=None, cutoff=2.0):
         self.cutoff = check_cutoff(cutoff)
-        covariates = np.ascontiguousarray(covariates, dtype=np.float64)
-        if covariates.ndim != 2 or covariates.shape[0] != np.size(null.mu) or not 1 <= covariates.shape[1] <= CMAX:
-            raise ValueError("covariates must be the n x c matrix (1 <= c <= %d) the null model was fitted with" % CMAX)
+        covariates = check_null_covariates(null, covariates)
         super(BinaryScan, self).__init__(cholesky_func, null.mats_full, null.sigma2_full, covariates, null.working_y, block)
-        torch, self.null = self.torch, null
-        w = np.asarray(null.weights, dtype=np.float64)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-        self.dmu, self.dC = up(null.mu), up(covariates)
-        self.dMinv = up(la.inv((covariates.T * w).dot(covariates)))
-        self.dR, self.du = up(self.R), up(self.u)
         self._dS = None
-        torch.cuda.synchronize()
+        upload_null(self, null, covariates)
 
     def _stats_buffer(self, nrows, m, blk=None, keep=True):
         buf = super(BinaryScan, self)._stats_buffer(nrows, m, blk)
@@ -309,3 +326,117 @@ class BinaryScan(assoc.AssociationScan):
         if chunk_bytes < 1:
             raise ValueError("chunk_bytes must be positive")
         return self._binary(src, slice(0, src.m), chunk_bytes)
+
+
+class BinarySetTest(setmod.VariantSetTest):
+    """Burden, SKAT and SKAT-O of marker sets at a fitted ``NullModel``, with the variance of every marker and of the burden
+    re-calibrated by the saddlepoint approximation before the tests are taken (SAIGE-GENE / SMMAT, with the exact
+    ``K = G~' P G~`` of the Gram block): a ``VariantSetTest`` of ``working_y`` under ``mats_full`` /
+    ``sigma2_full`` whose every block is followed, on the stream and without a wait in between, by the saddlepoint call of its
+    markers (``scan_spa*``), the sets' variance scales and burden saddlepoint (``sets_spa*``) and -- with ``finish="device"`` -- the
+    scaled finish.  ``__call__``, ``test_bed`` and ``test_dosages`` take the arguments of ``VariantSetTest``'s and return its keys
+    with ``burden_p = chi2_1.sf(burden_chi2)``, plus ``burden_chi2_norm = b_B^2 / a_B`` (the unadjusted burden), ``burden_spa_log_p``
+    and ``burden_spa_flag`` (the burden's own saddlepoint call; 0: not attempted), ``burden_scale = phi`` (the burden floor) and
+    ``n_adjusted`` (kept markers whose variance scale is not 1).  ``return_kernel=True`` (host finish) hands out
+    ``(s, K~, w, vscale)`` per set, ``K~ = diag(vscale) K diag(vscale)``.  ``last_bspa`` keeps the device's 13 numbers per set."""
+
+    def __init__(self, cholesky_func, null, covariates, block=None, cutoff=2.0):
+        self.cutoff = check_cutoff(cutoff)
+        covariates = check_null_covariates(null, covariates)
+        super(BinarySetTest, self).__init__(cholesky_func, null.mats_full, null.sigma2_full, covariates, null.working_y, block)
+        upload_null(self, null, covariates)
+
+    def _block_binary(self, src, mode, method, rho, device):
+        """(rows, offsets, weights) -> (the sets' 13 saddlepoint numbers, the columns' variance scales, the finish): the Gram entry
+        point, the markers' saddlepoint call, the sets' and -- ``device`` -- the scaled finish queued one behind the other, one wait;
+        the finish is the sets' rows of the device, or the block's statistics and Gram matrix for the host's."""
+        torch, q, blk, c = self.torch, self.q, self.block, self.c
+        src.stage(blk)
+        new = lambda k: torch.empty((k,), dtype=torch.float64, device="cuda")
+        dS, dK, dP, dB, dV, dW = new((q + 4) * blk), new(blk * blk), new(SPA_ROWS * blk), new(blk * binary_sets.BSPA_ROWLEN), new(blk), new(blk)
+        ld = setmod.FINISH_HEAD + rho.size
+        dO = new(blk * ld)
+        meth = setmod.METHODS.index(method)
+        pS, pK, pP, pB, pV, pO = (vp(d.data_ptr()) for d in (dS, dK, dP, dB, dV, dO))
+        pR, pu = vp(self.dR.data_ptr()), vp(self.du.data_ptr())
+        null = (pR, pu, vp(self.dmu.data_ptr()), vp(self.dC.data_ptr()), c, vp(self.dMinv.data_ptr()), self.cutoff, pP)
+
+        def run(rows, start, w):
+            rb, ns = rows.size, start.size - 1
+            src.load(rows)
+            if w is not None:
+                dW[:rb].copy_(torch.from_numpy(w))
+            pW = vp(dW.data_ptr()) if w is not None else None
+            src.enqueue(0, rb, pS, pK)
+            src.spa(0, rb, (pS,) + null)
+            src.sets_spa(0, rb, (pS, pK) + null + (ns, start, mode, pW, pB, pV))
+            if device:
+                self.factor.sets_finish_scaled_dev(rb, q, pS, pK, pR, pu, c, ns, start, mode, pW, meth, rho, pO, ld, None, pV)
+            self.sym.sync()
+            B = dB[:ns * binary_sets.BSPA_ROWLEN].cpu().numpy().reshape(ns, binary_sets.BSPA_ROWLEN)
+            if device:
+                return B, None, dO[:ns * ld].cpu().numpy().reshape(ns, ld)
+            return B, dV[:rb].cpu().numpy(), (dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb), dK[:rb * rb].cpu().numpy().reshape(rb, rb))
+        return run
+
+    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host"):
+        """The checks of ``VariantSetTest._run`` (before any launch), then block by block the four calls of ``_block_binary`` and
+        step 5 of the method: on the device's rows, or in NumPy on ``(t, A~)`` (``binary_sets.scaled_tests``)."""
+        sets = setmod.check_sets(sets, src.m, self.block)
+        weights = setmod.check_weights(weights, sets)
+        setmod.check_method(method)
+        if finish not in setmod.FINISHES:
+            raise ValueError("finish must be one of %s, got %r" % (", ".join(setmod.FINISHES), finish))
+        if finish == "device" and return_kernel:
+            raise ValueError('return_kernel=True needs finish="host": the device finish does not bring K back')
+        rho = setmod.check_rho(rho) if skato else None
+        self._check_factor()
+        ns, device = len(sets), finish == "device"
+        out = {k: np.full(ns, np.nan) for k in setmod.KEYS + binary_sets.BINARY_KEYS}
+        for k in ("n_used", "burden_spa_flag", "n_adjusted"):
+            out[k] = np.zeros(ns, dtype=np.int64)
+        if skato:
+            out.update({k: np.full(ns, np.nan) for k in setmod.SKATO_KEYS[:3]})
+            out["skato_p_rho"] = np.full((ns, rho.size), np.nan)
+        self.last_bspa = np.full((ns, binary_sets.BSPA_ROWLEN), np.nan)
+        given = not (weights is None or isinstance(weights, str))
+        mode = setmod.WEIGHT_GIVEN if given else setmod.WEIGHT_ONES if weights is None else setmod.WEIGHT_BETA
+        block = self._block_binary(src, mode, method, rho if skato else np.empty(0), device) if sets else None
+        kernel = [None] * ns
+        for members in setmod.pack_sets([s.size for s in sets], self.block):
+            start = np.concatenate([[0], np.cumsum([sets[i].size for i in members])]).astype(np.int32)
+            w = np.ascontiguousarray(np.concatenate([weights[i] for i in members])) if given else None
+            B, V, fin = block(np.concatenate([sets[i] for i in members]), start, w)
+            self.last_bspa[members] = B
+            if device:
+                out["n_used"][members] = fin[:, 0].astype(np.int64)
+                for col, k in ((1, "burden_beta"), (2, "burden_se"), (3, "burden_chi2"), (4, "skat_q"), (5, "skat_p")):
+                    out[k][members] = fin[:, col]
+                if skato:
+                    for col, k in ((6, "skato_p"), (7, "skato_pmin"), (8, "skato_rho")):
+                        out[k][members] = fin[:, col]
+                    out["skato_p_rho"][members] = fin[:, setmod.FINISH_HEAD:]
+                continue
+            S, G = fin
+            for i, a, b in zip(members, start[:-1], start[1:]):
+                wi = weights if not given else weights[i]
+                s, K, wk, keep = setmod.set_kernel(S[:, a:b], G[a:b, a:b], self.R, self.u, wi)
+                vs = V[a:b][keep]
+                out["n_used"][i] = int(keep.sum())
+                if keep.any():
+                    t = binary_sets.scaled_tests(s, K, wk, vs, method, rho)
+                    for k in ("burden_beta", "burden_se", "burden_chi2", "skat_q", "skat_p"):
+                        out[k][i] = t[k]
+                    if t["skato"] is not None:
+                        out["skato_p"][i], out["skato_pmin"][i], out["skato_rho"][i], out["skato_p_rho"][i] = t["skato"]
+                kernel[i] = (s, vs[:, None] * K * vs[None, :], wk, vs)
+        P = self.last_bspa
+        used = out["n_used"] > 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["burden_chi2_norm"] = P[:, 8] * P[:, 8] / P[:, 7]
+        out["burden_p"][used] = stats.chi2.sf(out["burden_chi2"][used], 1)
+        out["burden_spa_log_p"], out["burden_scale"] = P[:, 0].copy(), P[:, 11].copy()
+        out["burden_spa_flag"], out["n_adjusted"] = P[:, 6].astype(np.int64), P[:, 12].astype(np.int64)
+        if return_kernel:
+            out["kernel"] = kernel
+        return out

@@ -8,6 +8,8 @@ input form.  A source has ``m`` (its markers), ``row_bytes`` (host bytes of one 
                                block of ``m`` environment columns at ``pE`` (the ``_gxe_dev`` twin)
     spa(k0, rb, tail)          queue the saddlepoint p-values of block (k0, rb) behind its plain block (the ``scilmm_scan_spa*_dev``
                                twin; ``tail``: what follows ``r`` in its arguments -- ``scilmm_amd.glmm``)
+    sets_spa(k0, rb, tail)     queue the sets' variance scales and burden saddlepoint rows of block (k0, rb) behind its Gram block
+                               and its ``spa`` (the ``scilmm_sets_spa*_dev`` twin -- ``scilmm_amd.binary_sets``)
 
 Everything else -- chunks, blocks, the synchronisation, the host algebra -- is the callers' and does not depend on the form.
 """
@@ -80,6 +82,9 @@ class Int8Rows(MarkerSource):
     def spa(self, k0, rb, tail):
         self.model.factor.scan_spa_dev(*(self._head(k0) + (rb,) + tuple(tail)))
 
+    def sets_spa(self, k0, rb, tail):
+        self.model.factor.sets_spa_dev(*(self._head(k0) + (rb,) + tuple(tail)))
+
 
 class BedRows(MarkerSource):
     """The packed rows of a ``BedFile``, decoded on the device: mapped file -> pinned buffer (the one host pass over the bytes)
@@ -121,6 +126,9 @@ class BedRows(MarkerSource):
     def spa(self, k0, rb, tail):
         self.model.factor.scan_spa_bed_dev(*(self._head(k0) + (rb,) + tuple(tail)))
 
+    def sets_spa(self, k0, rb, tail):
+        self.model.factor.sets_spa_bed_dev(*(self._head(k0) + (rb,) + tuple(tail)))
+
 
 class DosageRows(MarkerSource):
     """m x N dosages (``check_dosages``; ``dtype``: the element type of the C entry point): host array -> pinned buffer (the one
@@ -153,3 +161,6 @@ class DosageRows(MarkerSource):
 
     def spa(self, k0, rb, tail):
         self.model.factor.scan_spa_dosage_dev(*(self._head(k0) + (rb,) + tuple(tail)))
+
+    def sets_spa(self, k0, rb, tail):
+        self.model.factor.sets_spa_dosage_dev(*(self._head(k0) + (rb,) + tuple(tail)))

@@ -12,7 +12,13 @@ block's, and the agreement of X'X with the gg row and between shapes.
 --finish times the finish of a block instead (scilmm_sets_finish_dev): 512 markers in consecutive sets of 2 .. 17 markers, packed
 into 128-wide blocks, and a block that is one 128-marker set.  Per block: k_sets_finish by HIP events, with and without SKAT-O
 (three warm-up rounds, 20 rounds, median and IQR), next to the block's forward sweep; and the wall time per set of the whole
-call with finish="device" and finish="host", with and without skato, on the same packed sets (the median of three calls)."""
+call with finish="device" and finish="host", with and without skato, on the same packed sets (the median of three calls).
+  usage: sets_timing.py 100k --binary [--out profiles/sets_spa_100k.json]
+--binary times one block of a dozen sets (3 .. 18 rare markers, 128 together) as the binary-trait tests queue it
+(scilmm_amd.glmm.BinarySetTest, finish="device"): the Gram block, k_scan_spa of its markers, k_sets_spa and the scaled
+k_sets_finish with SKAT-O, each by its own HIP events, at a null point of a simulated 5 % phenotype, at the default cutoff 2 and
+at cutoff 0 (every marker and every burden saddlepointed: the most the block can cost); next to it, in the same run and on the
+same sets, the quantitative Gram block + k_sets_finish, and the ratio of the two totals."""
 import argparse, ctypes, json, os, sys
 import numpy as np
 import scipy.sparse as sp
@@ -22,6 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("workload"); ap.add_argument("--blocks", type=int, default=20); ap.add_argument("--out", default=None)
 ap.add_argument("--shapes", default=None)
 ap.add_argument("--finish", action="store_true")
+ap.add_argument("--binary", action="store_true")
 args = ap.parse_args()
 import torch
 from scilmm_amd import SparseCholesky, VariantSetTest
@@ -99,8 +106,65 @@ def finish_leg():
     return rec
 
 
-if args.finish:
-    rec = finish_leg()
+def binary_leg():
+    from scilmm_amd import LogisticMixedModel
+    from scilmm_amd.binary_sets import BSPA_ROWLEN
+    from scilmm_amd.glmm import SPA_ROWS, logistic_irls
+    from scilmm_amd.sets import FINISH_HEAD, RHO_DEFAULT
+    sizes = [3, 5, 8, 8, 10, 10, 11, 12, 13, 14, 16, 18]
+    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    assert start[-1] == R
+    rho, ld_out = np.asarray(RHO_DEFAULT), FINISH_HEAD + len(RHO_DEFAULT)
+    new = lambda k: torch.zeros((k,), dtype=torch.float64, device="cuda")
+    dP, dB, dV, dO = new(SPA_ROWS * R), new(BSPA_ROWLEN * R), new(R), new(R * ld_out)
+    pG, pS, pK, pP, pB, pV, pO = (vp(d.data_ptr()) for d in (dG, dS, dK, dP, dB, dV, dO))
+    rec = {"workload": args.workload, "n": int(n), "r": R, "set_sizes": sizes, "n_rho": int(rho.size), "prevalence": 0.05,
+           "timer": "HIP events around each kernel, the block's calls queued behind each other, one synchronise per round; three "
+                    "warm-up rounds, then %d rounds" % args.blocks}
+    # the quantitative block on the same sets: Gram + finish
+    dR, du = (torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in (tester.R, tester.u))
+    t = []
+    for it in range(3 + args.blocks):
+        fac.scan_block_gram_dev(pG, ld, R, vp(tester.dQ.data_ptr()), q, pS, pK)
+        fac.sets_finish_dev(R, q, pS, pK, vp(dR.data_ptr()), vp(du.data_ptr()), q - 1, len(sizes), start, 0, None, 0, rho, pO, ld_out, None)
+        sym.sync()
+        if it >= 3: t.append(list(sym.scan_timing()) + [sym.sets_finish_timing()])
+    a = np.asarray(t)
+    quant = float(np.median(a.sum(axis=1)))
+    rec["quantitative"] = {"gram_block_ms": summary(a[:, :3].sum(axis=1)), "finish_ms": summary(a[:, 3]), "total_ms": summary(a.sum(axis=1))}
+    # the binary block: a null point at the covariate-only fit, a random effect drawn on top
+    yb = (rng.random(n) < 0.05).astype(np.float64)
+    model = LogisticMixedModel(SparseCholesky(), [A], Cv, yb)
+    null = model.null_at([0.5], logistic_irls(model.covariates, yb), 0.3 * rng.standard_normal(n))
+    rec["binary"] = {}
+    for cutoff in (2.0, 0.0):
+        bt = null.sets(block=R, cutoff=cutoff)
+        bf, bs, c = bt.factor, bt.sym, bt.c
+        tail = (vp(bt.dR.data_ptr()), vp(bt.du.data_ptr()), vp(bt.dmu.data_ptr()), vp(bt.dC.data_ptr()), c, vp(bt.dMinv.data_ptr()), cutoff, pP)
+        t = []
+        for it in range(3 + args.blocks):
+            bf.scan_block_gram_dev(pG, ld, R, vp(bt.dQ.data_ptr()), bt.q, pS, pK)
+            bf.scan_spa_dev(pG, ld, R, pS, *tail)
+            bf.sets_spa_dev(pG, ld, R, pS, pK, *(tail + (len(sizes), start, 0, None, pB, pV)))
+            bf.sets_finish_scaled_dev(R, bt.q, pS, pK, vp(bt.dR.data_ptr()), vp(bt.du.data_ptr()), c, len(sizes), start, 0, None, 0, rho, pO,
+                                      ld_out, None, pV)
+            bs.sync()
+            if it >= 3: t.append(list(bs.scan_timing()) + [bs.spa_timing(), bs.sets_spa_timing(), bs.sets_finish_timing()])
+        b = np.asarray(t)
+        P = dP.cpu().numpy().reshape(SPA_ROWS, R)
+        Bs = dB.cpu().numpy()[:BSPA_ROWLEN * len(sizes)].reshape(len(sizes), BSPA_ROWLEN)
+        tot = summary(b.sum(axis=1))
+        rec["binary"]["cutoff_%g" % cutoff] = {
+            "gram_block_ms": summary(b[:, :3].sum(axis=1)), "scan_spa_ms": summary(b[:, 3]), "sets_spa_ms": summary(b[:, 4]),
+            "scaled_finish_ms": summary(b[:, 5]), "total_ms": tot, "total_over_quantitative": tot["median"] / quant,
+            "markers_saddlepointed": int(np.sum(P[6] > 0)), "burdens_saddlepointed": int(np.sum(Bs[:, 6] > 0)),
+            "sets_with_an_adjusted_marker": int(np.sum(Bs[:, 12] > 0)), "sets_at_the_burden_floor": int(np.sum(Bs[:, 11] > 1.0))}
+        del bt
+    return rec
+
+
+if args.finish or args.binary:
+    rec = binary_leg() if args.binary else finish_leg()
     print(json.dumps(rec))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
