@@ -368,6 +368,25 @@ int scilmm_scan_panel_dev(scilmm_factor* fac, int32_t r, const double* d_Y, int6
  * follows it: ms[0] k_scan_panel, ms[1] k_panel_fold (tools/panel_timing.py).  No counterpart in the reference. */
 int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Variant sets wider than one block: keep the forward solution X that the LAST scan block on this handle left behind (any
+ * form), so that the sub-blocks that follow can form their cross products X_b^T X_a against it with scilmm_scan_panel_dev.  X is
+ * n x rp row-major in the PERMUTED row order, rp = r rounded up to 16, columns r .. rp - 1 zero; element (i, j) goes to
+ * d_dst[i * ld_dst + col0 + j].
+ *   r      : columns of the block left behind, 1 .. 128; it must be the r of that block.
+ *   d_dst  : the store, n x ld_dst row-major, 16-byte aligned; ld_dst % 16 == 0 and ld_dst >= col0 + rp.
+ *   col0   : first column of the store that is written, >= 0 and a multiple of 16.
+ * Exactly n rp doubles are written, the zero padding included: the store can go to scilmm_scan_panel_dev as d_Y (ld_y = ld_dst,
+ * t = the columns kept so far) without a memset; nothing outside columns col0 .. col0 + rp - 1 is touched.  One store-only
+ * kernel (k_scan_keep: 16-byte loads, 16-byte stores, no LDS, no atomics) is enqueued on the handle's stream without
+ * synchronising; scilmm_timing.n_float_atomic_launches is not touched.  It writes nothing of the work buffers and does not
+ * forget the block: a Gram pass has come before it, and panels and further keeps may follow the same block.  Nothing is allocated.
+ * SCILMM_ERR_ARG before anything is dereferenced: a null fac or d_dst, r outside 1 .. 128, col0 < 0 or col0 % 16 != 0,
+ * ld_dst % 16 != 0 or ld_dst < col0 + rp, d_dst not 16-byte aligned.  SCILMM_ERR_STATE with a message, the handle left usable,
+ * as for scilmm_scan_panel_dev: no block left behind, or another r than that block's; refusals as for the half-solves (a
+ * distributed handle, fp32-product fronts, a factor consumed by the selected inverse).  scilmm_amd.VariantSetTest with
+ * max_markers is the interface.  No counterpart in the reference. */
+int scilmm_scan_block_keep_dev(scilmm_factor* fac, int32_t r, double* d_dst, int64_t ld_dst, int64_t col0);
+
 /* Binary traits: the saddlepoint (SPA) p-value of the score test for the r markers of a plain scan block, queued BEHIND that
  * block (scilmm_scan_block_dev, _bed_dev or _dosage_dev with the same marker arguments and the same r) on the handle's stream.
  * With the working vector y~ of a logistic mixed model in the place of y (scilmm_amd.glmm), the block's statistics hold the

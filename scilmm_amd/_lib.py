@@ -79,7 +79,7 @@ SYMBOLS = [
     "scilmm_scan_block_gram_dev", "scilmm_scan_block_bed_gram_dev",
     "scilmm_scan_block_dosage_dev", "scilmm_scan_block_dosage_gram_dev",
     "scilmm_scan_block_gxe_dev", "scilmm_scan_block_bed_gxe_dev", "scilmm_scan_block_dosage_gxe_dev", "scilmm_gxe_timing",
-    "scilmm_scan_panel_dev", "scilmm_panel_timing",
+    "scilmm_scan_panel_dev", "scilmm_panel_timing", "scilmm_scan_block_keep_dev",
     "scilmm_scan_spa_dev", "scilmm_scan_spa_bed_dev", "scilmm_scan_spa_dosage_dev", "scilmm_spa_timing",
     "scilmm_sets_finish_dev", "scilmm_sets_finish_timing", "scilmm_sets_finish_scaled_dev",
     "scilmm_sets_spa_dev", "scilmm_sets_spa_bed_dev", "scilmm_sets_spa_dosage_dev", "scilmm_sets_spa_timing",
@@ -187,6 +187,7 @@ def lib():
     L.scilmm_gxe_timing.argtypes = [vp, P(dbl)]
     L.scilmm_scan_panel_dev.argtypes = [vp, i32, vp, i64, i32, vp, i64]
     L.scilmm_panel_timing.argtypes = [vp, P(dbl)]
+    L.scilmm_scan_block_keep_dev.argtypes = [vp, i32, vp, i64, i64]
     spa = [vp, vp, vp, vp, vp, i32, vp, dbl, vp]   # d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa
     L.scilmm_scan_spa_dev.argtypes = [vp, vp, i64, i32] + spa
     L.scilmm_scan_spa_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32] + spa

@@ -167,6 +167,20 @@ auto fill_dosage(const void* d_dos, int64_t ld, int32_t n_samples, const int32_t
   };
 }
 
+// What reads the block the last scan block on the handle left in X asks first: that it is still there, and that r is its.
+int block_left(scilmm_symbolic* sym, const Dev* D, const char* who, int32_t r) {
+  if (D->block_r == 0) {
+    sym->err = std::string(who) + ": no scan block on this handle since the work buffers were last used (a solve, a product or a "
+                                  "refactorization came in between): run the block first";
+    return SCILMM_ERR_STATE;
+  }
+  if (D->block_r != r) {
+    sym->err = std::string(who) + ": r = " + std::to_string(r) + ", the block left behind has " + std::to_string(D->block_r) + " columns";
+    return SCILMM_ERR_STATE;
+  }
+  return SCILMM_OK;
+}
+
 // X^T Y for the block the last scan block on the handle left in X (scilmm_scan_panel_dev): the refusals of the half-solves, the
 // record of that block, the partial tiles (grown for a wider panel only: the stream is synchronised first, and nothing is
 // allocated afterwards for the same or a smaller t), k_scan_panel and k_panel_fold between the call's own events.  Nothing of
@@ -178,15 +192,7 @@ int scan_panel(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, i
   TRY(check_half(fac, who));
   TRY(settle(fac, who));
   Dev* D = (Dev*)sym->device;
-  if (D->block_r == 0) {
-    sym->err = std::string(who) + ": no scan block on this handle since the work buffers were last used (a solve, a product or a "
-                                  "refactorization came in between): run the block first";
-    return SCILMM_ERR_STATE;
-  }
-  if (D->block_r != r) {
-    sym->err = std::string(who) + ": r = " + std::to_string(r) + ", the block left behind has " + std::to_string(D->block_r) + " columns";
-    return SCILMM_ERR_STATE;
-  }
+  TRY(block_left(sym, D, who, r));
   const int32_t n = sym->S->n, rp = D->block_rp, ntile = (rp / 16) * PANEL_NJ;
   const int32_t npanel = (t + PANEL_COLS - 1) / PANEL_COLS;
   const int slice = panel_slice();
@@ -205,6 +211,25 @@ int scan_panel(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, i
                      (const double*)D->panel_partial, r, t, d_xty, ld_out);
   HIPCHK(hipEventRecord(D->panel_ev[2], s0));
   D->panel_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
+// The block the last scan block on the handle left in X, copied to columns col0 .. of a caller's store
+// (scilmm_scan_block_keep_dev): the refusals and the record of scan_panel, then k_scan_keep.  Nothing is allocated, nothing of the
+// work buffers is written and the record stays: a Gram pass, panels and further keeps may follow the same block.
+int scan_keep(scilmm_factor* fac, int32_t r, double* d_dst, int64_t ld_dst, int64_t col0) {
+  const char* who = "scilmm_scan_block_keep_dev";
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  TRY(block_left(sym, D, who, r));
+  const int32_t n = sym->S->n;
+  const int64_t nchunk = ((int64_t)n + KEEP_ROWS - 1) / KEEP_ROWS;
+  hipLaunchKernelGGL(k_scan_keep, dim3((unsigned)std::min<int64_t>(nchunk, KEEP_GRID)), dim3(256), 0, D->stream, n, D->block_rp,
+                     (const double*)D->X, d_dst, ld_dst, col0);
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }

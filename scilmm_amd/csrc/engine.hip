@@ -317,6 +317,14 @@ int scilmm_scan_panel_dev(scilmm_factor* fac, int32_t r, const double* d_Y, int6
   return scan_panel(fac, r, d_Y, ld_y, t, d_xty, ld_out);
 }
 
+// The block the last scan block left behind, kept in a caller's store: what needs no handle is checked first
+int scilmm_scan_block_keep_dev(scilmm_factor* fac, int32_t r, double* d_dst, int64_t ld_dst, int64_t col0) {
+  if (!fac || !d_dst || r < 1 || r > RPMAX || col0 < 0 || col0 % 16 != 0 || ld_dst % 16 != 0) return SCILMM_ERR_ARG;
+  const int64_t rp = (r + 15) / 16 * 16;
+  if (ld_dst < rp || ld_dst - rp < col0 || (uintptr_t)d_dst % 16 != 0 || !fac->sym || !fac->sym->S) return SCILMM_ERR_ARG;
+  return scan_keep(fac, r, d_dst, ld_dst, col0);
+}
+
 // The saddlepoint p-values behind a plain block: the form's marker arguments are checked as its plain entry point checks them
 int scilmm_scan_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_R,
                         const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff,

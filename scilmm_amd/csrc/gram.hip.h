@@ -2,6 +2,7 @@
 // solution X a scan block leaves behind -- one more pass over X, GEMM-shaped, on the fp64 matrix pipe.
 //   k_scan_gram : slice partial tiles of X^T X (lower triangle of 16 x 16 tiles)   reads  n * rp * 8
 //   k_gram_fold : ... folded in slice order and mirrored into the r x r result     reads  slices * tiles * 2 KB
+//   k_scan_keep : X copied into a pitched store, for sets wider than a block       reads and writes  n * rp * 8
 // No floating-point atomics: every entry's summation order is fixed by (n, rp) alone, in either mode of the handle.
 //
 // X is row-major n x rp, rp = r rounded up to 16, columns r .. rp zero (k_scan_dequant / k_bed_dequant write them so).
@@ -180,6 +181,32 @@ __global__ __launch_bounds__(GRAM_FOLD * 256) void k_gram_fold(int64_t nslice, i
       for (int u = 1; u < GRAM_FOLD; ++u) v += red[u * 256 + e];
       gram[(int64_t)i * r + j] = v;
       if (j < i) gram[(int64_t)j * r + i] = v;
+    }
+  }
+}
+
+// A set wider than one block (scilmm_scan_block_keep_dev): the block's forward solution X (n x rp, contiguous) copied to
+// columns col0 .. col0 + rp - 1 of a pitched store (n x ld_dst), where scilmm_scan_panel_dev reads it as Y for the cross
+// products with the sub-blocks that follow.  Store-only: 16 bytes per lane in, 16 bytes per lane out, no LDS, no atomics.  A
+// workgroup takes KEEP_ROWS rows at a time, the workgroups stride over the chunks; rp, ld_dst and col0 are multiples of 16 and
+// both bases are 16-byte aligned, so every access is an aligned one.  Nothing is read at or past X + n * rp, nothing is written
+// outside the rp columns of a row below n (ld_dst >= col0 + rp); the zero padding r .. rp - 1 travels with the rest.
+constexpr int KEEP_ROWS = 32;      // rows per chunk: 32 * rp / 2 = 256 .. 2048 double2, one to eight per thread
+constexpr int KEEP_GRID = 2048;    // workgroups at most: eight per CU, the rest is strided
+
+__global__ __launch_bounds__(256) void k_scan_keep(int32_t n, int32_t rp, const double* __restrict__ X, double* __restrict__ dst, int64_t ld_dst,
+                                                   int64_t col0) {
+  const int hx = rp >> 1;                                       // double2 per row
+  const int64_t nchunk = ((int64_t)n + KEEP_ROWS - 1) / KEEP_ROWS;
+  for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+    const int64_t p0 = ch * KEEP_ROWS;
+    const int per = (int)min((int64_t)KEEP_ROWS, (int64_t)n - p0) * hx;
+    const double* src = X + p0 * rp;
+    double* out = dst + p0 * ld_dst + col0;
+    for (int e = threadIdx.x; e < per; e += 256) {
+      const int row = e / hx;
+      const double2 v = *(const double2*)(src + 2 * e);
+      *(double2*)(out + row * ld_dst + 2 * (e - row * hx)) = v;
     }
   }
 }

@@ -492,6 +492,14 @@ class Factor(object):
         ``scilmm_amd.panel.TraitPanel`` is the interface).  ``ScilmmError`` when no block was left behind or ``r`` is not its."""
         check(lib().scilmm_scan_panel_dev(self._h, r, dY_ptr, ld_y, t, dxty_ptr, ld_out), self.sym._h)
 
+    def scan_block_keep_dev(self, r, ddst_ptr, ld_dst, col0):
+        """Copy the ``r`` whitened columns the last scan block on this handle left behind (n x rp, rp = ``r`` rounded up to 16, the
+        padding zero) into columns ``col0 .. col0 + rp - 1`` of the device store ``ddst_ptr`` (n x ``ld_dst`` float64, 16-byte
+        aligned, ``ld_dst`` and ``col0`` multiples of 16), where ``scan_panel_dev`` reads them as its panel; enqueues without
+        synchronising and leaves the block where it is (``scilmm_scan_block_keep_dev``; ``scilmm_amd.sets.VariantSetTest`` with
+        ``max_markers`` is the interface).  ``ScilmmError`` when no block was left behind or ``r`` is not its."""
+        check(lib().scilmm_scan_block_keep_dev(self._h, r, ddst_ptr, ld_dst, col0), self.sym._h)
+
     def scan_spa_dev(self, dG_ptr, ld, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr):
         """The saddlepoint p-values of the ``r`` markers of the plain block queued before it (``scilmm_scan_spa_dev``: 7 x r
         numbers to ``dspa_ptr``; ``scilmm_amd.glmm.BinaryScan`` is the interface); enqueues without synchronising."""

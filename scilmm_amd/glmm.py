@@ -379,9 +379,13 @@ class BinarySetTest(setmod.VariantSetTest):
             return B, dV[:rb].cpu().numpy(), (dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb), dK[:rb * rb].cpu().numpy().reshape(rb, rb))
         return run
 
-    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host"):
+    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host", max_markers=None):
         """The checks of ``VariantSetTest._run`` (before any launch), then block by block the four calls of ``_block_binary`` and
-        step 5 of the method: on the device's rows, or in NumPy on ``(t, A~)`` (``binary_sets.scaled_tests``)."""
+        step 5 of the method: on the device's rows, or in NumPy on ``(t, A~)`` (``binary_sets.scaled_tests``).  ``max_markers``
+        must be None: the set saddlepoint collapses the genotypes of ONE block."""
+        if max_markers is not None:
+            raise ValueError("max_markers is not supported for binary traits: the set saddlepoint collapses the genotypes of one "
+                             "block, so a set holds at most %d markers" % self.block)
         sets = setmod.check_sets(sets, src.m, self.block)
         weights = setmod.check_weights(weights, sets)
         setmod.check_method(method)

@@ -32,6 +32,11 @@ DESIGN.md section 19).
 ``scilmm_sets_finish_dev`` behind the block instead: one workgroup per set does the projection, a Jacobi
 eigendecomposition, the tails and the SKAT-O quadrature in LDS, and one copy of a few doubles per set comes back (``burden_p``
 alone stays on the host).  The two agree to the accuracy of the tails (1e-6 relative), not bit for bit.
+
+``max_markers=k`` lets a set hold up to k <= 4096 markers instead of one block's: such a set runs as sub-blocks whose forward
+solutions are kept on the device (``scilmm_scan_block_keep_dev``) and whose cross products ``X_b' X_a`` come from
+``scilmm_scan_panel_dev``; ``assemble_wide`` puts the k x k ``X'X`` together and the host algebra above takes over (DESIGN.md
+section 21).
 """
 import ctypes as C
 
@@ -56,6 +61,8 @@ Z_END = 40.0              # the SKAT-O integral stops here: 2 Phi(-40) is zero i
 FINISHES = ("host", "device")
 WEIGHT_BETA, WEIGHT_ONES, WEIGHT_GIVEN = 0, 1, 2       # weight modes of scilmm_sets_finish_dev
 FINISH_HEAD = 10          # doubles of a set's row before its per-rho p-values
+WIDE_MAX = 4096           # markers of a set at most, with max_markers
+PANEL_COLUMNS = 4096      # columns of a scan_panel_dev call at most: what the kept sub-blocks of a wide set may add up to
 
 
 def _lam(lam):
@@ -266,10 +273,23 @@ def skato_pvalue(t, A, rho=RHO_DEFAULT, method="saddlepoint"):
     return min(p, nr * T), T, float(rho[j0]), p_rho
 
 
-def check_sets(sets, m, block):
-    """``sets`` as a list of int64 index arrays into ``0 .. m-1``: each 1-D, integer, 1 .. ``block`` distinct markers."""
+def check_max_markers(max_markers, block):
+    """``max_markers`` as an int with ``block <= max_markers <= WIDE_MAX``."""
+    if isinstance(max_markers, bool) or not isinstance(max_markers, (int, np.integer)):
+        raise ValueError("max_markers must be None or an integer, got %r" % (max_markers,))
+    if not block <= max_markers <= WIDE_MAX:
+        raise ValueError("max_markers must lie in block .. %d = %d .. %d, got %d" % (WIDE_MAX, block, WIDE_MAX, max_markers))
+    return int(max_markers)
+
+
+def check_sets(sets, m, block, max_markers=None):
+    """``sets`` as a list of int64 index arrays into ``0 .. m-1``: each 1-D, integer, 1 .. ``block`` distinct markers.  With
+    ``max_markers`` (``block .. 4096``) a set holds up to that many, and the kept sub-blocks of the widest set must fit the
+    panel call: ``(B - 1) bp <= 4096`` with ``bp`` = ``block`` rounded up to 16 and ``B`` its number of sub-blocks."""
     if isinstance(sets, np.ndarray) and sets.dtype != object and sets.ndim != 2:
         raise ValueError("sets must be a sequence of 1-D integer arrays, one per set")
+    if max_markers is not None:
+        max_markers = check_max_markers(max_markers, block)
     out = []
     for i, s in enumerate(sets):
         idx = np.asarray(s)
@@ -280,10 +300,18 @@ def check_sets(sets, m, block):
             raise ValueError("set %d holds a marker index outside 0 .. %d" % (i, m - 1))
         if np.unique(idx).size != idx.size:
             raise ValueError("set %d holds a marker twice" % i)
-        if idx.size > block:
+        if max_markers is None and idx.size > block:
             raise ValueError("set %d has %d markers, more than one device block of %d: sets wider than a block are not "
                              "supported" % (i, idx.size, block))
+        if max_markers is not None and idx.size > max_markers:
+            raise ValueError("set %d has %d markers, more than max_markers = %d" % (i, idx.size, max_markers))
         out.append(idx)
+    if max_markers is not None and out:
+        i = int(np.argmax([s.size for s in out]))
+        bp, B = (block + 15) // 16 * 16, -(-out[i].size // block)
+        if (B - 1) * bp > PANEL_COLUMNS:
+            raise ValueError("set %d has %d markers: the %d sub-blocks of %d before its last one keep %d columns, %d each, more than "
+                             "the %d columns of a panel call" % (i, out[i].size, B - 1, block, (B - 1) * bp, bp, PANEL_COLUMNS))
     return out
 
 
@@ -327,6 +355,43 @@ def pack_sets(sizes, block):
     return blocks
 
 
+def plan_sets(sizes, block):
+    """The device work for sets of ``sizes`` markers where some may be wider than ``block`` (``max_markers``): a list of lists of
+    set numbers in the order they run.  The sets of at most ``block`` markers are packed by ``pack_sets`` as if the wider ones
+    were not in the list -- the blocks of a call on them alone -- and a block runs where its first set stands; a wider set is a
+    list of its own, in its position."""
+    narrow = [i for i, k in enumerate(sizes) if int(k) <= block]
+    work = [[narrow[j] for j in b] for b in pack_sets([sizes[i] for i in narrow], block)]
+    work += [[i] for i, k in enumerate(sizes) if int(k) > block]
+    return sorted(work, key=lambda members: members[0])
+
+
+def assemble_wide(stats_blocks, gram_blocks, cross_blocks, bp):
+    """``((c + 5) x k statistics, k x k X'X)`` of one set of k markers run as B sub-blocks: ``stats_blocks[b]`` ((c + 5) x r_b) and
+    ``gram_blocks[b]`` (r_b x r_b) are what sub-block b's Gram call returned, ``cross_blocks[b - 1]`` (r_b x b ``bp``, b = 1 .. B - 1)
+    is ``X_b' [X_0 .. X_(b-1)]`` as ``scan_panel_dev`` formed it against the kept sub-blocks, each of them ``bp`` columns wide of
+    which the first ``block`` = r_0 are markers and the rest padding.  Every sub-block but the last holds ``block`` markers.  A
+    cross block is computed once and written twice, as it stands and transposed: the matrix is symmetric bit for bit where
+    the Gram blocks are."""
+    B = len(stats_blocks)
+    block = stats_blocks[0].shape[1]
+    if B < 1 or len(gram_blocks) != B or len(cross_blocks) != B - 1 or block > bp:
+        raise ValueError("%d sub-blocks need %d Gram blocks and %d cross blocks, and bp >= %d" % (B, B, B - 1, block))
+    if any(S.shape[1] != block for S in stats_blocks[:-1]) or not 1 <= stats_blocks[-1].shape[1] <= block:
+        raise ValueError("every sub-block but the last holds %d markers, the last 1 .. %d" % (block, block))
+    S = np.concatenate(stats_blocks, axis=1)
+    k = S.shape[1]
+    G = np.empty((k, k))
+    for b in range(B):
+        r0, rb = b * block, stats_blocks[b].shape[1]
+        G[r0:r0 + rb, r0:r0 + rb] = np.asarray(gram_blocks[b]).reshape(rb, rb)
+        if b:
+            X = np.asarray(cross_blocks[b - 1]).reshape(rb, b, bp)[:, :, :block].reshape(rb, r0)
+            G[r0:r0 + rb, :r0] = X
+            G[:r0, r0:r0 + rb] = X.T
+    return S, G
+
+
 def set_kernel(S, G, R, u, weights):
     """``(s, K, w, keep)`` of one set from its columns ``S`` of a block's statistics ((c + 5) x r) and its sub-block ``G`` of X'X,
     with the model's ``R`` and ``u``: the markers with an observed value and with variation are kept, ``z = R^-T S[4:4+c]``,
@@ -353,7 +418,7 @@ class VariantSetTest(AssociationScan):
     ``AssociationScan``'s; ``block`` bounds the markers of a set as well as of a device block."""
 
     def __call__(self, genotypes, sets, weights="beta", method="saddlepoint", return_kernel=False, skato=False, rho=None,
-                 finish="host"):
+                 finish="host", max_markers=None):
         """``genotypes``: m x n int8 as ``AssociationScan`` takes them; ``sets``: a sequence of 1-D integer arrays, the marker
         rows of each set (1 .. ``block`` distinct rows; a marker may belong to several sets); ``weights``: "beta" =
         Beta(1, 25) density at the marker's minor allele frequency, None = ones, or a sequence of arrays aligned with
@@ -367,28 +432,43 @@ class VariantSetTest(AssociationScan):
         (n_sets x n_rho), the per-rho tails by ``method``.  ``finish="device"`` does everything after the Gram block on the
         device (``scilmm_sets_finish_dev``) and brings back the sets' numbers alone; it excludes ``return_kernel``, and its
         p-values agree with the host's to 1e-6 relative, not bit for bit.  With the three at their defaults the call is what it
-        was: the same keys, the same bits."""
-        return self._run(Int8Rows(self, check_genotypes(genotypes, self.n)), sets, weights, method, return_kernel, skato, rho, finish)
+        was: the same keys, the same bits.
+
+        ``max_markers`` (None, or an integer in ``block`` .. 4096) lifts the bound on a set from ``block`` to that many
+        markers.  The sets of at most ``block`` markers are packed and run as without it -- the blocks of a call on them alone,
+        the same bits.  A wider set runs on its own, in its position in the list, as ``ceil(k / block)`` sub-blocks of its markers
+        in the order given: every sub-block is an ordinary Gram block, its forward solution is kept on the device
+        (``scilmm_scan_block_keep_dev``), and the sub-blocks behind it form their cross products against what is kept
+        (``scilmm_scan_panel_dev``), so ``K`` is the whole k x k matrix, symmetric bit for bit, and everything after it -- the
+        weights, burden, SKAT, ``skato``, ``return_kernel`` -- is what a narrow set gets.  With bp = ``block`` rounded up to 16 and
+        B the sub-blocks of the widest set, ``(B - 1) bp`` may not exceed 4096, the columns of a panel call.  The kept
+        solutions are ONE device allocation of n x (B - 1) bp doubles for the widest set of the call, dropped on return: 597 MB
+        at n = 83 320 and 1 024 markers, 5.9 GB at a cohort of 1M (both at ``block`` = 128).  The host algebra grows as k^3: expect
+        it to take longer than the device work of a wide set, SKAT-O above all.  ``finish="device"``
+        excludes a set wider than ``block``: the device finish holds one block in LDS."""
+        return self._run(Int8Rows(self, check_genotypes(genotypes, self.n)), sets, weights, method, return_kernel, skato, rho, finish,
+                         max_markers=max_markers)
 
     def test_bed(self, bed, sets, sample_index=None, count="A1", chunk_bytes=None, weights="beta", method="saddlepoint",
-                 return_kernel=False, skato=False, rho=None, finish="host"):
+                 return_kernel=False, skato=False, rho=None, finish="host", max_markers=None):
         """``__call__`` on the markers of a PLINK 1 fileset, decoded on the device (``scilmm_scan_block_bed_gram_dev``):
         ``sets`` index the file's markers; ``bed``, ``sample_index`` and ``count`` as for ``AssociationScan.scan_bed``.  A
         block's packed rows are uploaded as they lie in the file, so ``chunk_bytes`` has nothing to bound and is accepted
         for symmetry only.  Returns the bits of ``__call__`` on ``bed.read(None, sample_index, count)`` in deterministic
-        mode.  ``skato``, ``rho``, ``finish``: as for ``__call__``."""
+        mode.  ``skato``, ``rho``, ``finish``, ``max_markers``: as for ``__call__``."""
         src = self._bed_source(bed, sample_index, count)
         if chunk_bytes is not None and int(chunk_bytes) < 1:
             raise ValueError("chunk_bytes must be positive")
-        return self._run(src, sets, weights, method, return_kernel, skato, rho, finish)
+        return self._run(src, sets, weights, method, return_kernel, skato, rho, finish, max_markers=max_markers)
 
     def test_dosages(self, dosages, sets, sample_index=None, weights="beta", method="saddlepoint", return_kernel=False, skato=False,
-                     rho=None, finish="host"):
+                     rho=None, finish="host", max_markers=None):
         """``__call__`` on imputed dosages (``scilmm_scan_block_dosage_gram_dev``): ``sets`` index the rows of ``dosages``;
         ``dosages`` and ``sample_index`` as for ``AssociationScan.scan_dosages``.  The "beta" weights take half the mean
         dosage for the allele frequency.  For uint16 codes of hard calls it returns the bits of ``__call__`` on the int8
-        markers in deterministic mode.  ``skato``, ``rho``, ``finish``: as for ``__call__``."""
-        return self._run(self._dosage_source(dosages, sample_index), sets, weights, method, return_kernel, skato, rho, finish)
+        markers in deterministic mode.  ``skato``, ``rho``, ``finish``, ``max_markers``: as for ``__call__``."""
+        return self._run(self._dosage_source(dosages, sample_index), sets, weights, method, return_kernel, skato, rho, finish,
+                         max_markers=max_markers)
 
     def _block(self, src):
         """rows -> ((q + 4) x r statistics, r x r Gram matrix) of one block of the marker source ``src``, on the host: the rows
@@ -404,6 +484,45 @@ class VariantSetTest(AssociationScan):
             src.enqueue(0, rb, C.c_void_p(dS.data_ptr()), C.c_void_p(dK.data_ptr()))
             self.sym.sync()
             return dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb), dK[:rb * rb].cpu().numpy().reshape(rb, rb)
+        return run
+
+    def _block_wide(self, src, bmax, staged):
+        """rows (more than ``block`` of them) -> ((q + 4) x k statistics, k x k X'X) of one set of up to ``bmax`` sub-blocks, on the
+        host.  Sub-block b holds rows ``[b block, (b + 1) block)`` in the order given and is run as any block is: its rows are
+        brought to the device and the form's Gram entry point gives its statistics and its diagonal block of X'X.  Behind it,
+        on the stream, ``scan_panel_dev`` forms its cross block against the ``b bp`` columns kept so far (b > 0) and
+        ``scan_block_keep_dev`` puts its forward solution behind them (b < B - 1); one wait per sub-block, then the copies of
+        what it returned.  ``assemble_wide`` puts the pieces together.  The store is ONE allocation, n x (``bmax`` - 1) bp
+        doubles (bp = ``block`` rounded up to 16), shared by the wide sets of a call and dropped with this closure."""
+        torch, q, blk = self.torch, self.q, self.block
+        bp = (blk + 15) // 16 * 16
+        ld = (bmax - 1) * bp
+        if not staged:
+            src.stage(blk)
+        vp = C.c_void_p
+        dS = torch.empty(((q + 4) * blk,), dtype=torch.float64, device="cuda")
+        dK = torch.empty((blk * blk,), dtype=torch.float64, device="cuda")
+        dX = torch.empty((blk * ld,), dtype=torch.float64, device="cuda")
+        store = torch.empty((self.n * ld,), dtype=torch.float64, device="cuda")
+
+        def run(rows):
+            B = -(-rows.size // blk)
+            Ss, Gs, Xs = [], [], []
+            for b in range(B):
+                sub = rows[b * blk:(b + 1) * blk]
+                rb, t = sub.size, b * bp
+                src.load(sub)
+                src.enqueue(0, rb, vp(dS.data_ptr()), vp(dK.data_ptr()))
+                if b > 0:
+                    self.factor.scan_panel_dev(rb, vp(store.data_ptr()), ld, t, vp(dX.data_ptr()), t)
+                if b < B - 1:
+                    self.factor.scan_block_keep_dev(rb, vp(store.data_ptr()), ld, t)
+                self.sym.sync()
+                Ss.append(dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb))
+                Gs.append(dK[:rb * rb].cpu().numpy().reshape(rb, rb))
+                if b > 0:
+                    Xs.append(dX[:rb * t].cpu().numpy().reshape(rb, t))
+            return assemble_wide(Ss, Gs, Xs, bp)
         return run
 
     def _block_device(self, src, mode, method, rho):
@@ -434,16 +553,22 @@ class VariantSetTest(AssociationScan):
             return dO[:ns * ld].cpu().numpy().reshape(ns, ld)
         return run
 
-    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host"):
+    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host", max_markers=None):
         """The checks of the sets (before any launch), then block by block: gather the block's marker rows, one device call, the
         statistics and the Gram matrix (``_block``), the host algebra set by set -- or, with ``finish="device"``, the finish
-        queued behind the block and the sets' rows alone brought back (``_block_device``)."""
-        sets = check_sets(sets, src.m, self.block)
+        queued behind the block and the sets' rows alone brought back (``_block_device``).  With ``max_markers`` a set wider than
+        a block runs on its own, sub-block by sub-block (``_block_wide``), and meets the same host algebra."""
+        sets = check_sets(sets, src.m, self.block, max_markers)
         weights, sf = check_weights(weights, sets), check_method(method)
         if finish not in FINISHES:
             raise ValueError("finish must be one of %s, got %r" % (", ".join(FINISHES), finish))
         if finish == "device" and return_kernel:
             raise ValueError('return_kernel=True needs finish="host": the device finish does not bring K back')
+        sizes = [s.size for s in sets]
+        widest = max(sizes + [0])
+        if finish == "device" and widest > self.block:
+            raise ValueError('a set of %d markers needs finish="host": the device finish holds one block of at most %d markers in LDS'
+                             % (widest, self.block))
         rho = check_rho(rho) if skato else None
         self._check_factor()
         ns = len(sets)
@@ -452,7 +577,7 @@ class VariantSetTest(AssociationScan):
         if skato:
             out.update({k: np.full(ns, np.nan) for k in SKATO_KEYS[:3]})
             out["skato_p_rho"] = np.full((ns, rho.size), np.nan)
-        packed = pack_sets([s.size for s in sets], self.block)
+        packed = pack_sets(sizes, self.block) if widest <= self.block else plan_sets(sizes, self.block)
         if finish == "device":
             given = not (weights is None or isinstance(weights, str))
             mode = WEIGHT_GIVEN if given else WEIGHT_ONES if weights is None else WEIGHT_BETA
@@ -472,9 +597,17 @@ class VariantSetTest(AssociationScan):
             used = out["n_used"] > 0
             out["burden_p"][used] = self._f.sf(out["burden_chi2"][used])     # (one vectorised call over the sets)
             return out
-        block = self._block(src) if sets else None
+        narrow = any(s.size <= self.block for s in sets)
+        block = self._block(src) if narrow else None
+        wide = self._block_wide(src, -(-widest // self.block), narrow) if widest > self.block else None
         kernel = [None] * ns
         for members in packed:
+            if sets[members[0]].size > self.block:
+                i = members[0]
+                S, G = wide(sets[i])
+                w = weights if weights is None or isinstance(weights, str) else weights[i]
+                kernel[i] = self._one_set(out, i, S, G, w, sf, rho, method)
+                continue
             S, G = block(np.concatenate([sets[i] for i in members]))
             a = 0
             for i in members:

@@ -18,7 +18,15 @@ call with finish="device" and finish="host", with and without skato, on the same
 (scilmm_amd.glmm.BinarySetTest, finish="device"): the Gram block, k_scan_spa of its markers, k_sets_spa and the scaled
 k_sets_finish with SKAT-O, each by its own HIP events, at a null point of a simulated 5 % phenotype, at the default cutoff 2 and
 at cutoff 0 (every marker and every burden saddlepointed: the most the block can cost); next to it, in the same run and on the
-same sets, the quantitative Gram block + k_sets_finish, and the ratio of the two totals."""
+same sets, the quantitative Gram block + k_sets_finish, and the ratio of the two totals.
+  usage: sets_timing.py 100k --wide 256,1024 [--out profiles/sets_wide_100k.json]
+--wide times one set of k rare markers per width as VariantSetTest(..., max_markers=k) queues it, sub-block by sub-block: the Gram
+blocks (sweeps with statistics and Gram, scilmm_scan_timing) and the panels (scilmm_panel_timing) by their HIP events, the
+keeps as the wall time of 20 keeps queued behind one block over 20 (k_scan_keep has no events of its own); the same markers as
+ceil(k / 128) separate 128-marker sets without max_markers (the Gram blocks alone), in alternating rounds of the same run; the
+ratio of the two device times; the panel of the last block against its own kept copy next to its Gram matrix; the host finish
+of the assembled set with and without SKAT-O, and the wall time of the whole call.  One warm-up round, then --blocks rounds (use
+--blocks 5)."""
 import argparse, ctypes, json, os, sys
 import numpy as np
 import scipy.sparse as sp
@@ -29,6 +37,7 @@ ap.add_argument("workload"); ap.add_argument("--blocks", type=int, default=20); 
 ap.add_argument("--shapes", default=None)
 ap.add_argument("--finish", action="store_true")
 ap.add_argument("--binary", action="store_true")
+ap.add_argument("--wide", default=None)
 args = ap.parse_args()
 import torch
 from scilmm_amd import SparseCholesky, VariantSetTest
@@ -163,8 +172,87 @@ def binary_leg():
     return rec
 
 
-if args.finish or args.binary:
-    rec = binary_leg() if args.binary else finish_leg()
+def wide_leg(widths):
+    import time
+    from scilmm_amd import sets as mod
+    bp = R
+    rec = {"workload": args.workload, "n": int(n), "block": R, "widths": {},
+           "timer": "HIP events of the Gram blocks and the panels, one sub-block per synchronise; keeps: wall time of 20 queued keeps / 20; "
+                    "one warm-up round, then %d alternating rounds of the wide set and of its sub-blocks as separate sets" % args.blocks}
+    for k in widths:
+        B = -(-k // R)
+        ldw = (B - 1) * bp
+        Gm = rng.binomial(2, rng.uniform(0.005, 0.05, k)[:, None], size=(k, n)).astype(np.int8)
+        Gm[rng.random(Gm.shape) < 0.02] = -1
+        store = torch.empty((n * ldw,), dtype=torch.float64, device="cuda")
+        dX = torch.empty((R * ldw,), dtype=torch.float64, device="cuda")
+        pS, pK, pQ = vp(dS.data_ptr()), vp(dK.data_ptr()), vp(tester.dQ.data_ptr())
+
+        def load(b):
+            sub = np.ascontiguousarray(Gm[b * R:(b + 1) * R])
+            dG[:sub.shape[0], :n].copy_(torch.from_numpy(sub))
+            torch.cuda.synchronize()
+            return sub.shape[0]
+
+        t_wide, t_base, Ss, Gs, Xs = [], [], [], [], []
+        for it in range(1 + args.blocks):
+            gram_ms = panel_ms = 0.0
+            for b in range(B):                                   # the wide set, as VariantSetTest._block_wide queues it
+                rb = load(b)
+                fac.scan_block_gram_dev(vp(dG.data_ptr()), ld, rb, pQ, q, pS, pK)
+                if b > 0: fac.scan_panel_dev(rb, vp(store.data_ptr()), ldw, b * bp, vp(dX.data_ptr()), b * bp)
+                if b < B - 1: fac.scan_block_keep_dev(rb, vp(store.data_ptr()), ldw, b * bp)
+                sym.sync()
+                gram_ms += float(sum(sym.scan_timing()))
+                if b > 0: panel_ms += float(sum(sym.panel_timing()))
+                if it == 0:
+                    Ss.append(dS[:(q + 4) * rb].cpu().numpy().reshape(q + 4, rb)); Gs.append(dK[:rb * rb].cpu().numpy().reshape(rb, rb))
+                    if b > 0: Xs.append(dX[:rb * b * bp].cpu().numpy().reshape(rb, b * bp))
+            base_ms = 0.0
+            for b in range(B):                                   # the same markers as separate sets: the Gram blocks alone
+                rb = load(b)
+                fac.scan_block_gram_dev(vp(dG.data_ptr()), ld, rb, pQ, q, pS, pK); sym.sync()
+                base_ms += float(sum(sym.scan_timing()))
+            if it >= 1:
+                t_wide.append((gram_ms, panel_ms)); t_base.append(base_ms)
+        keeps = []
+        for it in range(4):                                      # the last block is still in X: 20 keeps of it behind each other
+            sym.sync(); t0 = time.perf_counter()
+            for _ in range(20): fac.scan_block_keep_dev(rb, vp(store.data_ptr()), ldw, 0)
+            sym.sync(); keeps.append(1e3 * (time.perf_counter() - t0) / 20)
+        keep_ms = float(np.median(keeps[1:])) * (B - 1)
+        tp = (rb + 15) // 16 * 16                                # the block against its own kept copy: its Gram matrix again
+        fac.scan_panel_dev(rb, vp(store.data_ptr()), ldw, tp, vp(dX.data_ptr()), tp); sym.sync()
+        own = dX[:rb * tp].cpu().numpy().reshape(rb, tp)[:, :rb]
+        Kb = dK[:rb * rb].cpu().numpy().reshape(rb, rb)
+        own_err = float(np.abs(own - Kb).max() / np.abs(Kb).max())
+        a = np.asarray(t_wide)
+        wide_ms = float(np.median(a.sum(axis=1))) + keep_ms
+        S, K = mod.assemble_wide(Ss, Gs, Xs, bp)
+        host = {}
+        for key, grid in (("burden_skat", None), ("skato", mod.check_rho(None))):
+            out = {kk: np.full(1, np.nan) for kk in mod.KEYS + mod.SKATO_KEYS[:3]}
+            out["n_used"] = np.zeros(1, dtype=np.int64); out["skato_p_rho"] = np.full((1, len(mod.RHO_DEFAULT)), np.nan)
+            t0 = time.perf_counter()
+            tester._one_set(out, 0, S, K, "beta", mod.mixture_sf_saddlepoint, grid, "saddlepoint")
+            host[key + "_ms"] = 1e3 * (time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        tester(Gm, [np.arange(k)], max_markers=k)
+        call_ms = 1e3 * (time.perf_counter() - t0)
+        rec["widths"][str(k)] = {
+            "sub_blocks": B, "store_bytes": int(n) * ldw * 8,
+            "wide_device_ms": {"sweeps_with_gram": summary(a[:, 0]), "panels": summary(a[:, 1]), "keeps": keep_ms,
+                               "keep_ms_each_of_20_queued": summary(keeps[1:]), "total": wide_ms},
+            "separate_sets_device_ms": summary(t_base), "wide_over_separate": wide_ms / float(np.median(t_base)),
+            "host_finish_ms": host, "host_share_burden_skat": host["burden_skat_ms"] / (host["burden_skat_ms"] + wide_ms),
+            "host_share_skato": host["skato_ms"] / (host["skato_ms"] + wide_ms), "whole_call_wall_ms": call_ms,
+            "symmetric_bits": bool(np.array_equal(K, K.T)), "panel_of_kept_copy_vs_gram_rel_err": own_err}
+        del store, dX
+    return rec
+
+
+if args.finish or args.binary or args.wide:
+    rec = wide_leg([int(v) for v in args.wide.split(",")]) if args.wide else binary_leg() if args.binary else finish_leg()
     print(json.dumps(rec))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
