@@ -477,6 +477,40 @@ int scilmm_sets_finish_dev(scilmm_factor* fac, int32_t r, int32_t q, const doubl
  * it: ms[0] k_sets_finish (tools/sets_timing.py --finish).  No counterpart in the reference. */
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms);
 
+/* The finish of ONE variant set of k markers, 1 <= k <= 4 096, that ran as B = ceil(k / block) sub-blocks (DESIGN.md section
+ * 22), queued on the handle's stream behind the last of them; everything scilmm_sets_finish_dev computes for a set, for a set
+ * wider than one block.  With bp = block rounded up to 16: (B - 1) bp <= 4 096.
+ *   block  : 1 .. 128, the markers of every sub-block but the last; sub-block b holds r_b = min(block, k - b block).
+ *   d_stats: B slices at a stride of (q + 4) block doubles; slice b is the (q + 4) x r_b array scilmm_scan_block_gram_dev (or a
+ *            twin) wrote for sub-block b.   d_gram: B slices at a stride of block^2; slice b is r_b x r_b.
+ *   d_cross: row i (the marker's index in the set) holds the b bp columns scilmm_scan_panel_dev wrote for it, b = i / block:
+ *            column a bp + j is marker a block + j, the padding columns are not read; ld_cross >= (B - 1) bp doubles between
+ *            rows.  Null exactly when B = 1.
+ *   d_R, d_u, c, q = c + 1, weight_mode, method, rho, n_rho: as for scilmm_sets_finish_dev; d_weights: k doubles, one per marker
+ *            of the set (mode 2).  rho is a HOST array, read before the call returns.
+ *   d_out  : ONE row of 10 + n_rho doubles in the layout of scilmm_sets_finish_dev.  flags: bit 0 the degenerate rule, bit 1 a
+ *            bisection ran out of steps, bit 2 a root of a tail ran out of steps, bit 3 SKAT-O was computed.
+ *   d_lam  : null, or k doubles: the eigenvalues of A = diag(w) K diag(w) in descending order (one per kept marker), then NaN.
+ * A is reduced once to a tridiagonal T whose first basis vector is 1 / sqrt(m) (a Householder pre-step, then m - 1 steps of two
+ * launches each on the m x m matrix in HBM); the spectra of A, of every A R_rho and of the remainder B are eigenvalues of
+ * rescaled T, found by bisection; the tails and the integral follow scilmm_sets_finish_dev's.  The work space (k^2 + 92 k doubles)
+ * is the handle's: grown for a wider set behind a stream synchronise, never allocated again for the same or a narrower one.
+ * No atomics, fixed reduction orders: the row depends on the set's inputs alone, and scilmm_timing.n_float_atomic_launches is
+ * not touched.  Enqueued without synchronising; nothing of the factor is read.  SCILMM_ERR_ARG before anything of the handle or
+ * the device is read: a null fac, d_stats, d_gram, d_R, d_u or d_out (rho with n_rho > 0, d_weights in mode 2), k outside
+ * 1 .. 4 096, block outside 1 .. 128, (B - 1) bp > 4 096, d_cross null with B > 1 or not null with B = 1, ld_cross < (B - 1) bp,
+ * c outside 1 .. 31, q != c + 1, n_rho outside 0 .. 16, a rho outside [0, 1] or NaN, an unknown weight mode or method.  Refusals as
+ * for scilmm_sets_finish_dev.  scilmm_amd.VariantSetTest with finish="wide" is the interface.  No counterpart in the reference. */
+int scilmm_sets_finish_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
+                                const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, int32_t c,
+                                int32_t weight_mode, const double* d_weights, int32_t method, const double* rho, int32_t n_rho,
+                                double* d_out, double* d_lam);
+
+/* HIP-event times of the last scilmm_sets_finish_wide_dev on the handle, in milliseconds, valid after the scilmm_sync that
+ * follows it: ms[0] prep + form, ms[1] the reduction, ms[2] the eigenvalues, ms[3] the tails (tools/sets_timing.py
+ * --wide-finish).  No counterpart in the reference. */
+int scilmm_sets_finish_wide_timing(const scilmm_symbolic* sym, double* ms);
+
 /* scilmm_sets_finish_dev with a variance scale per column of the block: in A alone a column's weight is multiplied by its
  * scale, A = diag(w o scale) K diag(w o scale), while t = w o s keeps w; everything else -- arguments, checks, refusals, the
  * layout of a row -- is scilmm_sets_finish_dev's (burden_chi2 = (1't)^2 / 1'A1 is then a chi-square with ONE degree of freedom

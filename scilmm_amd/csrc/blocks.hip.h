@@ -349,6 +349,81 @@ int sets_finish(scilmm_factor* fac, const FinishArgs& a, const char* who) {
   return SCILMM_OK;
 }
 
+// What scilmm_sets_finish_wide_dev takes beside the factor.
+struct WideArgs {
+  int32_t k, block, q;
+  const double *d_stats, *d_gram, *d_cross;
+  int64_t ld_cross;
+  const double *d_R, *d_u;
+  int32_t c, weight_mode;
+  const double* d_weights;
+  int32_t method;
+  const double* rho;
+  int32_t n_rho;
+  double *d_out, *d_lam;
+  int32_t bp() const { return (block + 15) / 16 * 16; }
+  int32_t nsub() const { return (k + block - 1) / block; }
+  // before anything of the handle is read; the grid is a HOST array and is read here (a NaN fails its comparison)
+  static bool args_ok(const scilmm_factor* fac, const WideArgs& a) {
+    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.d_out || a.k < 1 || a.k > WIDE_KMAX || a.block < 1 || a.block > RPMAX ||
+        a.c < 1 || a.c > FIN_CMAX || a.q != a.c + 1 || a.n_rho < 0 || a.n_rho > FIN_RHO_MAX || (a.n_rho > 0 && !a.rho) ||
+        (a.method != FIN_SADDLE && a.method != FIN_LIU) ||
+        (a.weight_mode != FIN_BETA && a.weight_mode != FIN_ONES && a.weight_mode != FIN_GIVEN) || (a.weight_mode == FIN_GIVEN && !a.d_weights))
+      return false;
+    const int64_t kept = (int64_t)(a.nsub() - 1) * a.bp();    // the columns of the cross store
+    if (kept > WIDE_KMAX || (a.nsub() == 1) != (a.d_cross == nullptr) || (a.nsub() > 1 && a.ld_cross < kept)) return false;
+    for (int32_t j = 0; j < a.n_rho; ++j)
+      if (!(a.rho[j] >= 0.0 && a.rho[j] <= 1.0)) return false;
+    return fac->sym && fac->sym->S;  // (what needs no handle has been checked: with it wrong, nothing of the handle is read)
+  }
+};
+
+// Everything after the sub-blocks of ONE set of up to 4 096 markers (scilmm_sets_finish_wide_dev; setwide.hip.h, DESIGN.md section
+// 22): the refusals of sets_finish, the work space (grown for a wider set only: the stream is synchronised first, and nothing is
+// allocated afterwards for the same or a narrower set), then plain launches between the call's own events -- prep, form, burden |
+// the pre-step and k - 1 steps of the reduction, two launches each, sized by k (the number of kept markers is the device's) |
+// scale, eig | tails.  Nothing of the factor is read and nothing of the work buffers is touched.
+int sets_finish_wide(scilmm_factor* fac, const WideArgs& a, const char* who) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const int32_t k = a.k;
+  const size_t need = wide_doubles((size_t)k);
+  if (D->wide_ws_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  TRY(grow(sym, &D->wide_ws, &D->wide_ws_cap, need));
+  if (!D->wide_ev[0])
+    for (auto& e : D->wide_ev) HIPCHK(hipEventCreate(&e));
+  const WideWs ws = wide_cut(D->wide_ws, (size_t)k);
+  const WideIn in{k, a.block, a.bp(), a.q, a.d_stats, a.d_gram, a.d_cross, a.ld_cross};
+  WideRho grid{};
+  for (int32_t j = 0; j < a.n_rho; ++j) grid.rho[j] = a.rho[j];
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->wide_ev[0], s0));
+  hipLaunchKernelGGL(k_wide_prep, dim3(1), dim3(WIDE_PREP_NT), 0, s0, in, a.c, a.d_R, a.d_u, a.weight_mode, a.d_weights, ws, a.n_rho, a.d_out,
+                     a.d_lam);
+  hipLaunchKernelGGL(k_wide_form, dim3((unsigned)k), dim3(256), 0, s0, in, a.c, ws);
+  hipLaunchKernelGGL(k_wide_burden, dim3(1), dim3(256), 0, s0, ws, a.d_out);
+  HIPCHK(hipEventRecord(D->wide_ev[1], s0));
+  // step j works on the trailing matrix of order at most k - 1 - j; the last one (order 1) only stores d and e, as does "step"
+  // k - 1, which has nothing behind it but the last diagonal entry
+  for (int32_t j = -1; j < k; ++j) {
+    const unsigned wgs = (unsigned)std::max(1, (k - 1 - j + WIDE_ROWS - 1) / WIDE_ROWS);
+    hipLaunchKernelGGL(k_wide_symv, dim3(wgs), dim3(256), 0, s0, j, ws);
+    if (k - 1 - j >= 2 || j < 0) hipLaunchKernelGGL(k_wide_rank2, dim3(wgs), dim3(256), 0, s0, j, ws);
+  }
+  HIPCHK(hipEventRecord(D->wide_ev[2], s0));
+  hipLaunchKernelGGL(k_wide_scale, dim3((unsigned)(a.n_rho + 2)), dim3(256), 0, s0, k, a.n_rho, grid, ws);
+  hipLaunchKernelGGL(k_wide_eig, dim3((unsigned)((k + 63) / 64), (unsigned)(a.n_rho + 2)), dim3(64), 0, s0, k, ws, a.d_lam);
+  HIPCHK(hipEventRecord(D->wide_ev[3], s0));
+  hipLaunchKernelGGL(k_wide_tails, dim3(1), dim3(256), 0, s0, k, a.n_rho, grid, a.method, ws, a.d_out);
+  HIPCHK(hipEventRecord(D->wide_ev[4], s0));
+  D->wide_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
 // What the three set SPA entry points take beside their form's marker arguments and the common part of the marker calls
 // (scilmm_sets_spa*_dev): the Gram matrix, the markers' saddlepoint rows, the sets and the two outputs.
 struct SetSpaArgs {

@@ -345,6 +345,12 @@ struct Dev {
   hipEvent_t sspa_ev[2] = {nullptr, nullptr};  // k_sets_spa begin | done (the first set SPA call creates them)
   bool sspa_pending = false;            // a set SPA call whose events have not been read yet (scilmm_sync)
   double sspa_ms = 0.0;                 // the last call's k_sets_spa (scilmm_sets_spa_timing)
+  // the finish of a wide set (scilmm_sets_finish_wide_dev): the m x m matrix, the vectors and the spectra (WideWs, setwide.hip.h)
+  double* wide_ws = nullptr;            // grown for the widest set seen, behind a stream synchronise; nothing is allocated afterwards
+  size_t wide_ws_cap = 0;               // doubles
+  hipEvent_t wide_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // begin | A formed | reduced | spectra | tails done
+  bool wide_pending = false;            // a wide finish whose events have not been read yet (scilmm_sync)
+  double wide_ms[4] = {0.0, 0.0, 0.0, 0.0};  // the last call's prep + form | reduction | eigenvalues | tails (scilmm_sets_finish_wide_timing)
   void clear_block() { block_r = block_rp = 0; }
 };
 

@@ -1,9 +1,9 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setfinish.hip.h, setspa.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setfinish.hip.h, setwide.hip.h, setspa.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_spa, rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_wide, sets_spa, rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
@@ -37,6 +37,7 @@
 #include "dosage.hip.h"
 #include "spa.hip.h"
 #include "setfinish.hip.h"
+#include "setwide.hip.h"
 #include "setspa.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
@@ -377,6 +378,16 @@ int scilmm_sets_finish_scaled_dev(scilmm_factor* fac, int32_t r, int32_t q, cons
   return sets_finish(fac, a, __func__);
 }
 
+// The finish of ONE set of up to 4 096 markers behind its sub-blocks: a pure function of what they left behind
+int scilmm_sets_finish_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
+                                const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, int32_t c,
+                                int32_t weight_mode, const double* d_weights, int32_t method, const double* rho, int32_t n_rho,
+                                double* d_out, double* d_lam) {
+  const WideArgs a{k, block, q, d_stats, d_gram, d_cross, ld_cross, d_R, d_u, c, weight_mode, d_weights, method, rho, n_rho, d_out, d_lam};
+  if (!WideArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_finish_wide(fac, a, __func__);
+}
+
 // The sets' variance scales and burden saddlepoint p-values behind a Gram block and its markers' saddlepoint call: the form's
 // marker arguments are checked as its scan_spa twin checks them
 int scilmm_sets_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_gram,
@@ -629,6 +640,14 @@ int scilmm_sync(scilmm_symbolic* sym) {
     HIPCHK(hipEventElapsedTime(&a, D->fin_ev[0], D->fin_ev[1]));
     D->fin_ms = a;
   }
+  if (D->wide_pending) {
+    D->wide_pending = false;
+    for (int i = 0; i < 4; ++i) {
+      float a = 0;
+      HIPCHK(hipEventElapsedTime(&a, D->wide_ev[i], D->wide_ev[i + 1]));
+      D->wide_ms[i] = a;
+    }
+  }
   if (D->sspa_pending) {
     D->sspa_pending = false;
     float a = 0;
@@ -685,6 +704,13 @@ int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms) {
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   ms[0] = ((const Dev*)sym->device)->fin_ms;
+  return SCILMM_OK;
+}
+
+int scilmm_sets_finish_wide_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const Dev* D = (const Dev*)sym->device;
+  for (int i = 0; i < 4; ++i) ms[i] = D->wide_ms[i];
   return SCILMM_OK;
 }
 

@@ -36,6 +36,9 @@ void dev_free(void* p) {
   if (D->gram_partial) (void)hipFree(D->gram_partial);
   if (D->panel_partial) (void)hipFree(D->panel_partial);
   if (D->spa_scratch) (void)hipFree(D->spa_scratch);
+  if (D->wide_ws) (void)hipFree(D->wide_ws);
+  for (auto& e : D->wide_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->spa_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->fin_ev)

@@ -283,6 +283,12 @@ class Symbolic(object):
         check(lib().scilmm_sets_finish_timing(self._h, ms), self._h)
         return float(ms[0])
 
+    def sets_finish_wide_timing(self):
+        """(prep + form, reduction, eigenvalues, tails) of the last ``Factor.sets_finish_wide_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 4)()
+        check(lib().scilmm_sets_finish_wide_timing(self._h, ms), self._h)
+        return tuple(float(v) for v in ms)
+
     def sets_spa_timing(self):
         """``k_sets_spa`` of the last ``Factor.sets_spa*_dev`` in ms, after ``sync()``."""
         ms = (C.c_double * 1)()
@@ -516,6 +522,17 @@ class Factor(object):
         rho = np.ascontiguousarray(rho, dtype=np.float64)
         check(lib().scilmm_sets_finish_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, ptr(set_start), weight_mode,
                                            dweights_ptr, method, ptr(rho), rho.size, dout_ptr, ld_out, dlam_ptr), self.sym._h)
+
+    def sets_finish_wide_dev(self, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr, c, weight_mode, dweights_ptr,
+                             method, rho, dout_ptr, dlam_ptr):
+        """Everything after the sub-blocks of ONE set of ``k`` <= 4096 markers (``scilmm_sets_finish_wide_dev``): the sub-blocks'
+        statistics at a stride of ``(q + 4) block`` doubles, their Gram blocks at a stride of ``block^2``, the rows of cross
+        products (``None`` for a set of one sub-block); ``rho`` (host float64, possibly empty: no SKAT-O) is read before the call
+        returns; one row of ``10 + len(rho)`` doubles goes to ``dout_ptr``; enqueues without synchronising
+        (``scilmm_amd.sets.VariantSetTest`` with ``finish="wide"`` is the interface)."""
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        check(lib().scilmm_sets_finish_wide_dev(self._h, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr, c,
+                                                weight_mode, dweights_ptr, method, ptr(rho), rho.size, dout_ptr, dlam_ptr), self.sym._h)
 
     def sets_finish_scaled_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method,
                                rho, dout_ptr, ld_out, dlam_ptr, dvscale_ptr):

@@ -36,7 +36,9 @@ alone stays on the host).  The two agree to the accuracy of the tails (1e-6 rela
 ``max_markers=k`` lets a set hold up to k <= 4096 markers instead of one block's: such a set runs as sub-blocks whose forward
 solutions are kept on the device (``scilmm_scan_block_keep_dev``) and whose cross products ``X_b' X_a`` come from
 ``scilmm_scan_panel_dev``; ``assemble_wide`` puts the k x k ``X'X`` together and the host algebra above takes over (DESIGN.md
-section 21).
+section 21).  ``finish="wide"`` is ``finish="device"`` for the sets of one block, and for a wider set it leaves the pieces on the
+device and queues ``scilmm_sets_finish_wide_dev`` behind the last sub-block: one tridiagonal reduction of ``A`` gives every
+spectrum SKAT-O needs, and one row of numbers comes back.
 """
 import ctypes as C
 
@@ -59,6 +61,7 @@ RHO_DEFAULT = (0.0, 0.01, 0.04, 0.09, 0.16, 0.25, 0.5, 1.0)
 RHO_MAX, RHO_CAP = 16, 0.999      # grid values at most; a value above RHO_CAP is computed as RHO_CAP (R_rho stays definite)
 Z_END = 40.0              # the SKAT-O integral stops here: 2 Phi(-40) is zero in double precision
 FINISHES = ("host", "device")
+FINISH_VALUES = FINISHES + ("wide",)     # what VariantSetTest takes: "wide" is the device finish that also takes a set wider than a block
 WEIGHT_BETA, WEIGHT_ONES, WEIGHT_GIVEN = 0, 1, 2       # weight modes of scilmm_sets_finish_dev
 FINISH_HEAD = 10          # doubles of a set's row before its per-rho p-values
 WIDE_MAX = 4096           # markers of a set at most, with max_markers
@@ -445,7 +448,13 @@ class VariantSetTest(AssociationScan):
         solutions are ONE device allocation of n x (B - 1) bp doubles for the widest set of the call, dropped on return: 597 MB
         at n = 83 320 and 1 024 markers, 5.9 GB at a cohort of 1M (both at ``block`` = 128).  The host algebra grows as k^3: expect
         it to take longer than the device work of a wide set, SKAT-O above all.  ``finish="device"``
-        excludes a set wider than ``block``: the device finish holds one block in LDS."""
+        excludes a set wider than ``block``: the device finish holds one block in LDS.
+
+        ``finish="wide"`` is the device finish for every width: a set of at most ``block`` markers runs exactly as under
+        ``finish="device"`` (the same packing, the same bits); a wider one (with ``max_markers``) runs sub-block by sub-block
+        as above, but its statistics, Gram blocks and cross products stay on the device, ``scilmm_sets_finish_wide_dev`` is
+        queued behind the last sub-block, and one row of numbers comes back.  It excludes ``return_kernel`` and agrees with the
+        host finish as ``finish="device"`` does."""
         return self._run(Int8Rows(self, check_genotypes(genotypes, self.n)), sets, weights, method, return_kernel, skato, rho, finish,
                          max_markers=max_markers)
 
@@ -525,6 +534,50 @@ class VariantSetTest(AssociationScan):
             return assemble_wide(Ss, Gs, Xs, bp)
         return run
 
+    def _block_wide_device(self, src, bmax, staged, mode, method, rho):
+        """(rows, weights) -> the row of ``scilmm_sets_finish_wide_dev`` (10 + n_rho doubles) of one set of more than ``block`` rows
+        and up to ``bmax`` sub-blocks, on the host.  The sub-blocks run as in ``_block_wide`` -- one wait each: the next one's rows
+        take the place of this one's -- but nothing of them is copied back: every Gram call writes its own slice of the
+        statistics and of the diagonal blocks, the panel call writes the sub-block's rows of the cross store.  The finish is
+        queued behind the last sub-block; one more wait, one copy of the row."""
+        torch, q, blk = self.torch, self.q, self.block
+        bp = (blk + 15) // 16 * 16
+        ld = (bmax - 1) * bp
+        if not staged:
+            src.stage(blk)
+        vp = C.c_void_p
+        dS = torch.empty((bmax * (q + 4) * blk,), dtype=torch.float64, device="cuda")
+        dK = torch.empty((bmax * blk * blk,), dtype=torch.float64, device="cuda")
+        dX = torch.empty((bmax * blk * ld,), dtype=torch.float64, device="cuda")
+        store = torch.empty((self.n * ld,), dtype=torch.float64, device="cuda")
+        dR = torch.from_numpy(np.ascontiguousarray(self.R)).cuda()
+        du = torch.from_numpy(np.ascontiguousarray(self.u)).cuda()
+        dW = torch.empty((bmax * blk,), dtype=torch.float64, device="cuda")
+        dO = torch.empty((FINISH_HEAD + rho.size,), dtype=torch.float64, device="cuda")
+        meth = METHODS.index(method)
+
+        def run(rows, w):
+            k = rows.size
+            B = -(-k // blk)
+            if w is not None:
+                dW[:k].copy_(torch.from_numpy(w))
+            for b in range(B):
+                sub = rows[b * blk:(b + 1) * blk]
+                rb, t = sub.size, b * bp
+                src.load(sub)
+                src.enqueue(0, rb, vp(dS.data_ptr() + 8 * b * (q + 4) * blk), vp(dK.data_ptr() + 8 * b * blk * blk))
+                if b > 0:
+                    self.factor.scan_panel_dev(rb, vp(store.data_ptr()), ld, t, vp(dX.data_ptr() + 8 * b * blk * ld), ld)
+                if b < B - 1:
+                    self.factor.scan_block_keep_dev(rb, vp(store.data_ptr()), ld, t)
+                self.sym.sync()
+            self.factor.sets_finish_wide_dev(k, blk, q, vp(dS.data_ptr()), vp(dK.data_ptr()), vp(dX.data_ptr()), ld, vp(dR.data_ptr()),
+                                             vp(du.data_ptr()), self.c, mode, vp(dW.data_ptr()) if w is not None else None, meth, rho,
+                                             vp(dO.data_ptr()), None)
+            self.sym.sync()
+            return dO.cpu().numpy().reshape(1, FINISH_HEAD + rho.size)
+        return run
+
     def _block_device(self, src, mode, method, rho):
         """(rows, offsets, weights) -> the block's per-set rows of ``scilmm_sets_finish_dev`` (n_sets x (10 + n_rho)), on the host:
         the rows and the weights are brought to the device, the form's Gram entry point and the finish are queued one behind the
@@ -557,18 +610,19 @@ class VariantSetTest(AssociationScan):
         """The checks of the sets (before any launch), then block by block: gather the block's marker rows, one device call, the
         statistics and the Gram matrix (``_block``), the host algebra set by set -- or, with ``finish="device"``, the finish
         queued behind the block and the sets' rows alone brought back (``_block_device``).  With ``max_markers`` a set wider than
-        a block runs on its own, sub-block by sub-block (``_block_wide``), and meets the same host algebra."""
+        a block runs on its own, sub-block by sub-block (``_block_wide``), and meets the same host algebra -- or, with
+        ``finish="wide"``, the wide finish on the device (``_block_wide_device``)."""
         sets = check_sets(sets, src.m, self.block, max_markers)
         weights, sf = check_weights(weights, sets), check_method(method)
-        if finish not in FINISHES:
-            raise ValueError("finish must be one of %s, got %r" % (", ".join(FINISHES), finish))
-        if finish == "device" and return_kernel:
+        if finish not in FINISH_VALUES:
+            raise ValueError("finish must be one of %s, got %r" % (", ".join(FINISH_VALUES), finish))
+        if finish != "host" and return_kernel:
             raise ValueError('return_kernel=True needs finish="host": the device finish does not bring K back')
         sizes = [s.size for s in sets]
         widest = max(sizes + [0])
         if finish == "device" and widest > self.block:
-            raise ValueError('a set of %d markers needs finish="host": the device finish holds one block of at most %d markers in LDS'
-                             % (widest, self.block))
+            raise ValueError('a set of %d markers needs finish="host" or finish="wide": the device finish holds one block of at most '
+                             '%d markers in LDS' % (widest, self.block))
         rho = check_rho(rho) if skato else None
         self._check_factor()
         ns = len(sets)
@@ -578,15 +632,20 @@ class VariantSetTest(AssociationScan):
             out.update({k: np.full(ns, np.nan) for k in SKATO_KEYS[:3]})
             out["skato_p_rho"] = np.full((ns, rho.size), np.nan)
         packed = pack_sets(sizes, self.block) if widest <= self.block else plan_sets(sizes, self.block)
-        if finish == "device":
+        if finish != "host":
             given = not (weights is None or isinstance(weights, str))
             mode = WEIGHT_GIVEN if given else WEIGHT_ONES if weights is None else WEIGHT_BETA
             grid = rho if skato else np.empty(0)
-            block = self._block_device(src, mode, method, grid) if sets else None
+            narrow = any(s.size <= self.block for s in sets)
+            block = self._block_device(src, mode, method, grid) if narrow else None
+            wide = self._block_wide_device(src, -(-widest // self.block), narrow, mode, method, grid) if widest > self.block else None
             for members in packed:
-                start = np.concatenate([[0], np.cumsum([sets[i].size for i in members])]).astype(np.int32)
-                w = np.ascontiguousarray(np.concatenate([weights[i] for i in members])) if given else None
-                O = block(np.concatenate([sets[i] for i in members]), start, w)
+                if sets[members[0]].size > self.block:           # (finish="wide": a wide set is a list of its own)
+                    O = wide(sets[members[0]], np.ascontiguousarray(weights[members[0]]) if given else None)
+                else:
+                    start = np.concatenate([[0], np.cumsum([sets[i].size for i in members])]).astype(np.int32)
+                    w = np.ascontiguousarray(np.concatenate([weights[i] for i in members])) if given else None
+                    O = block(np.concatenate([sets[i] for i in members]), start, w)
                 out["n_used"][members] = O[:, 0].astype(np.int64)
                 for col, k in ((1, "burden_beta"), (2, "burden_se"), (3, "burden_chi2"), (4, "skat_q"), (5, "skat_p")):
                     out[k][members] = O[:, col]

@@ -26,7 +26,14 @@ keeps as the wall time of 20 keeps queued behind one block over 20 (k_scan_keep 
 ceil(k / 128) separate 128-marker sets without max_markers (the Gram blocks alone), in alternating rounds of the same run; the
 ratio of the two device times; the panel of the last block against its own kept copy next to its Gram matrix; the host finish
 of the assembled set with and without SKAT-O, and the wall time of the whole call.  One warm-up round, then --blocks rounds (use
---blocks 5)."""
+--blocks 5).
+  usage: sets_timing.py 100k --wide-finish 256,1024 [--host-reps 3] [--out profiles/sets_wide_finish_100k.json]
+--wide-finish times the finish of one set of k rare markers per width (scilmm_sets_finish_wide_dev): the
+sub-blocks are queued once as VariantSetTest(..., max_markers=k, finish="wide") queues them and leave their pieces on the device;
+then, per round, the finish with SKAT-O and without, its four phases by HIP events (prep + form | reduction | eigenvalues |
+tails); the host finish of the same set in the same run (--host-reps timings each; 0 leaves it out), the deviation of the device's
+row from the host's, and the wall time of the whole call with finish="wide" and finish="host".  One warm-up round, then --blocks
+rounds."""
 import argparse, ctypes, json, os, sys
 import numpy as np
 import scipy.sparse as sp
@@ -38,6 +45,8 @@ ap.add_argument("--shapes", default=None)
 ap.add_argument("--finish", action="store_true")
 ap.add_argument("--binary", action="store_true")
 ap.add_argument("--wide", default=None)
+ap.add_argument("--wide-finish", dest="wide_finish", default=None)
+ap.add_argument("--host-reps", dest="host_reps", type=int, default=3)
 args = ap.parse_args()
 import torch
 from scilmm_amd import SparseCholesky, VariantSetTest
@@ -251,7 +260,92 @@ def wide_leg(widths):
     return rec
 
 
-if args.finish or args.binary or args.wide:
+def wide_finish_leg(widths):
+    import time
+    from scilmm_amd import sets as mod
+    bp = R
+    rho = mod.check_rho(None)
+    rec = {"workload": args.workload, "n": int(n), "block": R, "widths": {},
+           "timer": "HIP events of scilmm_sets_finish_wide_dev, one call per synchronise; one warm-up round, then %d rounds; the host "
+                    "finish: perf_counter around VariantSetTest._one_set, %d times" % (args.blocks, args.host_reps)}
+    dR, du = torch.from_numpy(np.ascontiguousarray(tester.R)).cuda(), torch.from_numpy(np.ascontiguousarray(tester.u)).cuda()
+    for k in widths:
+        B = -(-k // R)
+        ldw = max(B - 1, 1) * bp
+        Gm = rng.binomial(2, rng.uniform(0.005, 0.05, k)[:, None], size=(k, n)).astype(np.int8)
+        Gm[rng.random(Gm.shape) < 0.02] = -1
+        store = torch.empty((n * ldw,), dtype=torch.float64, device="cuda")
+        dSa = torch.empty((B * (q + 4) * R,), dtype=torch.float64, device="cuda")
+        dKa = torch.empty((B * R * R,), dtype=torch.float64, device="cuda")
+        dXa = torch.empty((B * R * ldw,), dtype=torch.float64, device="cuda")
+        dO = torch.empty((mod.FINISH_HEAD + rho.size,), dtype=torch.float64, device="cuda")
+        pQ = vp(tester.dQ.data_ptr())
+        sweeps_ms, Ss, Gs, Xs = 0.0, [], [], []
+        for b in range(B):                                       # the sub-blocks, as VariantSetTest._block_wide_device queues them
+            sub = np.ascontiguousarray(Gm[b * R:(b + 1) * R])
+            rb = sub.shape[0]
+            dG[:rb, :n].copy_(torch.from_numpy(sub)); torch.cuda.synchronize()
+            fac.scan_block_gram_dev(vp(dG.data_ptr()), ld, rb, pQ, q, vp(dSa.data_ptr() + 8 * b * (q + 4) * R), vp(dKa.data_ptr() + 8 * b * R * R))
+            if b > 0: fac.scan_panel_dev(rb, vp(store.data_ptr()), ldw, b * bp, vp(dXa.data_ptr() + 8 * b * R * ldw), ldw)
+            if b < B - 1: fac.scan_block_keep_dev(rb, vp(store.data_ptr()), ldw, b * bp)
+            sym.sync()
+            sweeps_ms += float(sum(sym.scan_timing())) + (float(sum(sym.panel_timing())) if b > 0 else 0.0)
+            Ss.append(dSa[b * (q + 4) * R:b * (q + 4) * R + (q + 4) * rb].cpu().numpy().reshape(q + 4, rb))
+            Gs.append(dKa[b * R * R:b * R * R + rb * rb].cpu().numpy().reshape(rb, rb))
+            if b > 0: Xs.append(dXa[b * R * ldw:(b * R + rb) * ldw].cpu().numpy().reshape(rb, ldw)[:, :b * bp])
+        phases = {"skato": [], "burden_skat": []}
+        rows = {}
+        for it in range(1 + args.blocks):
+            for key, grid in (("skato", rho), ("burden_skat", np.empty(0))):
+                fac.sets_finish_wide_dev(k, R, q, vp(dSa.data_ptr()), vp(dKa.data_ptr()), vp(dXa.data_ptr()) if B > 1 else None, ldw if B > 1 else 0,
+                                         vp(dR.data_ptr()), vp(du.data_ptr()), q - 1, 0, None, 0, grid, vp(dO.data_ptr()), None)
+                sym.sync()
+                if it >= 1: phases[key].append(sym.sets_finish_wide_timing())
+                rows[key] = dO.cpu().numpy().copy()
+        dev = {}
+        for key, v in phases.items():
+            a = np.asarray(v)
+            dev[key] = {"prep_form_ms": summary(a[:, 0]), "reduction_ms": summary(a[:, 1]), "eigenvalues_ms": summary(a[:, 2]),
+                        "tails_ms": summary(a[:, 3]), "total_ms": summary(a.sum(axis=1))}
+        host, dev_vs_host = {}, None
+        if args.host_reps > 0:
+            S, K = mod.assemble_wide(Ss, Gs, Xs, bp)
+            for key, grid in (("burden_skat", None), ("skato", rho)):
+                t = []
+                for _ in range(args.host_reps):
+                    out = {kk: np.full(1, np.nan) for kk in mod.KEYS + mod.SKATO_KEYS[:3]}
+                    out["n_used"] = np.zeros(1, dtype=np.int64); out["skato_p_rho"] = np.full((1, rho.size), np.nan)
+                    t0 = time.perf_counter()
+                    tester._one_set(out, 0, S, K, "beta", mod.mixture_sf_saddlepoint, grid, "saddlepoint")
+                    t.append(1e3 * (time.perf_counter() - t0))
+                host[key + "_ms"] = summary(t)
+            h = np.r_[out["skat_p"][0], out["skato_p"][0], out["skato_pmin"][0], out["skato_p_rho"][0]]
+            d = np.r_[rows["skato"][5:8], rows["skato"][mod.FINISH_HEAD:]]
+            dev_vs_host = {"worst_rel_dev_of_a_p_value": float(np.max(np.abs(d - h) / np.abs(h))), "skat_q_rel_dev": float(abs(rows["skato"][4] - out["skat_q"][0]) / out["skat_q"][0]),
+                           "same_rho": bool(rows["skato"][8] == out["skato_rho"][0]), "n_used": int(rows["skato"][0]), "flags": int(rows["skato"][9]),
+                           "skato_p": float(rows["skato"][6])}
+        calls = {}
+        for fin, reps in (("wide", 3), ("host", min(3, args.host_reps))):
+            t = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                tester(Gm, [np.arange(k)], max_markers=k, skato=True, finish=fin)
+                t.append(1e3 * (time.perf_counter() - t0))
+            if t: calls[fin] = summary(t)
+        rec["widths"][str(k)] = {"sub_blocks": B, "sweeps_and_panels_device_ms": sweeps_ms, "wide_finish_device_ms": dev, "host_finish_ms": host,
+                                 "device_row_vs_host_row": dev_vs_host, "whole_call_wall_ms_skato": calls}
+        del store, dSa, dKa, dXa
+    return rec
+
+
+if args.finish or args.binary or args.wide or args.wide_finish:
+    if args.wide_finish:
+        rec = wide_finish_leg([int(v) for v in args.wide_finish.split(",")])
+        print(json.dumps(rec))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rec, open(args.out, "w"), indent=1)
+        sys.exit(0)
     rec = wide_leg([int(v) for v in args.wide.split(",")]) if args.wide else binary_leg() if args.binary else finish_leg()
     print(json.dumps(rec))
     if args.out:
