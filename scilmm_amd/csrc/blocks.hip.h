@@ -280,6 +280,22 @@ int scan_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const Sp
   return SCILMM_OK;
 }
 
+// What the finish of a block and of a wide set refuse alike: the pointers, c, q, the tail method, the weight mode and the grid (a
+// HOST array, read here: a NaN fails its comparison).  Nothing of a handle is read.
+inline bool fin_weights_ok(int32_t weight_mode, const double* d_weights) {
+  return (weight_mode == FIN_BETA || weight_mode == FIN_ONES || weight_mode == FIN_GIVEN) && (weight_mode != FIN_GIVEN || d_weights);
+}
+template <class Args>
+bool fin_args_ok(const Args& a) {
+  if (!a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.d_out || a.c < 1 || a.c > FIN_CMAX || a.q != a.c + 1 || a.n_rho < 0 ||
+      a.n_rho > FIN_RHO_MAX || (a.n_rho > 0 && !a.rho) || (a.method != FIN_SADDLE && a.method != FIN_LIU) ||
+      !fin_weights_ok(a.weight_mode, a.d_weights))
+    return false;
+  for (int32_t j = 0; j < a.n_rho; ++j)
+    if (!(a.rho[j] >= 0.0 && a.rho[j] <= 1.0)) return false;
+  return true;
+}
+
 // What scilmm_sets_finish_dev takes beside the factor.
 struct FinishArgs {
   int32_t r, q;
@@ -297,23 +313,17 @@ struct FinishArgs {
   const double* d_vscale = nullptr;   // the columns' variance scales (scilmm_sets_finish_scaled_dev), or null: all 1
   // what the set SPA entry points check as well: the offsets (a HOST array, read here) and the weights
   static bool sets_ok(int32_t r, int32_t n_sets, const int32_t* set_start, int32_t weight_mode, const double* d_weights) {
-    if (!set_start || n_sets < 1 || n_sets > r || (weight_mode != FIN_BETA && weight_mode != FIN_ONES && weight_mode != FIN_GIVEN) ||
-        (weight_mode == FIN_GIVEN && !d_weights))
-      return false;
+    if (!set_start || n_sets < 1 || n_sets > r || !fin_weights_ok(weight_mode, d_weights)) return false;
     if (set_start[0] != 0 || set_start[n_sets] > r) return false;
     for (int32_t i = 0; i < n_sets; ++i)
       if (set_start[i + 1] <= set_start[i]) return false;
     return true;
   }
-  // before anything of the handle is read; the offsets and the grid are HOST arrays and are read here (a NaN fails its comparison)
+  // before anything of the handle is read; the offsets are a HOST array and are read here
   static bool args_ok(const scilmm_factor* fac, const FinishArgs& a) {
-    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.d_out || a.r < 1 || a.r > RPMAX || a.c < 1 || a.c > FIN_CMAX ||
-        a.q != a.c + 1 || a.n_rho < 0 || a.n_rho > FIN_RHO_MAX || (a.n_rho > 0 && !a.rho) || a.ld_out < FIN_HEAD + a.n_rho ||
-        (a.method != FIN_SADDLE && a.method != FIN_LIU))
+    if (!fac || !fin_args_ok(a) || a.r < 1 || a.r > RPMAX || a.ld_out < FIN_HEAD + a.n_rho ||
+        !sets_ok(a.r, a.n_sets, a.set_start, a.weight_mode, a.d_weights))
       return false;
-    for (int32_t j = 0; j < a.n_rho; ++j)
-      if (!(a.rho[j] >= 0.0 && a.rho[j] <= 1.0)) return false;
-    if (!sets_ok(a.r, a.n_sets, a.set_start, a.weight_mode, a.d_weights)) return false;
     return fac->sym && fac->sym->S;  // (what needs no handle has been checked: with it wrong, nothing of the handle is read)
   }
 };
@@ -331,7 +341,7 @@ int sets_finish(scilmm_factor* fac, const FinishArgs& a, const char* who) {
   int32_t widest = 0;
   for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
   for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
-  for (int32_t j = 0; j < a.n_rho; ++j) sets.rho[j] = a.rho[j];
+  for (int32_t j = 0; j < a.n_rho; ++j) sets.grid.rho[j] = a.rho[j];
   const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
   const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
   // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
@@ -363,17 +373,11 @@ struct WideArgs {
   double *d_out, *d_lam;
   int32_t bp() const { return (block + 15) / 16 * 16; }
   int32_t nsub() const { return (k + block - 1) / block; }
-  // before anything of the handle is read; the grid is a HOST array and is read here (a NaN fails its comparison)
+  // before anything of the handle is read
   static bool args_ok(const scilmm_factor* fac, const WideArgs& a) {
-    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.d_out || a.k < 1 || a.k > WIDE_KMAX || a.block < 1 || a.block > RPMAX ||
-        a.c < 1 || a.c > FIN_CMAX || a.q != a.c + 1 || a.n_rho < 0 || a.n_rho > FIN_RHO_MAX || (a.n_rho > 0 && !a.rho) ||
-        (a.method != FIN_SADDLE && a.method != FIN_LIU) ||
-        (a.weight_mode != FIN_BETA && a.weight_mode != FIN_ONES && a.weight_mode != FIN_GIVEN) || (a.weight_mode == FIN_GIVEN && !a.d_weights))
-      return false;
+    if (!fac || !fin_args_ok(a) || a.k < 1 || a.k > WIDE_KMAX || a.block < 1 || a.block > RPMAX) return false;
     const int64_t kept = (int64_t)(a.nsub() - 1) * a.bp();    // the columns of the cross store
     if (kept > WIDE_KMAX || (a.nsub() == 1) != (a.d_cross == nullptr) || (a.nsub() > 1 && a.ld_cross < kept)) return false;
-    for (int32_t j = 0; j < a.n_rho; ++j)
-      if (!(a.rho[j] >= 0.0 && a.rho[j] <= 1.0)) return false;
     return fac->sym && fac->sym->S;  // (what needs no handle has been checked: with it wrong, nothing of the handle is read)
   }
 };
@@ -397,7 +401,7 @@ int sets_finish_wide(scilmm_factor* fac, const WideArgs& a, const char* who) {
     for (auto& e : D->wide_ev) HIPCHK(hipEventCreate(&e));
   const WideWs ws = wide_cut(D->wide_ws, (size_t)k);
   const WideIn in{k, a.block, a.bp(), a.q, a.d_stats, a.d_gram, a.d_cross, a.ld_cross};
-  WideRho grid{};
+  FinGrid grid{};
   for (int32_t j = 0; j < a.n_rho; ++j) grid.rho[j] = a.rho[j];
   hipStream_t s0 = D->stream;
   HIPCHK(hipEventRecord(D->wide_ev[0], s0));

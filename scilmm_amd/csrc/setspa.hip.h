@@ -24,7 +24,7 @@
 #include <stdint.h>
 
 #include "plan_types.h"
-#include "setfinish.hip.h"
+#include "setmath.hip.h"
 #include "spa.hip.h"
 
 namespace scilmm {
@@ -64,7 +64,7 @@ __device__ double sspa_deviate(double lp) {
 // x = v^2 of a saddlepoint row (flag, log p), or NaN where the row gives none: the flag is not 1, log p is NaN or >= 0, or x is
 // not finite and positive
 __device__ __forceinline__ double sspa_chi2(double flag, double lp) {
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = fin_nan();
   if (!(flag == 1.0) || !(lp < 0.0)) return nan;
   const double v = sspa_deviate(lp), x = v * v;
   return x > 0.0 && x < INFINITY ? x : nan;
@@ -91,15 +91,14 @@ __global__ __launch_bounds__(256) void k_sets_spa(int32_t n, int32_t r, int32_t 
   const int set = blockIdx.x;
   const int c0 = sets.start[set], m = sets.start[set + 1] - c0;
   const SpaFold fold{red, lane, wv};
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = fin_nan();
   double* row = bspa + (int64_t)set * SSPA_ROWLEN;
 
   // 0. the kept markers
   if (tid == 0) {
     int k = 0;
     for (int j = 0; j < m; ++j) {
-      const double n_obs = stats[c0 + j], css = stats[2 * (int64_t)r + c0 + j];
-      const bool keep = !(n_obs == 0.0 || css == 0.0);
+      const bool keep = fin_kept(stats[c0 + j], stats[2 * (int64_t)r + c0 + j]);
       slot[j] = keep ? k : -1;
       if (keep) idx[k++] = c0 + j;
     }
@@ -120,14 +119,8 @@ __global__ __launch_bounds__(256) void k_sets_spa(int32_t n, int32_t r, int32_t 
   // 1. z, s, w, a and rho: a thread per kept marker
   if (tid < k) {
     const int col = idx[tid];
-    double uz = 0.0, zz = 0.0;
-    for (int a = 0; a < c; ++a) {
-      double v = stats[(int64_t)(4 + a) * r + col];
-      for (int l = 0; l < a; ++l) v -= R[l * c + a] * Z[l * RPMAX + tid];
-      v /= R[a * c + a];
-      Z[a * RPMAX + tid] = v;
-      uz += u[a] * v;
-    }
+    const double uz = fin_forward(c, R, u, [&](int a) { return stats[(int64_t)(4 + a) * r + col]; }, Z, RPMAX, tid);
+    double zz = 0.0;
     for (int l = 0; l < c; ++l) zz = fma(Z[l * RPMAX + tid], Z[l * RPMAX + tid], zz);
     const double s = stats[(int64_t)(4 + c) * r + col] - uz;
     const double mean = stats[(int64_t)r + col];
@@ -146,7 +139,7 @@ __global__ __launch_bounds__(256) void k_sets_spa(int32_t n, int32_t r, int32_t 
     const int i = at / k, j = at - i * k;
     double zz = 0.0;
     for (int l = 0; l < c; ++l) zz = fma(Z[l * RPMAX + i], Z[l * RPMAX + j], zz);
-    const double kij = 0.5 * (gram[(int64_t)idx[i] * r + idx[j]] + gram[(int64_t)idx[j] * r + idx[i]]) - zz;
+    const double kij = fin_kernel_entry(gram[(int64_t)idx[i] * r + idx[j]], gram[(int64_t)idx[j] * r + idx[i]], zz);
     aB += wv_[i] * kij * wv_[j];
     vq += (wv_[i] * rv[i]) * kij * (wv_[j] * rv[j]);
   }

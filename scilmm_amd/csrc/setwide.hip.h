@@ -13,14 +13,14 @@
 //   k_wide_scale  : a workgroup per task (SKAT, the grid values, the remainder B): the task's scaled d and e^2, its Gershgorin
 //                   interval, pivmin;
 //   k_wide_eig    : a thread per (task, index): bisection on the Sturm count, the spectra in descending order;
-//   k_wide_tails  : one workgroup; steps 6 and 7 of k_sets_finish (setfinish.hip.h) on the spectra in HBM, a wave per task with
-//                   the task's spectrum dealt across its lanes.
+//   k_wide_tails  : one workgroup; the tails of the mixtures on the spectra in HBM, a wave per task with the task's spectrum
+//                   dealt across its lanes (FinWave), then the SKAT-O tail of setmath.hip.h, the one k_sets_finish runs.
 // The full symmetric matrix is kept (not one triangle): row j is then the step's column, read along the lanes, and symv and rank2
 // share one decomposition (WIDE_ROWS rows per workgroup, a wave per two rows, the columns along the lanes).  No atomics; every
 // sum is taken in a fixed order and folded by a fixed tree.  The number m of kept markers is known to the device alone: the grids
 // are sized by k and a workgroup with nothing to do returns.
 #pragma once
-#include "setfinish.hip.h"
+#include "setmath.hip.h"
 
 namespace scilmm {
 
@@ -78,47 +78,11 @@ struct WideIn {
     if (bi == bj) {
       const int rb = min(block, k - bi * block);
       const double* g = gram + (int64_t)bi * block * block;
-      return 0.5 * (g[ji * rb + jj] + g[jj * rb + ji]);
+      return fin_kernel_entry(g[ji * rb + jj], g[jj * rb + ji], 0.0);
     }
     return bi > bj ? cross[(int64_t)i * ld_cross + bj * bp + jj] : cross[(int64_t)j * ld_cross + bi * bp + ji];
   }
 };
-
-// the workgroup's integers added up; every thread gets the sum (red: blockDim.x integers)
-__device__ __forceinline__ int wide_fold_int(int v, int32_t* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const int out = red[0];
-  __syncthreads();
-  return out;
-}
-// ... the largest of the workgroup's values (exact, whatever the order)
-__device__ __forceinline__ double wide_fold_max(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  const double out = red[0];
-  __syncthreads();
-  return out;
-}
-
-// What k_sets_finish writes for a set with nothing left.
-__device__ __forceinline__ void wide_empty_row(double* row, int n_rho) {
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  row[0] = 0.0;
-  for (int i = 1; i < FIN_HEAD - 1; ++i) row[i] = nan;
-  row[FIN_HEAD - 1] = 0.0;
-  for (int j = 0; j < n_rho; ++j) row[FIN_HEAD + j] = nan;
-}
 
 // Steps 0 and 1 of k_sets_finish for k <= 4 096: one workgroup of WIDE_PREP_NT threads, a run of consecutive markers each.
 __global__ __launch_bounds__(WIDE_PREP_NT) void k_wide_prep(WideIn in, int32_t c, const double* __restrict__ R, const double* __restrict__ u,
@@ -128,7 +92,7 @@ __global__ __launch_bounds__(WIDE_PREP_NT) void k_wide_prep(WideIn in, int32_t c
   const int tid = threadIdx.x, k = in.k;
   const int per = (k + WIDE_PREP_NT - 1) / WIDE_PREP_NT, i0 = min(k, tid * per), i1 = min(k, i0 + per);
   int mine = 0;
-  for (int i = i0; i < i1; ++i) mine += !(in.stat(0, i) == 0.0 || in.stat(2, i) == 0.0) ? 1 : 0;
+  for (int i = i0; i < i1; ++i) mine += fin_kept(in.stat(0, i), in.stat(2, i)) ? 1 : 0;
   cnt[tid] = mine;
   __syncthreads();
   for (int o = 1; o < WIDE_PREP_NT; o <<= 1) {                // (inclusive prefix sum)
@@ -140,25 +104,18 @@ __global__ __launch_bounds__(WIDE_PREP_NT) void k_wide_prep(WideIn in, int32_t c
   const int m = cnt[WIDE_PREP_NT - 1];
   int at = cnt[tid] - mine;
   for (int i = i0; i < i1; ++i)
-    if (!(in.stat(0, i) == 0.0 || in.stat(2, i) == 0.0)) ws.idx[at++] = i;
+    if (fin_kept(in.stat(0, i), in.stat(2, i))) ws.idx[at++] = i;
   if (tid == 0) {
     ws.ic[WI_M] = m;
     ws.ic[WI_FLAG] = 0;
-    if (m == 0) wide_empty_row(row, n_rho);
+    if (m == 0) fin_empty_row(row, n_rho);
   }
   if (lam_out)
-    for (int i = tid; i < k; i += WIDE_PREP_NT) lam_out[i] = __longlong_as_double(0x7ff8000000000000ll);
+    for (int i = tid; i < k; i += WIDE_PREP_NT) lam_out[i] = fin_nan();
   __syncthreads();                                            // (the list of kept markers is visible to the workgroup)
   for (int a = tid; a < m; a += WIDE_PREP_NT) {
     const int col = ws.idx[a];
-    double uz = 0.0;
-    for (int r = 0; r < c; ++r) {
-      double v = in.stat(4 + r, col);
-      for (int l = 0; l < r; ++l) v -= R[l * c + r] * ws.Z[(int64_t)l * k + a];    // (this thread's own stores)
-      v /= R[r * c + r];
-      ws.Z[(int64_t)r * k + a] = v;
-      uz += u[r] * v;
-    }
+    const double uz = fin_forward(c, R, u, [&](int r) { return in.stat(4 + r, col); }, ws.Z, (int64_t)k, a);
     const double s = in.stat(4 + c, col) - uz;
     const double w = fin_weight(wmode, in.stat(1, col), weights, col);
     ws.wa[a] = w;
@@ -187,7 +144,7 @@ __global__ __launch_bounds__(256) void k_wide_form(WideIn in, int32_t c, WideWs 
     if (b == a) ws.dg[a] = v;
     rs += v;
   }
-  rs = fin_fold(rs, red);
+  rs = fin_fold(rs, red, FinAdd{});
   if (tid == 0) ws.rs[a] = rs;
 }
 
@@ -204,7 +161,7 @@ __global__ __launch_bounds__(256) void k_wide_burden(WideWs ws, double* __restri
     c += t * t;
     d += ws.dg[i];
   }
-  const double s11 = fin_fold(a, red), sum = fin_fold(b, red), tt = fin_fold(c, red), tr = fin_fold(d, red);
+  const double s11 = fin_fold(a, red, FinAdd{}), sum = fin_fold(b, red, FinAdd{}), tt = fin_fold(c, red, FinAdd{}), tr = fin_fold(d, red, FinAdd{});
   if (tid == 0) {
     ws.sc[WS_S11] = s11;
     ws.sc[WS_WS] = sum;
@@ -248,7 +205,7 @@ __global__ __launch_bounds__(256) void k_wide_symv(int32_t step, WideWs ws) {
     h.x = ws.A + (int64_t)j * m + s;
     double ss = 0.0;
     for (int b = 1 + tid; b < n; b += 256) ss = fma(h.x[b], h.x[b], ss);
-    ss = fin_fold(ss, red);
+    ss = fin_fold(ss, red, FinAdd{});
     const double alpha = h.x[0];
     double beta = alpha;
     tau = 0.0;
@@ -299,7 +256,7 @@ __global__ __launch_bounds__(256) void k_wide_rank2(int32_t step, WideWs ws) {
   const double* p = ws.p + s;
   double dot = 0.0;
   for (int b = tid; b < n; b += 256) dot = fma(p[b], h.v(b), dot);
-  dot = fin_fold(dot, red);
+  dot = fin_fold(dot, red, FinAdd{});
   const double half = 0.5 * tau * dot;
   auto w = [&](int b) { return fma(-half, h.v(b), p[b]); };
   const int r0 = blockIdx.x * WIDE_ROWS + 2 * wv, r1 = r0 + 1;
@@ -319,11 +276,7 @@ __global__ __launch_bounds__(256) void k_wide_rank2(int32_t step, WideWs ws) {
 // The tasks' tridiagonal matrices from T = (d, e): task 0 SKAT (T itself), task 1 + j the grid value rho_j (D^1/2 T D^1/2), task
 // n_rho + 1 the remainder B (the Schur complement of d_0, order m - 1); with them the Gershgorin interval widened as dstebz widens
 // it, pivmin and the absolute tolerance eps |T| (dstebz's default).  A task that is not wanted has order 0.
-struct WideRho {
-  double rho[FIN_RHO_MAX];
-};
-
-__global__ __launch_bounds__(256) void k_wide_scale(int32_t k, int32_t n_rho, WideRho grid, WideWs ws) {
+__global__ __launch_bounds__(256) void k_wide_scale(int32_t k, int32_t n_rho, FinGrid grid, WideWs ws) {
   __shared__ double red[256];
   const int tid = threadIdx.x, task = blockIdx.x, m = ws.ic[WI_M];
   if (m == 0) return;
@@ -357,9 +310,9 @@ __global__ __launch_bounds__(256) void k_wide_scale(int32_t k, int32_t n_rho, Wi
     nlo = fmax(nlo, rad - d);
     emax = fmax(emax, above);
   }
-  hi = wide_fold_max(hi, red);
-  nlo = wide_fold_max(nlo, red);
-  emax = wide_fold_max(emax, red);
+  hi = fin_fold(hi, red, FinMax{});
+  nlo = fin_fold(nlo, red, FinMax{});
+  emax = fin_fold(emax, red, FinMax{});
   if (tid == 0) {
     double* rec = ws.tsc + task * WIDE_TSC;
     rec[0] = (double)n;
@@ -409,112 +362,18 @@ __global__ __launch_bounds__(64) void k_wide_eig(int32_t k, WideWs ws, double* _
   if (!ok) ws.ic[WI_FLAG] = FIN_F_SWEEPS;                     // (every writer stores the same value)
 }
 
-// ---- the mixtures' tails with a spectrum dealt across a wave (twins of fin_liu_params, fin_lugannani_rice and fin_mixture_sf of
-// setfinish.hip.h, formula by formula): lane l takes the eigenvalues l, l + 64, ..., the lanes' sums are added by a fixed
-// butterfly that leaves the same bits in every lane, so all 64 lanes take every branch together.  Measured before this was
-// written: a lane per task walked 1 024 eigenvalues per Newton step and the tails took 11.4 ms beside a reduction of 16.4 ms.
-
-__device__ __forceinline__ double wide_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ FinLiu wide_liu_params(const double* lam, int n) {
-  const int lane = threadIdx.x & 63;
-  double c1 = 0.0, c2 = 0.0, c4 = 0.0;
-  for (int i = lane; i < n; i += 64) {
-    const double v = lam[i], v2 = v * v;
-    c1 += v;
-    c2 += v2;
-    c4 += v2 * v2;
-  }
-  c1 = wide_wave_sum(c1);
-  c2 = wide_wave_sum(c2);
-  c4 = wide_wave_sum(c4);
-  FinLiu p{c1, c2, 0.0, c2 * c2 / c4};
-  p.a = sqrt(p.l);
-  return p;
-}
-
-__device__ double wide_lugannani_rice(double q, const double* lam, int n, double mu, double lmax, bool& ok) {
-  const int lane = threadIdx.x & 63;
-  const double pole = 0.5 / lmax;
-  auto k1 = [&](double t, double& k2) {
-    double f = 0.0, g = 0.0;
-    for (int i = lane; i < n; i += 64) {
-      const double r = lam[i] / (1.0 - 2.0 * lam[i] * t);
-      f += r;
-      g += r * r;
-    }
-    k2 = 2.0 * wide_wave_sum(g);
-    return wide_wave_sum(f) - q;
-  };
-  double lo, hi, k2;
-  if (q > mu) {
-    lo = 0.0;
-    hi = pole * (1.0 - fmin(0.5, lmax / (2.0 * q)));
-  } else {
-    lo = -pole;
-    hi = 0.0;
-    for (int g = 0; g < 1100 && k1(lo, k2) > 0.0; ++g) lo *= 2.0;
-  }
-  double t = 0.0;
-  ok = false;
-  for (int it = 0; it < FIN_ITMAX; ++it) {
-    const double f = k1(t, k2);
-    if (f < 0.0) lo = t; else hi = t;
-    double tn = t - f / k2;
-    if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
-    const double dt = fabs(tn - t);
-    t = tn;
-    if (dt <= 1e-15 * pole + 4e-16 * fabs(t)) {
-      ok = true;
-      break;
-    }
-  }
-  double K0 = 0.0;
-  k2 = 0.0;
-  for (int i = lane; i < n; i += 64) {
-    const double den = 1.0 - 2.0 * lam[i] * t, r = lam[i] / den;
-    K0 += log1p(-2.0 * lam[i] * t);
-    k2 += r * r;
-  }
-  K0 = -0.5 * wide_wave_sum(K0);
-  k2 = 2.0 * wide_wave_sum(k2);
-  const double w = copysign(sqrt(2.0 * (t * q - K0)), t), v = t * sqrt(k2);
-  return fin_norm_sf(w + log(v / w) / w);
-}
-
-// (lam in descending order: the largest is the first)
-__device__ double wide_mixture_sf(double q, const double* lam, int n, const FinLiu& liu, int method, bool& ok) {
-  ok = true;
-  if (method == FIN_LIU) return fin_liu_sf(q, liu);
-  if (q <= 0.0) return 1.0;
-  const double lmax = lam[0];
-  const double mu = liu.c1, sd = sqrt(2.0 * liu.c2);
-  if (fabs(q - mu) >= FIN_SEAM * sd) return wide_lugannani_rice(q, lam, n, mu, lmax, ok);
-  const double lo = mu - FIN_SEAM * sd, hi = mu + FIN_SEAM * sd;
-  bool ok1, ok2;
-  const double c_lo = wide_lugannani_rice(lo, lam, n, mu, lmax, ok1) / fin_liu_sf(lo, liu);
-  const double c_hi = wide_lugannani_rice(hi, lam, n, mu, lmax, ok2) / fin_liu_sf(hi, liu);
-  ok = ok1 && ok2;
-  return fin_liu_sf(q, liu) * (c_lo + (c_hi - c_lo) * (q - lo) / (hi - lo));
-}
-
-// Steps 6 and 7 of k_sets_finish on the spectra in HBM (descending: what is above a floor is a prefix).  The twin of every piece
-// is named where it starts; unifying the two is left for later.
-__global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, WideRho grid, int32_t method, WideWs ws, double* __restrict__ row) {
+// The tails of the mixtures and the SKAT-O tail on the spectra in HBM (descending: what is above a floor is a prefix, the largest
+// is the first).  Measured before the spectra were dealt across a wave: a lane per task walked 1 024 eigenvalues per Newton step
+// and the tails took 11.4 ms beside a reduction of 16.4 ms.
+__global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, FinGrid grid, int32_t method, WideWs ws, double* __restrict__ row) {
   __shared__ double prho[8 * FIN_RHO_MAX], sc[64], fm[FIN_RHO_MAX + 2], pts[128], spts[128];
   __shared__ int32_t ic[16], nf[WIDE_TASKS], redi[256];
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
   const int m = ws.ic[WI_M];
   if (m == 0) return;  // (the whole workgroup; k_wide_prep wrote the row)
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  double *qrho = prho + FIN_RHO_MAX, *lc1 = qrho + FIN_RHO_MAX, *lsd = lc1 + FIN_RHO_MAX, *ll = lsd + FIN_RHO_MAX;
-  double *al = ll + FIN_RHO_MAX, *be = al + FIN_RHO_MAX;
-  enum { S_SKATP = 0, S_T, S_MU, S_SD, S_DF, S_Z0, S_END };
-  enum { I_FLAG = 0, I_J0, I_DEG, I_NB };
+  const double nan = fin_nan();
+  const FinTail tail{prho, sc, fm, pts, spts, ic};
+  double *qrho = tail.qrho(), *lc1 = tail.lc1(), *lsd = tail.lsd(), *ll = tail.ll();
   const double ws_ = ws.sc[WS_WS], tt = ws.sc[WS_TT], tr = ws.sc[WS_TR];
   // the scalars of the route: s11 = m d0, a'a = m (d0^2 + e0^2), a'Ba = m e0^2 (d1 - e0^2 / d0)
   const double d0 = ws.d[0], e0 = m > 1 ? ws.e[0] : 0.0, d1 = m > 1 ? ws.d[1] : 0.0;
@@ -529,11 +388,12 @@ __global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, Wi
     int c = 0;
     if (live)
       for (int i = tid; i < n; i += nt) c += ev[i] > FIN_FLOOR * top ? 1 : 0;
-    c = wide_fold_int(c, redi);
+    c = fin_fold(c, redi, FinAdd{});
     if (tid == 0) nf[task] = c;
   }
   if (tid == 0) {
-    ic[I_FLAG] = ws.ic[WI_FLAG];
+    ic[FI_FLAG] = ws.ic[WI_FLAG];
+    sc[FS_AA] = aa;
     for (int j = 0; j < FIN_RHO_MAX + 2; ++j) fm[j] = 0.0;
   }
   __syncthreads();
@@ -542,19 +402,19 @@ __global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, Wi
   const bool want_b = skato && m > 1 && (int)ws.tsc[(n_rho + 1) * WIDE_TSC] > 0;
   const int ntask = skato && m > 1 ? n_rho + (want_b ? 1 : 0) : 0;
 
-  // 6. the tails (twin: step 6 of k_sets_finish): a WAVE per task, the tasks dealt to the waves in turn, the task's spectrum
-  // dealt across the lanes (every lane holds the same numbers; lane 0 stores them)
+  // the tails: a WAVE per task, the tasks dealt to the waves in turn, the task's spectrum dealt across the lanes (every lane
+  // holds the same numbers; lane 0 stores them)
   for (int j = wv; j < FIN_RHO_MAX + 2; j += nw) {
     if (j == FIN_RHO_MAX + 1) {
       double p = nan;
       bool ok = true;
       if (nskat > 0) {
-        const FinLiu liu = wide_liu_params(ws.ev, nskat);
-        p = wide_mixture_sf(tt, ws.ev, nskat, liu, method, ok);
+        const FinLiu liu = fin_liu_params<FinWave>(ws.ev, nskat);
+        p = fin_mixture_sf<FinWave>(tt, ws.ev, nskat, ws.ev[0], liu, method, ok);
       }
       if (lane == 0) {
         if (!ok) fm[0] = 1.0;
-        sc[S_SKATP] = p;
+        sc[FS_SKATP] = p;
       }
     } else if (j < ntask && j < n_rho) {
       const double* ev = ws.ev + (int64_t)(1 + j) * k;
@@ -565,8 +425,8 @@ __global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, Wi
       bool ok = true;
       FinLiu liu{0.0, 0.0, 0.0, 0.0};
       if (n > 0) {
-        liu = wide_liu_params(ev, n);
-        p = wide_mixture_sf(q, ev, n, liu, method, ok);
+        liu = fin_liu_params<FinWave>(ev, n);
+        p = fin_mixture_sf<FinWave>(q, ev, n, ev[0], liu, method, ok);
       }
       if (lane == 0) {
         if (n > 0) {
@@ -581,160 +441,18 @@ __global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, Wi
     } else if (j < ntask && j == n_rho) {
       const double* ev = ws.ev + (int64_t)(n_rho + 1) * k;
       const int n = nf[n_rho + 1];
-      double mu = 0.0, l2 = 0.0, l4 = 0.0;
-      for (int i = lane; i < n; i += 64) {
-        const double v = ev[i];
-        mu += v;
-        l2 += v * v;
-        l4 += (v * v) * (v * v);
-      }
-      mu = wide_wave_sum(mu);
-      l2 = wide_wave_sum(l2);
-      l4 = wide_wave_sum(l4);
+      const FinMoments b = fin_b_moments<FinWave>(ev, n);
       if (lane == 0) {
-        ic[I_NB] = n;
-        sc[S_MU] = mu;
-        sc[S_SD] = sqrt(2.0 * l2 + 4.0 * aba / s11e);
-        sc[S_DF] = l2 * l2 / l4;
+        ic[FI_NB] = n;
+        sc[FS_MU] = b.mu;
+        sc[FS_SD] = sqrt(2.0 * b.l2 + 4.0 * aba / s11e);
+        sc[FS_DF] = b.l2 * b.l2 / b.l4;
       }
     }
   }
   __syncthreads();
-  // T, its first minimiser, the degenerate rule (twin: behind step 6 of k_sets_finish)
-  if (tid == 0) {
-    const double ps = sc[S_SKATP];
-    row[5] = ps;
-    int flag = ic[I_FLAG];
-    for (int j = 0; j < 1 + FIN_RHO_MAX; ++j)
-      if (fm[j] != 0.0) flag |= FIN_F_ROOT;
-    int deg = 1;
-    double T = nan;
-    int j0 = 0;
-    if (skato) {
-      flag |= FIN_F_SKATO;
-      if (m == 1) {
-        for (int j = 0; j < n_rho; ++j) prho[j] = ps;
-        T = ps;
-      } else {
-        bool any_nan = false;
-        T = prho[0];
-        for (int j = 0; j < n_rho; ++j) {
-          any_nan = any_nan || !(prho[j] == prho[j]);
-          if (prho[j] < T) {
-            T = prho[j];
-            j0 = j;
-          }
-        }
-        if (any_nan) T = nan;
-        deg = any_nan || !want_b || ic[I_NB] == 0 || !(T > 0.0);
-      }
-      if (deg) {
-        const bool same = m == 1 || !want_b || ic[I_NB] == 0;
-        row[6] = T;
-        row[7] = T;
-        row[8] = T == T ? grid.rho[same ? 0 : j0] : nan;
-        flag |= FIN_F_DEGENERATE;
-      }
-      for (int j = 0; j < n_rho; ++j) row[FIN_HEAD + j] = prho[j];
-    } else {
-      row[6] = row[7] = row[8] = nan;
-      for (int j = 0; j < n_rho; ++j) row[FIN_HEAD + j] = nan;
-    }
-    sc[S_T] = T;
-    ic[I_J0] = j0;
-    ic[I_DEG] = skato ? deg : 1;
-    ic[I_FLAG] = flag;
-  }
-  __syncthreads();
-  if (ic[I_DEG]) {
-    if (tid == 0) row[9] = (double)ic[I_FLAG];
-    return;  // (the whole workgroup)
-  }
-
-  // 7. the quantiles, the lines, the break points and the integral (twin: step 7 of k_sets_finish, line by line)
-  const double T = sc[S_T];
-  for (int j = wv; j < n_rho; j += nw) {
-    if (lane != 0) continue;
-    bool ok;
-    const double l = ll[j], rho = fmin(grid.rho[j], FIN_RHO_CAP);
-    const double qmin = (fin_chi2_isf(T, l, ok) - l) / sqrt(2.0 * l) * lsd[j] + lc1[j];
-    const double tau = rho * s11e + (1.0 - rho) * aa / s11e;
-    al[j] = qmin / (1.0 - rho);
-    be[j] = tau / (1.0 - rho);
-    fm[1 + j] = ok ? 0.0 : 1.0;
-  }
-  __syncthreads();
-  const double mu = sc[S_MU], sd = sc[S_SD], df = sc[S_DF];
-  if (tid == 0) {
-    const double level = mu - sd * sqrt(0.5 * df);
-    double x0 = INFINITY;
-    for (int j = 0; j < n_rho; ++j) x0 = fmin(x0, (al[j] - level) / be[j]);
-    const double z0 = x0 > 0.0 ? sqrt(x0) : 0.0;
-    sc[S_Z0] = z0;
-    sc[S_END] = fmin(z0, FIN_Z_END);
-    for (int j = 0; j < n_rho; ++j)
-      if (fm[1 + j] != 0.0) ic[I_FLAG] |= FIN_F_ROOT;
-  }
-  __syncthreads();
-  const double z0 = sc[S_Z0], end = sc[S_END];
-  const int npair = n_rho * (n_rho - 1) / 2, npts = npair + 2;
-  for (int at = tid; at < npts; at += nt) {
-    double z = end;
-    if (at == 0) {
-      z = 0.0;
-    } else if (at >= 2) {
-      int i = 0, rest = at - 2;
-      while (rest >= n_rho - 1 - i) {
-        rest -= n_rho - 1 - i;
-        ++i;
-      }
-      const int j = i + 1 + rest;
-      if (be[i] != be[j]) {
-        const double x = (al[i] - al[j]) / (be[i] - be[j]);
-        if (x > 0.0 && sqrt(x) < end) z = sqrt(x);
-      }
-    }
-    pts[at] = z;
-  }
-  __syncthreads();
-  for (int at = tid; at < npts; at += nt) {
-    const double v = pts[at];
-    int rank = 0;
-    for (int j = 0; j < npts; ++j) rank += (pts[j] < v || (pts[j] == v && j < at)) ? 1 : 0;
-    spts[rank] = v;
-  }
-  __syncthreads();
-  const double sq = sqrt(2.0 * df);
-  const int node = tid & (FIN_GL - 1), grp = tid / FIN_GL, ngrp = nt / FIN_GL;
-  const int hn = node < FIN_GL / 2 ? FIN_GL / 2 - 1 - node : node - FIN_GL / 2;
-  const double xn = node < FIN_GL / 2 ? -FIN_GL_X[hn] : FIN_GL_X[hn];
-  for (int base = 0; base < npts - 1; base += ngrp) {
-    const int piece = base + grp;
-    double term = 0.0;
-    if (piece < npts - 1) {
-      const double lo = spts[piece], hi = spts[piece + 1];
-      if (hi > lo) {
-        const double v = 0.5 + 0.5 * xn, z = hi - (hi - lo) * (v * v);
-        double del = INFINITY;
-        for (int j = 0; j < n_rho; ++j) del = fmin(del, al[j] - be[j] * (z * z));
-        const double arg = (del - mu) / sd * sq + df;
-        term = (hi - lo) * v * FIN_GL_W[hn] * fin_chi2_sf(arg, df) * (0.79788456080286535588 * exp(-0.5 * z * z));   // 2 phi(z)
-      }
-    }
-#pragma unroll
-    for (int o = FIN_GL / 2; o > 0; o >>= 1) term += __shfl_down(term, o, FIN_GL);
-    if (node == 0 && piece < npts - 1) pts[piece] = term;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double integral = 0.0;
-    for (int piece = 0; piece < npts - 1; ++piece) integral += pts[piece];
-    const double p = integral + erfc(z0 * 0.70710678118654752440);
-    row[6] = fmin(p, (double)n_rho * T);
-    row[7] = T;
-    row[8] = grid.rho[ic[I_J0]];
-    row[9] = (double)ic[I_FLAG];
-  }
+  if (fin_skato_decide(tail, m, nskat, want_b, n_rho, 0, grid, row)) return;  // (the whole workgroup)
+  fin_skato_integral(tail, n_rho, s11e, grid, row);
 }
 
 }  // namespace scilmm
