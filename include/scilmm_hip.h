@@ -576,6 +576,75 @@ int scilmm_sets_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dt
  * ms[0] k_sets_spa (tools/sets_timing.py --binary).  No counterpart in the reference. */
 int scilmm_sets_spa_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Binary traits, ONE variant set of k markers, 1 <= k <= 4 096, that runs as B = ceil(k / block) sub-blocks (DESIGN.md section
+ * 23): what scilmm_sets_spa*_dev does for the sets of one block, cut where a sub-block ends.  Three pieces:
+ *
+ * (a) scilmm_sets_collapse*_dev, queued BEHIND the Gram entry point of a sub-block, on the handle's stream: the collapsed
+ * genotype g_B = sum_j w_j g~_j of the set grows by the sub-block's kept markers.
+ *   the form's marker arguments and r: as for the scilmm_scan_spa*_dev twin (the sub-block's rows).
+ *   d_stats    : the sub-block's (q + 4) x r statistics; rows 0 .. 2 (n_obs, mean, css) are read.
+ *   weight_mode, d_weights: as for scilmm_sets_finish_dev; d_weights holds the sub-block's r entries (mode 2).
+ *   first      : 1 for the set's first sub-block (the row starts from 0), 0 otherwise (it starts from what d_gB holds).
+ *   d_gB       : n doubles, the caller's, in the ORIGINAL order of the individuals.
+ * For every individual i: acc = first ? 0 : d_gB[i]; for the sub-block's kept markers j (an observed value and variation, as
+ * scilmm_sets_finish_dev keeps them) in ascending column order acc = fma(w_j, g~_ji, acc), g~ the centred, mean-imputed value the
+ * saddlepoint kernels read; d_gB[i] = acc.  An individual's value is ONE fma chain over the set's kept markers in the order
+ * given: the row carries the same bits however the set is cut into sub-blocks, and from int8, .bed and hard-call dosage rows
+ * alike.  A sub-block with nothing kept leaves the row as it is (zero if first).  A thread per individual on a capped grid with a
+ * fixed stride, the reads of a marker row along the lanes; no atomics, nothing allocated, nothing of the work buffers or of the
+ * saddlepoint scratch written: scilmm_scan_panel_dev and scilmm_scan_block_keep_dev may still follow the block.
+ * SCILMM_ERR_ARG before anything is dereferenced: what the form's scilmm_scan_spa*_dev rejects of its marker arguments and r, a
+ * null fac, d_stats or d_gB, first outside 0 / 1, an unknown weight mode, mode 2 without d_weights.  Refusals as for the scan
+ * blocks.
+ *
+ * (b) scilmm_sets_spa_wide_dev, queued behind the last sub-block (its Gram entry point, saddlepoint call, collapse and panel):
+ * the set's variance scales and the saddlepoint p-value of its burden.  It reads no genotypes.
+ *   k, block, q, d_stats, d_gram, d_cross, ld_cross: the slices of scilmm_sets_finish_wide_dev.
+ *   d_R, d_u, d_mu, d_C, c, d_Minv, cutoff: as for scilmm_sets_spa_dev.
+ *   d_spa      : B slices at a stride of 7 block doubles; slice b is the 7 x r_b rows scilmm_scan_spa*_dev wrote for sub-block b.
+ *   weight_mode, d_weights: as above; d_weights holds k entries, one per marker of the set.
+ *   d_gB       : n doubles: in, the collapsed row; where the burden is attempted it is overwritten with g^_B, as
+ *                scilmm_sets_spa_dev overwrites its scratch row.
+ *   d_bspa     : ONE row of 13 doubles in the layout of scilmm_sets_spa_dev.
+ *   d_vscale   : k doubles: rho_j sqrt(phi) for a kept marker, 1.0 for a dropped one.
+ * Every number is defined as for scilmm_sets_spa_dev.  The pair sums a_B and V_Q are taken row by row (each row in ascending
+ * column order, folded by a fixed tree, two partials per row in HBM) and the rows folded in a fixed order: they agree with
+ * scilmm_sets_spa_dev's to rounding, not bit for bit.  A set with nothing kept: flag 0, n_adj 0, the other eleven numbers NaN,
+ * every scale 1.0.  No atomics; scilmm_timing.n_float_atomic_launches is not touched.  The work space is the wide finish's, by
+ * its growth rule: grown for a wider set behind a stream synchronise, and the finish that follows for the same k allocates
+ * nothing.  SCILMM_ERR_ARG before anything is dereferenced: a null fac, d_stats, d_gram, d_R, d_u, d_mu, d_C, d_Minv, d_spa, d_gB,
+ * d_bspa or d_vscale, what scilmm_sets_finish_wide_dev rejects of k, block, d_cross and ld_cross, c outside 1 .. 31, q != c + 1, a
+ * negative or NaN cutoff, an unknown weight mode, mode 2 without d_weights.  Refusals as for the scan blocks.
+ *
+ * (c) scilmm_sets_finish_wide_scaled_dev: scilmm_sets_finish_wide_dev with a variance scale per marker of the set, in A alone:
+ * A = diag(w o scale) K diag(w o scale), while t = w o s keeps w.
+ *   d_vscale   : k doubles on the device, what scilmm_sets_spa_wide_dev wrote; null is SCILMM_ERR_ARG.
+ * flags: bit 4 (16) is set where a kept marker's scale is not 1.  With every scale 1.0 the row is the bits of
+ * scilmm_sets_finish_wide_dev (w * 1.0 = w), which passes none.  scilmm_sets_finish_wide_timing reports either.
+ *
+ * scilmm_amd.glmm.BinaryWideSetTest (NullModel.sets(max_markers=...)) is the interface.  No counterpart in the reference. */
+int scilmm_sets_collapse_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats,
+                             int32_t weight_mode, const double* d_weights, int32_t first, double* d_gB);
+int scilmm_sets_collapse_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                                 int32_t flags, int32_t r, const double* d_stats, int32_t weight_mode, const double* d_weights,
+                                 int32_t first, double* d_gB);
+int scilmm_sets_collapse_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                    const int32_t* d_sample, int32_t r, const double* d_stats, int32_t weight_mode,
+                                    const double* d_weights, int32_t first, double* d_gB);
+int scilmm_sets_spa_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
+                             const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, const double* d_mu,
+                             const double* d_C, int32_t c, const double* d_Minv, double cutoff, const double* d_spa, int32_t weight_mode,
+                             const double* d_weights, double* d_gB, double* d_bspa, double* d_vscale);
+int scilmm_sets_finish_wide_scaled_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
+                                       const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, int32_t c,
+                                       int32_t weight_mode, const double* d_weights, int32_t method, const double* rho, int32_t n_rho,
+                                       double* d_out, double* d_lam, const double* d_vscale);
+
+/* HIP-event times on the handle, in milliseconds, valid after the scilmm_sync that follows the call: ms[0] k_sets_collapse of the
+ * last scilmm_sets_collapse*_dev; of the last scilmm_sets_spa_wide_dev ms[1] markers + pairs and ms[2] the burden kernel
+ * (tools/sets_timing.py --binary-wide).  No counterpart in the reference. */
+int scilmm_sets_spa_wide_timing(const scilmm_symbolic* sym, double* ms);
+
 /* One block of BLUP predictions on the device: with the scan's w(b) = L^-1 P b and Q = [w(C) | w(y)], the right-hand-side
  * block is r columns g of a relationship matrix instead of r markers, and what comes back gives g' P_V g and g' P_V y
  * (P_V = V^-1 - V^-1 C (C' V^-1 C)^-1 C' V^-1) per column by the scan's algebra: predicted value, prediction error variance

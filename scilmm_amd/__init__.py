@@ -15,7 +15,7 @@ from .bed import BedFile  # noqa: F401
 from .blup import BLUP  # noqa: F401
 from .gxe import InteractionScan  # noqa: F401
 from .panel import TraitPanel, panel_stats, panel_thresholds  # noqa: F401
-from .glmm import LogisticMixedModel, BinaryScan, BinarySetTest  # noqa: F401
+from .glmm import LogisticMixedModel, BinaryScan, BinarySetTest, BinaryWideSetTest  # noqa: F401
 from . import dosage  # noqa: F401
 from .sets import VariantSetTest  # noqa: F401
 from ._lib import ScilmmError, NotPositiveDefiniteError  # noqa: F401

@@ -84,6 +84,8 @@ SYMBOLS = [
     "scilmm_sets_finish_dev", "scilmm_sets_finish_timing", "scilmm_sets_finish_scaled_dev",
     "scilmm_sets_finish_wide_dev", "scilmm_sets_finish_wide_timing",
     "scilmm_sets_spa_dev", "scilmm_sets_spa_bed_dev", "scilmm_sets_spa_dosage_dev", "scilmm_sets_spa_timing",
+    "scilmm_sets_collapse_dev", "scilmm_sets_collapse_bed_dev", "scilmm_sets_collapse_dosage_dev",
+    "scilmm_sets_spa_wide_dev", "scilmm_sets_finish_wide_scaled_dev", "scilmm_sets_spa_wide_timing",
 ]
 
 _lib = None
@@ -206,6 +208,14 @@ def lib():
     L.scilmm_sets_spa_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32] + sspa
     L.scilmm_sets_spa_dosage_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32] + sspa
     L.scilmm_sets_spa_timing.argtypes = [vp, P(dbl)]
+    coll = [vp, i32, vp, i32, vp]                               # d_stats, weight_mode, d_weights, first, d_gB
+    L.scilmm_sets_collapse_dev.argtypes = [vp, vp, i64, i32] + coll
+    L.scilmm_sets_collapse_bed_dev.argtypes = [vp, vp, i64, i32, vp, i32, i32] + coll
+    L.scilmm_sets_collapse_dosage_dev.argtypes = [vp, vp, i32, i64, i32, vp, i32] + coll
+    # k, block, q, d_stats, d_gram, d_cross, ld_cross, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa, weight_mode, d_weights, d_gB, d_bspa, d_vscale
+    L.scilmm_sets_spa_wide_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, dbl, vp, i32, vp, vp, vp, vp]
+    L.scilmm_sets_finish_wide_scaled_dev.argtypes = L.scilmm_sets_finish_wide_dev.argtypes + [vp]     # ... d_vscale
+    L.scilmm_sets_spa_wide_timing.argtypes = [vp, P(dbl)]
     L.scilmm_rel_block_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_rows_block_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
     L.scilmm_order.argtypes = [i32, vp, vp, i32, vp]

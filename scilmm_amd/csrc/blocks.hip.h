@@ -371,19 +371,25 @@ struct WideArgs {
   const double* rho;
   int32_t n_rho;
   double *d_out, *d_lam;
+  const double* d_vscale = nullptr;   // the markers' variance scales (scilmm_sets_finish_wide_scaled_dev), or null: all 1
   int32_t bp() const { return (block + 15) / 16 * 16; }
   int32_t nsub() const { return (k + block - 1) / block; }
   // before anything of the handle is read
+  // the shape of a wide set's pieces, which the set saddlepoint checks as well
+  static bool shape_ok(int32_t k, int32_t block, const double* d_cross, int64_t ld_cross) {
+    if (k < 1 || k > WIDE_KMAX || block < 1 || block > RPMAX) return false;
+    const int32_t nsub = (k + block - 1) / block;
+    const int64_t kept = (int64_t)(nsub - 1) * ((block + 15) / 16 * 16);    // the columns of the cross store
+    return kept <= WIDE_KMAX && (nsub == 1) == (d_cross == nullptr) && (nsub == 1 || ld_cross >= kept);
+  }
   static bool args_ok(const scilmm_factor* fac, const WideArgs& a) {
-    if (!fac || !fin_args_ok(a) || a.k < 1 || a.k > WIDE_KMAX || a.block < 1 || a.block > RPMAX) return false;
-    const int64_t kept = (int64_t)(a.nsub() - 1) * a.bp();    // the columns of the cross store
-    if (kept > WIDE_KMAX || (a.nsub() == 1) != (a.d_cross == nullptr) || (a.nsub() > 1 && a.ld_cross < kept)) return false;
+    if (!fac || !fin_args_ok(a) || !shape_ok(a.k, a.block, a.d_cross, a.ld_cross)) return false;
     return fac->sym && fac->sym->S;  // (what needs no handle has been checked: with it wrong, nothing of the handle is read)
   }
 };
 
-// Everything after the sub-blocks of ONE set of up to 4 096 markers (scilmm_sets_finish_wide_dev; setwide.hip.h, DESIGN.md section
-// 22): the refusals of sets_finish, the work space (grown for a wider set only: the stream is synchronised first, and nothing is
+// Everything after the sub-blocks of ONE set of up to 4 096 markers (scilmm_sets_finish_wide_dev and, with the markers' variance
+// scales, scilmm_sets_finish_wide_scaled_dev; setwide.hip.h): the refusals of sets_finish, the work space (grown for a wider set only: the stream is synchronised first, and nothing is
 // allocated afterwards for the same or a narrower set), then plain launches between the call's own events -- prep, form, burden |
 // the pre-step and k - 1 steps of the reduction, two launches each, sized by k (the number of kept markers is the device's) |
 // scale, eig | tails.  Nothing of the factor is read and nothing of the work buffers is touched.
@@ -406,7 +412,7 @@ int sets_finish_wide(scilmm_factor* fac, const WideArgs& a, const char* who) {
   hipStream_t s0 = D->stream;
   HIPCHK(hipEventRecord(D->wide_ev[0], s0));
   hipLaunchKernelGGL(k_wide_prep, dim3(1), dim3(WIDE_PREP_NT), 0, s0, in, a.c, a.d_R, a.d_u, a.weight_mode, a.d_weights, ws, a.n_rho, a.d_out,
-                     a.d_lam);
+                     a.d_lam, a.d_vscale);
   hipLaunchKernelGGL(k_wide_form, dim3((unsigned)k), dim3(256), 0, s0, in, a.c, ws);
   hipLaunchKernelGGL(k_wide_burden, dim3(1), dim3(256), 0, s0, ws, a.d_out);
   HIPCHK(hipEventRecord(D->wide_ev[1], s0));
@@ -468,6 +474,98 @@ int sets_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const Se
                      a.d_weights, D->spa_scratch, a.d_bspa, a.d_vscale);
   HIPCHK(hipEventRecord(D->sspa_ev[1], s0));
   D->sspa_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
+// The collapsed genotype of a wide set, grown by the kept markers of the sub-block queued before this call
+// (scilmm_sets_collapse*_dev; setspawide.hip.h): the refusals of the scan blocks, k_sets_collapse between the
+// call's own events, a capped grid over the individuals.  Nothing is allocated and nothing of the work buffers or of the
+// saddlepoint scratch is touched: the panel and the keep may still follow the block.
+struct CollapseArgs {
+  const double* d_stats;
+  int32_t weight_mode;
+  const double* d_weights;
+  int32_t first;
+  double* d_gB;
+  // before anything of the handle is read
+  static bool args_ok(const scilmm_factor* fac, int32_t r, const CollapseArgs& a) {
+    return fac && a.d_stats && a.d_gB && r >= 1 && r <= RPMAX && (a.first == 0 || a.first == 1) && fin_weights_ok(a.weight_mode, a.d_weights) &&
+           fac->sym && fac->sym->S;
+  }
+};
+
+template <class Reader>
+int sets_collapse(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const CollapseArgs& a) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const int32_t n = sym->S->n;
+  if (!D->coll_ev[0])
+    for (auto& e : D->coll_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  const unsigned wgs = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)n + 255) / 256, COLLAPSE_GRID));
+  HIPCHK(hipEventRecord(D->coll_ev[0], s0));
+  hipLaunchKernelGGL(k_sets_collapse<Reader>, dim3(wgs), dim3(256), 0, s0, n, r, rd, a.d_stats, a.weight_mode, a.d_weights, a.first, a.d_gB);
+  HIPCHK(hipEventRecord(D->coll_ev[1], s0));
+  D->coll_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
+// What scilmm_sets_spa_wide_dev takes beside the factor.
+struct SpaWideArgs {
+  int32_t k, block, q;
+  const double *d_stats, *d_gram, *d_cross;
+  int64_t ld_cross;
+  const double *d_R, *d_u, *d_mu, *d_C;
+  int32_t c;
+  const double* d_Minv;
+  double cutoff;
+  const double* d_spa;
+  int32_t weight_mode;
+  const double* d_weights;
+  double *d_gB, *d_bspa, *d_vscale;
+  // before anything of the handle is read (a NaN cutoff fails the comparison)
+  static bool args_ok(const scilmm_factor* fac, const SpaWideArgs& a) {
+    if (!fac || !a.d_stats || !a.d_gram || !a.d_R || !a.d_u || !a.d_mu || !a.d_C || !a.d_Minv || !a.d_spa || !a.d_gB || !a.d_bspa ||
+        !a.d_vscale || a.c < 1 || a.c > SPA_CMAX || a.q != a.c + 1 || !(a.cutoff >= 0.0) || !fin_weights_ok(a.weight_mode, a.d_weights) ||
+        !WideArgs::shape_ok(a.k, a.block, a.d_cross, a.ld_cross))
+      return false;
+    return fac->sym && fac->sym->S;
+  }
+};
+
+// The variance scales and the burden's saddlepoint p-value of ONE set of up to 4 096 markers behind its last sub-block
+// (scilmm_sets_spa_wide_dev; setspawide.hip.h): the refusals of the scan blocks, the wide finish's work
+// space by the wide finish's growth rule (the finish that follows for the same k allocates nothing), then keep, markers, pairs | burden
+// between the call's own events.  No genotype is read: the collapsed row is the caller's.
+int sets_spa_wide(scilmm_factor* fac, const SpaWideArgs& a, const char* who) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const int32_t k = a.k, n = sym->S->n;
+  const size_t need = wide_doubles((size_t)k);
+  if (D->wide_ws_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  TRY(grow(sym, &D->wide_ws, &D->wide_ws_cap, need));
+  if (!D->swide_ev[0])
+    for (auto& e : D->swide_ev) HIPCHK(hipEventCreate(&e));
+  const SwideWs ws = swide_cut(D->wide_ws, (size_t)k);
+  const WideIn in{k, a.block, (a.block + 15) / 16 * 16, a.q, a.d_stats, a.d_gram, a.d_cross, a.ld_cross};
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->swide_ev[0], s0));
+  hipLaunchKernelGGL(k_swide_keep, dim3(1), dim3(WIDE_PREP_NT), 0, s0, in, ws);
+  hipLaunchKernelGGL(k_swide_markers, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, s0, in, a.c, a.d_R, a.d_u, a.d_spa, a.weight_mode,
+                     a.d_weights, ws);
+  hipLaunchKernelGGL(k_swide_pairs, dim3((unsigned)k), dim3(256), 0, s0, in, a.c, ws);
+  HIPCHK(hipEventRecord(D->swide_ev[1], s0));
+  hipLaunchKernelGGL(k_swide_burden, dim3(1), dim3(256), 0, s0, in, n, a.c, a.d_mu, a.d_C, a.d_Minv, a.cutoff, ws, a.d_gB, a.d_bspa, a.d_vscale);
+  HIPCHK(hipEventRecord(D->swide_ev[2], s0));
+  D->swide_pending = true;
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }

@@ -351,6 +351,11 @@ struct Dev {
   hipEvent_t wide_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // begin | A formed | reduced | spectra | tails done
   bool wide_pending = false;            // a wide finish whose events have not been read yet (scilmm_sync)
   double wide_ms[4] = {0.0, 0.0, 0.0, 0.0};  // the last call's prep + form | reduction | eigenvalues | tails (scilmm_sets_finish_wide_timing)
+  // the set saddlepoint of a wide set (scilmm_sets_collapse*_dev, scilmm_sets_spa_wide_dev): it cuts wide_ws its own way (SwideWs)
+  hipEvent_t coll_ev[2] = {nullptr, nullptr};           // k_sets_collapse begin | done (the first collapse creates them)
+  hipEvent_t swide_ev[3] = {nullptr, nullptr, nullptr};  // begin | markers + pairs done | k_swide_burden done
+  bool coll_pending = false, swide_pending = false;     // calls whose events have not been read yet (scilmm_sync)
+  double swide_ms[3] = {0.0, 0.0, 0.0};  // the last collapse | the last call's markers + pairs | its burden kernel (scilmm_sets_spa_wide_timing)
   void clear_block() { block_r = block_rp = 0; }
 };
 

@@ -1,9 +1,9 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setmath.hip.h, setfinish.hip.h, setwide.hip.h, setspa.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setmath.hip.h, setfinish.hip.h, setwide.hip.h, setspa.hip.h, setspawide.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_wide, sets_spa, rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide, rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
@@ -39,6 +39,7 @@
 #include "setfinish.hip.h"
 #include "setwide.hip.h"
 #include "setspa.hip.h"
+#include "setspawide.hip.h"
 #include "blup.hip.h"
 #include "dev.h"
 #include "host_threads.h"
@@ -388,6 +389,59 @@ int scilmm_sets_finish_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, in
   return sets_finish_wide(fac, a, __func__);
 }
 
+// ... with the variance scales of the set's markers (scilmm_sets_spa_wide_dev) in the weights of A
+int scilmm_sets_finish_wide_scaled_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
+                                       const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, int32_t c,
+                                       int32_t weight_mode, const double* d_weights, int32_t method, const double* rho, int32_t n_rho,
+                                       double* d_out, double* d_lam, const double* d_vscale) {
+  const WideArgs a{k, block, q, d_stats, d_gram, d_cross, ld_cross, d_R, d_u, c, weight_mode, d_weights, method, rho, n_rho, d_out, d_lam,
+                   d_vscale};
+  if (!d_vscale || !WideArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_finish_wide(fac, a, __func__);
+}
+
+// The collapsed genotype of a wide set behind a sub-block's Gram entry point: the form's marker arguments are checked as its
+// scan_spa twin checks them
+int scilmm_sets_collapse_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats,
+                             int32_t weight_mode, const double* d_weights, int32_t first, double* d_gB) {
+  const CollapseArgs a{d_stats, weight_mode, d_weights, first, d_gB};
+  if (!d_geno || !CollapseArgs::args_ok(fac, r, a) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
+  return sets_collapse(fac, __func__, r, SpaInt8{d_geno, ld_geno}, a);
+}
+
+int scilmm_sets_collapse_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
+                                 int32_t flags, int32_t r, const double* d_stats, int32_t weight_mode, const double* d_weights,
+                                 int32_t first, double* d_gB) {
+  const CollapseArgs a{d_stats, weight_mode, d_weights, first, d_gB};
+  if (!d_bed || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) || !CollapseArgs::args_ok(fac, r, a) ||
+      (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return sets_collapse(fac, __func__, r, SpaBed{d_bed, ld_bed, n_samples, d_sample, flags}, a);
+}
+
+int scilmm_sets_collapse_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
+                                    const int32_t* d_sample, int32_t r, const double* d_stats, int32_t weight_mode,
+                                    const double* d_weights, int32_t first, double* d_gB) {
+  const CollapseArgs a{d_stats, weight_mode, d_weights, first, d_gB};
+  if (!d_dos || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
+      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
+      !CollapseArgs::args_ok(fac, r, a) || (!d_sample && n_samples != fac->sym->S->n))
+    return SCILMM_ERR_ARG;
+  return dtype == SCILMM_DOSAGE_U16 ? sets_collapse(fac, __func__, r, SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}, a)
+                                    : sets_collapse(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
+}
+
+// The variance scales and the burden saddlepoint of ONE wide set behind its last sub-block: it reads no genotypes, so there is one
+int scilmm_sets_spa_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
+                             const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, const double* d_mu,
+                             const double* d_C, int32_t c, const double* d_Minv, double cutoff, const double* d_spa, int32_t weight_mode,
+                             const double* d_weights, double* d_gB, double* d_bspa, double* d_vscale) {
+  const SpaWideArgs a{k, block, q, d_stats, d_gram, d_cross, ld_cross, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa, weight_mode, d_weights,
+                      d_gB, d_bspa, d_vscale};
+  if (!SpaWideArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_spa_wide(fac, a, __func__);
+}
+
 // The sets' variance scales and burden saddlepoint p-values behind a Gram block and its markers' saddlepoint call: the form's
 // marker arguments are checked as its scan_spa twin checks them
 int scilmm_sets_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats, const double* d_gram,
@@ -654,6 +708,20 @@ int scilmm_sync(scilmm_symbolic* sym) {
     HIPCHK(hipEventElapsedTime(&a, D->sspa_ev[0], D->sspa_ev[1]));
     D->sspa_ms = a;
   }
+  if (D->coll_pending) {
+    D->coll_pending = false;
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->coll_ev[0], D->coll_ev[1]));
+    D->swide_ms[0] = a;
+  }
+  if (D->swide_pending) {
+    D->swide_pending = false;
+    for (int i = 0; i < 2; ++i) {
+      float a = 0;
+      HIPCHK(hipEventElapsedTime(&a, D->swide_ev[i], D->swide_ev[i + 1]));
+      D->swide_ms[1 + i] = a;
+    }
+  }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
 }
@@ -717,6 +785,13 @@ int scilmm_sets_finish_wide_timing(const scilmm_symbolic* sym, double* ms) {
 int scilmm_sets_spa_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   ms[0] = ((const Dev*)sym->device)->sspa_ms;
+  return SCILMM_OK;
+}
+
+int scilmm_sets_spa_wide_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const Dev* D = (const Dev*)sym->device;
+  for (int i = 0; i < 3; ++i) ms[i] = D->swide_ms[i];
   return SCILMM_OK;
 }
 

@@ -39,6 +39,10 @@ void dev_free(void* p) {
   if (D->wide_ws) (void)hipFree(D->wide_ws);
   for (auto& e : D->wide_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->coll_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->swide_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->spa_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->fin_ev)

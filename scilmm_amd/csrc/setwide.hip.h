@@ -2,7 +2,8 @@
 // section 22): the set's sub-blocks left their statistics, their diagonal blocks of X'X and their rows of cross products in HBM;
 // the finish needs no eigenvector.  One orthogonal reduction of A = diag(w) K diag(w) to a tridiagonal T whose first basis vector
 // is 1 / sqrt(m) gives every spectrum of SKAT-O as the eigenvalues of a tridiagonal matrix:
-//   k_wide_prep   : one workgroup; the kept markers (in order, by a prefix sum), z = R^-T w(C)'x, the weights, t = w o s;
+//   k_wide_prep   : one workgroup; the kept markers (in order, by a prefix sum), z = R^-T w(C)'x, the weights, t = w o s; with
+//                   the markers' variance scales (scilmm_sets_finish_wide_scaled_dev) the weight in A is w o scale, t keeps w;
 //   k_wide_form   : a workgroup per kept row; A, compacted (m x m, ld = m, symmetric bit for bit), its row sums and diagonal;
 //   k_wide_burden : one workgroup; 1'A1, 1't, t't, trace, the burden numbers and Q into the output row;
 //   k_wide_symv, k_wide_rank2 : the reduction, two launches per step.  Step -1 is the Householder reflector that maps 1 to
@@ -31,7 +32,7 @@ constexpr int WIDE_PREP_NT = 1024;
 constexpr int WIDE_BISECT = 100;                 // bisection steps at most (54 halve a Gershgorin interval to eps |T|)
 constexpr int WIDE_TSC = 8;                      // doubles of a task's record: order | lower end | upper end | pivmin | atol
 enum { WS_TAU = 0, WS_SCALE, WS_WS, WS_TT, WS_S11, WS_TR, WS_N = 16 };   // scalars of the work space
-enum { WI_M = 0, WI_FLAG, WI_N = 16 };                                   // integers of the work space
+enum { WI_M = 0, WI_FLAG, WI_SCALED, WI_N = 16 };                        // integers of the work space (WI_SCALED: FIN_F_SCALED or 0)
 
 // The handle's work space of one call, cut for a set of k markers and c covariates.
 struct WideWs {
@@ -85,9 +86,11 @@ struct WideIn {
 };
 
 // Steps 0 and 1 of k_sets_finish for k <= 4 096: one workgroup of WIDE_PREP_NT threads, a run of consecutive markers each.
+// vscale: k variance scales, one per marker of the set, or null (all 1).
 __global__ __launch_bounds__(WIDE_PREP_NT) void k_wide_prep(WideIn in, int32_t c, const double* __restrict__ R, const double* __restrict__ u,
                                                             int32_t wmode, const double* __restrict__ weights, WideWs ws, int32_t n_rho,
-                                                            double* __restrict__ row, double* __restrict__ lam_out) {
+                                                            double* __restrict__ row, double* __restrict__ lam_out,
+                                                            const double* __restrict__ vscale) {
   __shared__ int32_t cnt[WIDE_PREP_NT];
   const int tid = threadIdx.x, k = in.k;
   const int per = (k + WIDE_PREP_NT - 1) / WIDE_PREP_NT, i0 = min(k, tid * per), i1 = min(k, i0 + per);
@@ -108,6 +111,7 @@ __global__ __launch_bounds__(WIDE_PREP_NT) void k_wide_prep(WideIn in, int32_t c
   if (tid == 0) {
     ws.ic[WI_M] = m;
     ws.ic[WI_FLAG] = 0;
+    ws.ic[WI_SCALED] = 0;
     if (m == 0) fin_empty_row(row, n_rho);
   }
   if (lam_out)
@@ -118,8 +122,9 @@ __global__ __launch_bounds__(WIDE_PREP_NT) void k_wide_prep(WideIn in, int32_t c
     const double uz = fin_forward(c, R, u, [&](int r) { return in.stat(4 + r, col); }, ws.Z, (int64_t)k, a);
     const double s = in.stat(4 + c, col) - uz;
     const double w = fin_weight(wmode, in.stat(1, col), weights, col);
-    ws.wa[a] = w;
+    ws.wa[a] = vscale ? w * vscale[col] : w;                  // (the weight in A alone: t keeps w)
     ws.t[a] = w * s;
+    if (vscale && vscale[col] != 1.0) ws.ic[WI_SCALED] = FIN_F_SCALED;   // (every writer stores the same value)
   }
 }
 
@@ -392,7 +397,7 @@ __global__ __launch_bounds__(256) void k_wide_tails(int32_t k, int32_t n_rho, Fi
     if (tid == 0) nf[task] = c;
   }
   if (tid == 0) {
-    ic[FI_FLAG] = ws.ic[WI_FLAG];
+    ic[FI_FLAG] = ws.ic[WI_FLAG] | ws.ic[WI_SCALED];
     sc[FS_AA] = aa;
     for (int j = 0; j < FIN_RHO_MAX + 2; ++j) fm[j] = 0.0;
   }

@@ -295,6 +295,13 @@ class Symbolic(object):
         check(lib().scilmm_sets_spa_timing(self._h, ms), self._h)
         return float(ms[0])
 
+    def sets_spa_wide_timing(self):
+        """(the last ``Factor.sets_collapse*_dev``, markers + pairs and the burden kernel of the last ``Factor.sets_spa_wide_dev``)
+        in ms, after ``sync()``."""
+        ms = (C.c_double * 3)()
+        check(lib().scilmm_sets_spa_wide_timing(self._h, ms), self._h)
+        return tuple(float(v) for v in ms)
+
     def timing(self):
         t = _lib.Timing()
         check(lib().scilmm_last_timing(self._h, C.byref(t)), self._h)
@@ -568,6 +575,48 @@ class Factor(object):
     def sets_spa_timing(self):
         """``k_sets_spa`` of the last ``sets_spa*_dev`` on the handle in ms, after ``sync()`` (``Symbolic.sets_spa_timing``)."""
         return self.sym.sets_spa_timing()
+
+    def sets_collapse_dev(self, dG_ptr, ld, r, dstats_ptr, weight_mode, dweights_ptr, first, dgB_ptr):
+        """The collapsed genotype of a wide set grown by the kept markers of the sub-block queued before it
+        (``scilmm_sets_collapse_dev``): ``dstats_ptr`` the sub-block's statistics, ``dweights_ptr`` its ``r`` weights (mode 2),
+        ``first`` whether the row starts from zero, ``dgB_ptr`` n doubles; enqueues without synchronising
+        (``scilmm_amd.glmm.BinaryWideSetTest`` is the interface)."""
+        check(lib().scilmm_sets_collapse_dev(self._h, dG_ptr, ld, r, dstats_ptr, weight_mode, dweights_ptr, int(bool(first)), dgB_ptr),
+              self.sym._h)
+
+    def sets_collapse_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, weight_mode, dweights_ptr, first, dgB_ptr):
+        """``sets_collapse_dev`` behind a sub-block of packed PLINK rows (``scilmm_sets_collapse_bed_dev``)."""
+        check(lib().scilmm_sets_collapse_bed_dev(self._h, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, weight_mode,
+                                                 dweights_ptr, int(bool(first)), dgB_ptr), self.sym._h)
+
+    def sets_collapse_dosage_dev(self, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dstats_ptr, weight_mode, dweights_ptr, first,
+                                 dgB_ptr):
+        """``sets_collapse_dev`` behind a sub-block of dosage rows (``scilmm_sets_collapse_dosage_dev``)."""
+        check(lib().scilmm_sets_collapse_dosage_dev(self._h, ddos_ptr, dtype, ld, n_samples, dsample_ptr, r, dstats_ptr, weight_mode,
+                                                    dweights_ptr, int(bool(first)), dgB_ptr), self.sym._h)
+
+    def sets_spa_wide_dev(self, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c, dMinv_ptr,
+                          cutoff, dspa_ptr, weight_mode, dweights_ptr, dgB_ptr, dbspa_ptr, dvscale_ptr):
+        """The variance scales (``k`` doubles to ``dvscale_ptr``) and the burden saddlepoint row (13 doubles to ``dbspa_ptr``) of ONE
+        set of ``k`` <= 4096 markers behind its last sub-block (``scilmm_sets_spa_wide_dev``): the slices of
+        ``sets_finish_wide_dev``, the markers' saddlepoint rows at a stride of ``7 block`` and the collapsed row ``dgB_ptr``;
+        enqueues without synchronising."""
+        check(lib().scilmm_sets_spa_wide_dev(self._h, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr, dmu_ptr,
+                                             dC_ptr, c, dMinv_ptr, cutoff, dspa_ptr, weight_mode, dweights_ptr, dgB_ptr, dbspa_ptr,
+                                             dvscale_ptr), self.sym._h)
+
+    def sets_finish_wide_scaled_dev(self, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr, c, weight_mode,
+                                    dweights_ptr, method, rho, dout_ptr, dlam_ptr, dvscale_ptr):
+        """``sets_finish_wide_dev`` with the markers' variance scales ``dvscale_ptr`` (``k`` doubles, what ``sets_spa_wide_dev``
+        wrote) in the weights of ``A`` alone (``scilmm_sets_finish_wide_scaled_dev``)."""
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        check(lib().scilmm_sets_finish_wide_scaled_dev(self._h, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr,
+                                                       c, weight_mode, dweights_ptr, method, ptr(rho), rho.size, dout_ptr, dlam_ptr,
+                                                       dvscale_ptr), self.sym._h)
+
+    def sets_spa_wide_timing(self):
+        """``Symbolic.sets_spa_wide_timing`` of the handle."""
+        return self.sym.sets_spa_wide_timing()
 
     def scan_spa_bed_dev(self, dbed_ptr, ld, n_samples, dsample_ptr, flags, r, dstats_ptr, dR_ptr, du_ptr, dmu_ptr, dC_ptr, c,
                          dMinv_ptr, cutoff, dspa_ptr):

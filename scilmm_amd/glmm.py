@@ -21,7 +21,8 @@ the variance ratio ``a / a_w`` rescales the score to ``s = b sqrt(a_w / a)`` of 
 
 There is no CPU form of the device side; the argument checks and ``binary_stats`` are pure NumPy.  Out of scope: other families,
 Firth correction, G x E tests for binary traits, distributed handles.  Variant-set tests at a fitted null: ``null.sets()``, a
-``BinarySetTest`` (the method: DESIGN.md section 20; its host algebra: ``scilmm_amd.binary_sets``).
+``BinarySetTest`` (the method: DESIGN.md section 20; its host algebra: ``scilmm_amd.binary_sets``); with sets wider than one device
+block, ``null.sets(max_markers=k)``, a ``BinaryWideSetTest``.
 """
 import numpy as np
 import scipy.linalg as la
@@ -134,9 +135,13 @@ class NullModel(object):
         """The score scan with saddlepoint p-values at this null: a ``BinaryScan``."""
         return BinaryScan(self._model.cholesky_func, self, self._model.covariates, block=block, cutoff=cutoff)
 
-    def sets(self, block=None, cutoff=2.0):
-        """Burden, SKAT and SKAT-O of marker sets at this null, with saddlepoint-adjusted variances: a ``BinarySetTest``."""
-        return BinarySetTest(self._model.cholesky_func, self, self._model.covariates, block=block, cutoff=cutoff)
+    def sets(self, block=None, cutoff=2.0, max_markers=None):
+        """Burden, SKAT and SKAT-O of marker sets at this null, with saddlepoint-adjusted variances: a ``BinarySetTest``.  With
+        ``max_markers`` (an integer in ``block`` .. 4096) a ``BinaryWideSetTest``, whose sets hold up to that many markers."""
+        if max_markers is None:
+            return BinarySetTest(self._model.cholesky_func, self, self._model.covariates, block=block, cutoff=cutoff)
+        return BinaryWideSetTest(self._model.cholesky_func, self, self._model.covariates, block=block, cutoff=cutoff,
+                                 max_markers=max_markers)
 
 
 class LogisticMixedModel(object):
@@ -396,6 +401,16 @@ class BinarySetTest(setmod.VariantSetTest):
         rho = setmod.check_rho(rho) if skato else None
         self._check_factor()
         ns, device = len(sets), finish == "device"
+        out = self._out(ns, skato, rho)
+        given, mode = self._weight_mode(weights)
+        block = self._block_binary(src, mode, method, rho if skato else np.empty(0), device) if sets else None
+        kernel = [None] * ns
+        for members in setmod.pack_sets([s.size for s in sets], self.block):
+            self._narrow(out, kernel, members, sets, weights, given, block, device, method, rho, skato)
+        return self._done(out, kernel, return_kernel)
+
+    def _out(self, ns, skato, rho):
+        """The result of a call before any set has run: NaN, the counts 0; ``last_bspa`` likewise."""
         out = {k: np.full(ns, np.nan) for k in setmod.KEYS + binary_sets.BINARY_KEYS}
         for k in ("n_used", "burden_spa_flag", "n_adjusted"):
             out[k] = np.zeros(ns, dtype=np.int64)
@@ -403,37 +418,51 @@ class BinarySetTest(setmod.VariantSetTest):
             out.update({k: np.full(ns, np.nan) for k in setmod.SKATO_KEYS[:3]})
             out["skato_p_rho"] = np.full((ns, rho.size), np.nan)
         self.last_bspa = np.full((ns, binary_sets.BSPA_ROWLEN), np.nan)
+        return out
+
+    @staticmethod
+    def _weight_mode(weights):
         given = not (weights is None or isinstance(weights, str))
-        mode = setmod.WEIGHT_GIVEN if given else setmod.WEIGHT_ONES if weights is None else setmod.WEIGHT_BETA
-        block = self._block_binary(src, mode, method, rho if skato else np.empty(0), device) if sets else None
-        kernel = [None] * ns
-        for members in setmod.pack_sets([s.size for s in sets], self.block):
-            start = np.concatenate([[0], np.cumsum([sets[i].size for i in members])]).astype(np.int32)
-            w = np.ascontiguousarray(np.concatenate([weights[i] for i in members])) if given else None
-            B, V, fin = block(np.concatenate([sets[i] for i in members]), start, w)
-            self.last_bspa[members] = B
-            if device:
-                out["n_used"][members] = fin[:, 0].astype(np.int64)
-                for col, k in ((1, "burden_beta"), (2, "burden_se"), (3, "burden_chi2"), (4, "skat_q"), (5, "skat_p")):
-                    out[k][members] = fin[:, col]
-                if skato:
-                    for col, k in ((6, "skato_p"), (7, "skato_pmin"), (8, "skato_rho")):
-                        out[k][members] = fin[:, col]
-                    out["skato_p_rho"][members] = fin[:, setmod.FINISH_HEAD:]
-                continue
-            S, G = fin
-            for i, a, b in zip(members, start[:-1], start[1:]):
-                wi = weights if not given else weights[i]
-                s, K, wk, keep = setmod.set_kernel(S[:, a:b], G[a:b, a:b], self.R, self.u, wi)
-                vs = V[a:b][keep]
-                out["n_used"][i] = int(keep.sum())
-                if keep.any():
-                    t = binary_sets.scaled_tests(s, K, wk, vs, method, rho)
-                    for k in ("burden_beta", "burden_se", "burden_chi2", "skat_q", "skat_p"):
-                        out[k][i] = t[k]
-                    if t["skato"] is not None:
-                        out["skato_p"][i], out["skato_pmin"][i], out["skato_rho"][i], out["skato_p_rho"][i] = t["skato"]
-                kernel[i] = (s, vs[:, None] * K * vs[None, :], wk, vs)
+        return given, setmod.WEIGHT_GIVEN if given else setmod.WEIGHT_ONES if weights is None else setmod.WEIGHT_BETA
+
+    @staticmethod
+    def _device_rows(out, members, fin, skato):
+        """The rows of a device finish into the result."""
+        out["n_used"][members] = fin[:, 0].astype(np.int64)
+        for col, k in ((1, "burden_beta"), (2, "burden_se"), (3, "burden_chi2"), (4, "skat_q"), (5, "skat_p")):
+            out[k][members] = fin[:, col]
+        if skato:
+            for col, k in ((6, "skato_p"), (7, "skato_pmin"), (8, "skato_rho")):
+                out[k][members] = fin[:, col]
+            out["skato_p_rho"][members] = fin[:, setmod.FINISH_HEAD:]
+
+    def _host_set(self, out, kernel, i, S, G, wi, V, method, rho):
+        """Step 5 of set ``i`` on the host: its columns of the statistics, its X'X and its columns' scales."""
+        s, K, wk, keep = setmod.set_kernel(S, G, self.R, self.u, wi)
+        vs = V[keep]
+        out["n_used"][i] = int(keep.sum())
+        if keep.any():
+            t = binary_sets.scaled_tests(s, K, wk, vs, method, rho)
+            for k in ("burden_beta", "burden_se", "burden_chi2", "skat_q", "skat_p"):
+                out[k][i] = t[k]
+            if t["skato"] is not None:
+                out["skato_p"][i], out["skato_pmin"][i], out["skato_rho"][i], out["skato_p_rho"][i] = t["skato"]
+        kernel[i] = (s, vs[:, None] * K * vs[None, :], wk, vs)
+
+    def _narrow(self, out, kernel, members, sets, weights, given, block, device, method, rho, skato):
+        """One block of sets of at most ``block`` markers through ``_block_binary``'s ``block`` and into the result."""
+        start = np.concatenate([[0], np.cumsum([sets[i].size for i in members])]).astype(np.int32)
+        w = np.ascontiguousarray(np.concatenate([weights[i] for i in members])) if given else None
+        B, V, fin = block(np.concatenate([sets[i] for i in members]), start, w)
+        self.last_bspa[members] = B
+        if device:
+            return self._device_rows(out, members, fin, skato)
+        S, G = fin
+        for i, a, b in zip(members, start[:-1], start[1:]):
+            self._host_set(out, kernel, i, S[:, a:b], G[a:b, a:b], weights if not given else weights[i], V[a:b], method, rho)
+
+    def _done(self, out, kernel, return_kernel):
+        """What follows from the sets' 13 numbers, for every set of the call at once."""
         P = self.last_bspa
         used = out["n_used"] > 0
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -444,3 +473,119 @@ class BinarySetTest(setmod.VariantSetTest):
         if return_kernel:
             out["kernel"] = kernel
         return out
+
+
+class BinaryWideSetTest(BinarySetTest):
+    """``BinarySetTest`` for sets of up to ``max_markers`` <= 4096 markers (``NullModel.sets(max_markers=...)``; DESIGN.md section
+    23).  ``__call__``, ``test_bed`` and ``test_dosages`` take the arguments of ``BinarySetTest``'s; a per-call ``max_markers``
+    overrides the constructor's, and ``finish`` is ``"host"``, ``"device"`` or ``"wide"`` with the meaning it has on
+    ``VariantSetTest`` (``"device"`` with a set wider than ``block`` is the same ``ValueError``).  The sets of at most ``block``
+    markers are packed as if the wider ones were not in the list (``sets.plan_sets``) and run as ``BinarySetTest`` runs them: the
+    blocks and the bits of a call on them alone.  A wider set runs on its own, in its position, as ``ceil(k / block)`` sub-blocks
+    with one wait each: the rows are loaded, then the Gram entry point into the set's slices, the markers' saddlepoint call into
+    its slice, the collapse (``scilmm_sets_collapse*_dev``: the burden's collapsed genotype grows by the sub-block's kept
+    markers), the panel against the kept sub-blocks and the keep.  ``scilmm_sets_spa_wide_dev`` is queued behind the last one;
+    with ``finish="wide"`` ``scilmm_sets_finish_wide_scaled_dev`` follows and the set's 13 numbers and one row come back, with
+    ``finish="host"`` the pieces, the 13 numbers and the scales come back and the host runs ``sets.assemble_wide``,
+    ``sets.set_kernel`` and ``binary_sets.scaled_tests``.  The result has the keys of ``BinarySetTest``, ``last_bspa`` included;
+    ``return_kernel=True`` (host finish) hands out ``(s, K~, w, vscale)`` per set."""
+
+    def __init__(self, cholesky_func, null, covariates, block=None, cutoff=2.0, max_markers=None):
+        super(BinaryWideSetTest, self).__init__(cholesky_func, null, covariates, block=block, cutoff=cutoff)
+        self.max_markers = setmod.check_max_markers(max_markers, self.block)
+
+    def _block_binary_wide(self, src, bmax, staged, mode, method, rho, device):
+        """(rows, weights) -> (the set's 13 saddlepoint numbers, its markers' variance scales, the finish) of one set of more than
+        ``block`` rows and up to ``bmax`` sub-blocks: the sub-blocks as in ``VariantSetTest._block_wide_device``, each followed by
+        its saddlepoint call and its collapse; then the set saddlepoint and -- ``device`` -- the scaled wide finish.  The finish is
+        the row of the device, or the assembled statistics and X'X for the host's."""
+        torch, q, blk, c, n = self.torch, self.q, self.block, self.c, self.n
+        bp = (blk + 15) // 16 * 16
+        ld = (bmax - 1) * bp
+        if not staged:
+            src.stage(blk)
+        new = lambda k: torch.empty((k,), dtype=torch.float64, device="cuda")
+        dS, dK, dX, dP = new(bmax * (q + 4) * blk), new(bmax * blk * blk), new(bmax * blk * ld), new(bmax * SPA_ROWS * blk)
+        store, dg, dW, dB, dV = new(n * ld), new(n), new(bmax * blk), new(binary_sets.BSPA_ROWLEN), new(bmax * blk)
+        lo = setmod.FINISH_HEAD + rho.size
+        dO = new(lo)
+        meth = setmod.METHODS.index(method)
+        pR, pu = vp(self.dR.data_ptr()), vp(self.du.data_ptr())
+        null = (pR, pu, vp(self.dmu.data_ptr()), vp(self.dC.data_ptr()), c, vp(self.dMinv.data_ptr()), self.cutoff)
+        at = lambda d, off: vp(d.data_ptr() + 8 * off)
+
+        def run(rows, w):
+            k = rows.size
+            B = -(-k // blk)
+            if w is not None:
+                dW[:k].copy_(torch.from_numpy(w))
+            for b in range(B):
+                sub = rows[b * blk:(b + 1) * blk]
+                rb, t = sub.size, b * bp
+                pS = at(dS, b * (q + 4) * blk)
+                src.load(sub)
+                src.enqueue(0, rb, pS, at(dK, b * blk * blk))
+                src.spa(0, rb, (pS,) + null + (at(dP, b * SPA_ROWS * blk),))
+                src.collapse(0, rb, (pS, mode, at(dW, b * blk) if w is not None else None, b == 0, vp(dg.data_ptr())))
+                if b > 0:
+                    self.factor.scan_panel_dev(rb, vp(store.data_ptr()), ld, t, at(dX, b * blk * ld), ld)
+                if b < B - 1:
+                    self.factor.scan_block_keep_dev(rb, vp(store.data_ptr()), ld, t)
+                self.sym.sync()
+            pW = vp(dW.data_ptr()) if w is not None else None
+            wide = (k, blk, q, vp(dS.data_ptr()), vp(dK.data_ptr()), vp(dX.data_ptr()), ld)
+            self.factor.sets_spa_wide_dev(*(wide + null + (vp(dP.data_ptr()), mode, pW, vp(dg.data_ptr()), vp(dB.data_ptr()),
+                                                          vp(dV.data_ptr()))))
+            if device:
+                self.factor.sets_finish_wide_scaled_dev(*(wide + (pR, pu, c, mode, pW, meth, rho, vp(dO.data_ptr()), None,
+                                                                  vp(dV.data_ptr()))))
+            self.sym.sync()
+            row = dB.cpu().numpy().reshape(1, binary_sets.BSPA_ROWLEN)
+            if device:
+                return row, None, dO.cpu().numpy().reshape(1, lo)
+            hS, hK, hX = dS.cpu().numpy(), dK.cpu().numpy(), dX.cpu().numpy()
+            rbs = [min(blk, k - b * blk) for b in range(B)]
+            Ss = [hS[b * (q + 4) * blk:][:(q + 4) * rb].reshape(q + 4, rb) for b, rb in enumerate(rbs)]
+            Gs = [hK[b * blk * blk:][:rb * rb].reshape(rb, rb) for b, rb in enumerate(rbs)]
+            Xs = [hX[b * blk * ld:][:rb * ld].reshape(rb, ld)[:, :b * bp] for b, rb in enumerate(rbs) if b > 0]
+            return row, dV[:k].cpu().numpy(), setmod.assemble_wide(Ss, Gs, Xs, bp)
+        return run
+
+    def _run(self, src, sets, weights, method, return_kernel, skato=False, rho=None, finish="host", max_markers=None):
+        """The checks of ``VariantSetTest._run`` (before any launch); then the work of ``sets.plan_sets`` in its order: a block of
+        narrow sets through ``BinarySetTest``'s calls, a wide set through ``_block_binary_wide``."""
+        max_markers = self.max_markers if max_markers is None else max_markers
+        sets = setmod.check_sets(sets, src.m, self.block, max_markers)
+        weights = setmod.check_weights(weights, sets)
+        setmod.check_method(method)
+        if finish not in setmod.FINISH_VALUES:
+            raise ValueError("finish must be one of %s, got %r" % (", ".join(setmod.FINISH_VALUES), finish))
+        if finish != "host" and return_kernel:
+            raise ValueError('return_kernel=True needs finish="host": the device finish does not bring K back')
+        sizes = [s.size for s in sets]
+        widest = max(sizes + [0])
+        if finish == "device" and widest > self.block:
+            raise ValueError('a set of %d markers needs finish="host" or finish="wide": the device finish holds one block of at most '
+                             '%d markers in LDS' % (widest, self.block))
+        rho = setmod.check_rho(rho) if skato else None
+        self._check_factor()
+        ns, device = len(sets), finish != "host"
+        out = self._out(ns, skato, rho)
+        given, mode = self._weight_mode(weights)
+        grid = rho if skato else np.empty(0)
+        narrow = any(k <= self.block for k in sizes)
+        block = self._block_binary(src, mode, method, grid, device) if narrow else None
+        wide = self._block_binary_wide(src, -(-widest // self.block), narrow, mode, method, grid, device) if widest > self.block else None
+        kernel = [None] * ns
+        for members in setmod.plan_sets(sizes, self.block):
+            i = members[0]
+            if sizes[i] <= self.block:
+                self._narrow(out, kernel, members, sets, weights, given, block, device, method, rho, skato)
+                continue
+            B, V, fin = wide(sets[i], np.ascontiguousarray(weights[i]) if given else None)
+            self.last_bspa[members] = B
+            if device:
+                self._device_rows(out, members, fin, skato)
+            else:
+                self._host_set(out, kernel, i, fin[0], fin[1], weights if not given else weights[i], V, method, rho)
+        return self._done(out, kernel, return_kernel)

@@ -10,6 +10,8 @@ input form.  A source has ``m`` (its markers), ``row_bytes`` (host bytes of one 
                                twin; ``tail``: what follows ``r`` in its arguments -- ``scilmm_amd.glmm``)
     sets_spa(k0, rb, tail)     queue the sets' variance scales and burden saddlepoint rows of block (k0, rb) behind its Gram block
                                and its ``spa`` (the ``scilmm_sets_spa*_dev`` twin -- ``scilmm_amd.binary_sets``)
+    collapse(k0, rb, tail)     queue the collapsed genotype of a wide set behind the Gram block of sub-block (k0, rb) (the
+                               ``scilmm_sets_collapse*_dev`` twin; ``tail``: statistics, weight mode, weights, first, the row)
 
 Everything else -- chunks, blocks, the synchronisation, the host algebra -- is the callers' and does not depend on the form.
 """
@@ -85,6 +87,9 @@ class Int8Rows(MarkerSource):
     def sets_spa(self, k0, rb, tail):
         self.model.factor.sets_spa_dev(*(self._head(k0) + (rb,) + tuple(tail)))
 
+    def collapse(self, k0, rb, tail):
+        self.model.factor.sets_collapse_dev(*(self._head(k0) + (rb,) + tuple(tail)))
+
 
 class BedRows(MarkerSource):
     """The packed rows of a ``BedFile``, decoded on the device: mapped file -> pinned buffer (the one host pass over the bytes)
@@ -129,6 +134,9 @@ class BedRows(MarkerSource):
     def sets_spa(self, k0, rb, tail):
         self.model.factor.sets_spa_bed_dev(*(self._head(k0) + (rb,) + tuple(tail)))
 
+    def collapse(self, k0, rb, tail):
+        self.model.factor.sets_collapse_bed_dev(*(self._head(k0) + (rb,) + tuple(tail)))
+
 
 class DosageRows(MarkerSource):
     """m x N dosages (``check_dosages``; ``dtype``: the element type of the C entry point): host array -> pinned buffer (the one
@@ -164,3 +172,6 @@ class DosageRows(MarkerSource):
 
     def sets_spa(self, k0, rb, tail):
         self.model.factor.sets_spa_dosage_dev(*(self._head(k0) + (rb,) + tuple(tail)))
+
+    def collapse(self, k0, rb, tail):
+        self.model.factor.sets_collapse_dosage_dev(*(self._head(k0) + (rb,) + tuple(tail)))

@@ -33,7 +33,15 @@ sub-blocks are queued once as VariantSetTest(..., max_markers=k, finish="wide") 
 then, per round, the finish with SKAT-O and without, its four phases by HIP events (prep + form | reduction | eigenvalues |
 tails); the host finish of the same set in the same run (--host-reps timings each; 0 leaves it out), the deviation of the device's
 row from the host's, and the wall time of the whole call with finish="wide" and finish="host".  One warm-up round, then --blocks
-rounds."""
+rounds.
+  usage: sets_timing.py 100k --binary-wide 256,1024 [--blocks 5] [--out profiles/sets_binary_wide_100k.json]
+--binary-wide times one set of k rare markers per width as the binary-trait tests queue it (scilmm_amd.glmm.BinaryWideSetTest,
+finish="wide", SKAT-O, cutoff 2), at a null point of a simulated 5 % phenotype: per sub-block the Gram block,
+k_scan_spa of its markers, k_sets_collapse and the panel by their HIP events (the keeps as for --wide), then
+scilmm_sets_spa_wide_dev by phase and the scaled wide finish by phase; the same markers as ceil(k / 128) separate 128-marker binary
+sets (Gram block, k_scan_spa, k_sets_spa, the scaled k_sets_finish), in alternating rounds of the same run; the ratio of the two
+device times, the share of the panels and keeps, and every collapse against the k_scan_spa of its own sub-block.  One warm-up
+round, then --blocks rounds."""
 import argparse, ctypes, json, os, sys
 import numpy as np
 import scipy.sparse as sp
@@ -46,6 +54,7 @@ ap.add_argument("--finish", action="store_true")
 ap.add_argument("--binary", action="store_true")
 ap.add_argument("--wide", default=None)
 ap.add_argument("--wide-finish", dest="wide_finish", default=None)
+ap.add_argument("--binary-wide", dest="binary_wide", default=None)
 ap.add_argument("--host-reps", dest="host_reps", type=int, default=3)
 args = ap.parse_args()
 import torch
@@ -338,7 +347,134 @@ def wide_finish_leg(widths):
     return rec
 
 
-if args.finish or args.binary or args.wide or args.wide_finish:
+def binary_wide_leg(widths):
+    import time
+    from scilmm_amd import LogisticMixedModel
+    from scilmm_amd.binary_sets import BSPA_ROWLEN
+    from scilmm_amd.glmm import SPA_ROWS, logistic_irls
+    from scilmm_amd.sets import FINISH_HEAD, RHO_DEFAULT
+    bp, cutoff = R, 2.0
+    rho, ld_out = np.asarray(RHO_DEFAULT), FINISH_HEAD + len(RHO_DEFAULT)
+    yb = (rng.random(n) < 0.05).astype(np.float64)
+    model = LogisticMixedModel(SparseCholesky(), [A], Cv, yb)
+    null = model.null_at([0.5], logistic_irls(model.covariates, yb), 0.3 * rng.standard_normal(n))
+    bt = null.sets(block=R, cutoff=cutoff, max_markers=max(widths))
+    bf, bs, c, bq = bt.factor, bt.sym, bt.c, bt.q
+    nullp = (vp(bt.dR.data_ptr()), vp(bt.du.data_ptr()), vp(bt.dmu.data_ptr()), vp(bt.dC.data_ptr()), c, vp(bt.dMinv.data_ptr()), cutoff)
+    pQ = vp(bt.dQ.data_ptr())
+    new = lambda m: torch.zeros((m,), dtype=torch.float64, device="cuda")
+    rec = {"workload": args.workload, "n": int(n), "block": R, "cutoff": cutoff, "prevalence": 0.05, "n_rho": int(rho.size), "widths": {},
+           "timer": "HIP events of every call, one sub-block per synchronise; keeps: wall time of 20 queued keeps / 20; one warm-up "
+                    "round, then %d alternating rounds of the wide set and of its sub-blocks as separate narrow binary sets" % args.blocks}
+    for k in widths:
+        B = -(-k // R)
+        ldw = (B - 1) * bp
+        Gm = rng.binomial(2, rng.uniform(0.005, 0.05, k)[:, None], size=(k, n)).astype(np.int8)
+        Gm[rng.random(Gm.shape) < 0.02] = -1
+        store, dSa, dKa, dXa, dPa = new(n * ldw), new(B * (bq + 4) * R), new(B * R * R), new(B * R * ldw), new(B * SPA_ROWS * R)
+        dg, dBw, dVw, dOw = new(n), new(BSPA_ROWLEN), new(B * R), new(ld_out)
+        dBn, dVn, dOn, dPn = new(BSPA_ROWLEN), new(R), new(ld_out), new(SPA_ROWS * R)
+        at = lambda d, off: vp(d.data_ptr() + 8 * off)
+        wide = (k, R, bq, vp(dSa.data_ptr()), vp(dKa.data_ptr()), vp(dXa.data_ptr()), ldw)
+
+        def load(b):
+            sub = np.ascontiguousarray(Gm[b * R:(b + 1) * R])
+            dG[:sub.shape[0], :n].copy_(torch.from_numpy(sub))
+            torch.cuda.synchronize()
+            return sub.shape[0]
+
+        t_wide, t_base, per_block = [], [], []
+        for it in range(1 + args.blocks):
+            w = dict(gram=0.0, spa=0.0, collapse=0.0, panel=0.0)
+            blocks = []
+            for b in range(B):                                   # the wide set, as BinaryWideSetTest queues it
+                rb = load(b)
+                pS = at(dSa, b * (bq + 4) * R)
+                bf.scan_block_gram_dev(vp(dG.data_ptr()), ld, rb, pQ, bq, pS, at(dKa, b * R * R))
+                bf.scan_spa_dev(vp(dG.data_ptr()), ld, rb, pS, *(nullp + (at(dPa, b * SPA_ROWS * R),)))
+                bf.sets_collapse_dev(vp(dG.data_ptr()), ld, rb, pS, 0, None, b == 0, vp(dg.data_ptr()))
+                if b > 0: bf.scan_panel_dev(rb, vp(store.data_ptr()), ldw, b * bp, at(dXa, b * R * ldw), ldw)
+                if b < B - 1: bf.scan_block_keep_dev(rb, vp(store.data_ptr()), ldw, b * bp)
+                bs.sync()
+                spa_ms, coll_ms = bs.spa_timing(), bs.sets_spa_wide_timing()[0]
+                w["gram"] += float(sum(bs.scan_timing())); w["spa"] += spa_ms; w["collapse"] += coll_ms
+                if b > 0: w["panel"] += float(sum(bs.panel_timing()))
+                blocks.append((coll_ms, spa_ms))
+            bf.sets_spa_wide_dev(*(wide + nullp + (vp(dPa.data_ptr()), 0, None, vp(dg.data_ptr()), vp(dBw.data_ptr()), vp(dVw.data_ptr()))))
+            bf.sets_finish_wide_scaled_dev(*(wide + (nullp[0], nullp[1], c, 0, None, 0, rho, vp(dOw.data_ptr()), None, vp(dVw.data_ptr()))))
+            bs.sync()
+            sw, fw = bs.sets_spa_wide_timing(), bs.sets_finish_wide_timing()
+            base = dict(gram=0.0, spa=0.0, sets_spa=0.0, finish=0.0)
+            for b in range(B):                                   # the same markers as separate narrow sets: BinarySetTest's calls
+                rb = load(b)
+                start = np.array([0, rb], dtype=np.int32)
+                pS, pK, pP = vp(dS.data_ptr()), vp(dK.data_ptr()), vp(dPn.data_ptr())
+                bf.scan_block_gram_dev(vp(dG.data_ptr()), ld, rb, pQ, bq, pS, pK)
+                bf.scan_spa_dev(vp(dG.data_ptr()), ld, rb, pS, *(nullp + (pP,)))
+                bf.sets_spa_dev(vp(dG.data_ptr()), ld, rb, pS, pK, *(nullp + (pP, 1, start, 0, None, vp(dBn.data_ptr()), vp(dVn.data_ptr()))))
+                bf.sets_finish_scaled_dev(rb, bq, pS, pK, nullp[0], nullp[1], c, 1, start, 0, None, 0, rho, vp(dOn.data_ptr()), ld_out, None,
+                                          vp(dVn.data_ptr()))
+                bs.sync()
+                base["gram"] += float(sum(bs.scan_timing())); base["spa"] += bs.spa_timing()
+                base["sets_spa"] += bs.sets_spa_timing(); base["finish"] += bs.sets_finish_timing()
+            if it >= 1:
+                t_wide.append([w["gram"], w["spa"], w["collapse"], w["panel"], sw[1], sw[2], float(sum(fw))] + list(fw))
+                t_base.append([base["gram"], base["spa"], base["sets_spa"], base["finish"]])
+                per_block.append(blocks)
+        keeps = []
+        for it in range(4):                                      # the last block is still in X: 20 keeps of it behind each other
+            bs.sync(); t0 = time.perf_counter()
+            for _ in range(20): bf.scan_block_keep_dev(rb, vp(store.data_ptr()), ldw, 0)
+            bs.sync(); keeps.append(1e3 * (time.perf_counter() - t0) / 20)
+        keep_ms = float(np.median(keeps[1:])) * (B - 1)
+        # the set saddlepoint once more at cutoff 0: the burden is attempted whatever its score (the row is put back every round,
+        # the call overwrites it with g^_B)
+        Bw2 = dBw.cpu().numpy().copy()
+        g0, forced = dg.clone(), []
+        for it in range(1 + args.blocks):
+            dg.copy_(g0)
+            bf.sets_spa_wide_dev(*(wide + nullp[:6] + (0.0, vp(dPa.data_ptr()), 0, None, vp(dg.data_ptr()), vp(dBw.data_ptr()), vp(dVw.data_ptr()))))
+            bs.sync()
+            if it >= 1: forced.append(bs.sets_spa_wide_timing()[1:])
+        forced, Bf = np.asarray(forced), dBw.cpu().numpy().copy()
+        dBw.copy_(torch.from_numpy(Bw2))
+        a, bb, pb = np.asarray(t_wide), np.asarray(t_base), np.asarray(per_block)
+        wide_ms = float(np.median(a[:, :7].sum(axis=1))) + keep_ms
+        base_ms = float(np.median(bb.sum(axis=1)))
+        Bw, hP = dBw.cpu().numpy(), dPa.cpu().numpy()
+        t0 = time.perf_counter()
+        out = bt(Gm, [np.arange(k)], skato=True, finish="wide")
+        call_ms = 1e3 * (time.perf_counter() - t0)
+        names = ("sweeps_with_gram", "marker_spa", "collapses", "panels", "sets_spa_wide_markers_pairs", "sets_spa_wide_burden", "scaled_finish")
+        rec["widths"][str(k)] = {
+            "sub_blocks": B, "store_bytes": int(n) * ldw * 8,
+            "wide_device_ms": dict({nm: summary(a[:, i]) for i, nm in enumerate(names)}, keeps=keep_ms, total=wide_ms,
+                                   scaled_finish_phases={nm: summary(a[:, 7 + i]) for i, nm in enumerate(("prep_form", "reduction", "eigenvalues", "tails"))}),
+            "separate_sets_device_ms": dict({nm: summary(bb[:, i]) for i, nm in enumerate(("sweeps_with_gram", "marker_spa", "sets_spa", "scaled_finish"))},
+                                            total=base_ms),
+            "wide_over_separate": wide_ms / base_ms,
+            "panels_and_keeps_share_of_wide": (float(np.median(a[:, 3])) + keep_ms) / wide_ms,
+            "collapse_over_scan_spa_per_sub_block": [float(np.median(pb[:, b, 0]) / np.median(pb[:, b, 1])) for b in range(B)],
+            "collapse_ms_per_sub_block": [float(np.median(pb[:, b, 0])) for b in range(B)],
+            # (sub-block 1: r bytes of genotypes per individual, the row read and written)
+            "collapse_implied_bytes_per_s": float(n) * (min(R, k - R) + 16) / (1e-3 * float(np.median(pb[:, 1, 0]))),
+            "markers_saddlepointed": int(sum(np.sum(hP[b * SPA_ROWS * R:][:SPA_ROWS * min(R, k - b * R)].reshape(SPA_ROWS, -1)[6] > 0) for b in range(B))),
+            "sets_spa_wide_at_cutoff_0_ms": {"markers_pairs": summary(forced[:, 0]), "burden": summary(forced[:, 1]), "burden_flag": int(Bf[6]),
+                                             "iters": float(Bf[5]), "phi": float(Bf[11])},
+            "burden_flag": int(Bw[6]), "n_adjusted": int(Bw[12]), "phi": float(Bw[11]), "n_used": int(out["n_used"][0]),
+            "skato_p": float(out["skato_p"][0]), "whole_call_wall_ms_skato": call_ms}
+        del store, dSa, dKa, dXa, dPa
+    return rec
+
+
+if args.finish or args.binary or args.wide or args.wide_finish or args.binary_wide:
+    if args.binary_wide:
+        rec = binary_wide_leg([int(v) for v in args.binary_wide.split(",")])
+        print(json.dumps(rec))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rec, open(args.out, "w"), indent=1)
+        sys.exit(0)
     if args.wide_finish:
         rec = wide_finish_leg([int(v) for v in args.wide_finish.split(",")])
         print(json.dumps(rec))
