@@ -477,6 +477,48 @@ int scilmm_sets_finish_dev(scilmm_factor* fac, int32_t r, int32_t q, const doubl
  * it: ms[0] k_sets_finish (tools/sets_timing.py --finish).  No counterpart in the reference. */
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Variant-set tests over a phenotype panel: scilmm_sets_finish_dev for the sets of a Gram block against t traits at once
+ * (DESIGN.md section 24), queued on the handle's stream behind the block and the scilmm_scan_panel_dev that formed the traits'
+ * scores.  Of the finish only the score depends on the trait: the projection K = G - z'z, A = diag(w) K diag(w), its Jacobi
+ * eigendecomposition, the secular equations of every A R_rho and of the remainder term, the floors and the Liu moments are
+ * computed ONCE per set (k_sets_spectra, one workgroup per set) and kept as a record in a scratch buffer of the handle; one
+ * workgroup per (set, group of traits) then loads the record and runs the tails, T = min p_rho and the SKAT-O integral per trait
+ * (k_sets_panel_tail) with the routines scilmm_sets_finish_dev runs.
+ *   r, q, d_stats, d_gram, d_R, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho: as for scilmm_sets_finish_dev.
+ *            There is no u: the traits arrive projected off the whitened covariates, so a trait's score is its column of d_xty
+ *            as it stands; the score row of d_stats is not used.
+ *   d_xty, ld_xty, t: the r x t scores X'Y~ as scilmm_scan_panel_dev wrote them (row = the block's column, column = the trait),
+ *            ld_xty >= t doubles between rows; 1 <= t <= 4 096.
+ *   d_tscale: null (every scale 1), or t positive finite scales on the device: trait k is tested with t = w o s / sqrt(scale_k),
+ *            which divides burden_chi2 and skat_q by scale_k (scale="profile" of scilmm_amd.panel).
+ *   d_head : n_sets rows of 4 doubles:  n_used | w'Kw | the set's flag word (bit 1 the Jacobi iteration ran out of sweeps, bit 2
+ *            a secular root ran out of steps) | 0.
+ *   d_out  : n_sets t rows of 8 doubles, row = set t + trait:  1'(w o s), unscaled | burden_chi2 | skat_q | skat_p | skato_p |
+ *            skato_pmin | skato_rho | flags (the set's, and the trait's as scilmm_sets_finish_dev sets them).  burden_beta =
+ *            1'(w o s) / w'Kw and burden_se = (scale / w'Kw)^1/2 are the caller's, as is burden_p.  A set with nothing left:
+ *            n_used = 0, w'Kw NaN, flags 0, every row of it NaN with flags 0.  Without SKAT-O (n_rho = 0) the three skato numbers
+ *            are NaN.  Exactly 4 n_sets and 8 n_sets t doubles are written.
+ * The traits of a tail workgroup (1 .. 32) are chosen by the engine so that sets x groups covers the device several times over;
+ * the environment variable SCILMM_SETS_PANEL_GROUP=<1 .. 32>, read per call, takes its place.  No atomics, fixed strides and
+ * fixed reduction trees: the numbers of a (set, trait) pair depend on that set's inputs and that trait's column alone -- not on
+ * t, the group size, the set's place in the block or the mode of the handle -- and scilmm_timing.n_float_atomic_launches is not
+ * touched.  They agree with scilmm_sets_finish_dev on the same score to rounding in the sums (1e-9) and to the accuracy of the
+ * tails (1e-6), not bit for bit.  The records (n_sets (96 + (n_rho + 3) cap) doubles, cap the block's largest set) are the
+ * handle's: grown behind a stream synchronise, never allocated again for the same or a smaller call.  Enqueued without
+ * synchronising; nothing of the factor is read.  SCILMM_ERR_ARG before anything of the handle or of the device is read: what
+ * scilmm_sets_finish_dev rejects of the arguments they share, a null d_xty, d_head or d_out, t outside 1 .. 4 096, ld_xty < t,
+ * and a scale that is not finite and positive where d_tscale is memory the host can read (pinned or managed; scales in device
+ * memory are the caller's to check).  Refusals as for scilmm_sets_finish_dev.  scilmm_amd.VariantSetTest.set_traits is the
+ * interface.  No counterpart in the reference. */
+int scilmm_sets_finish_panel_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram, const double* d_R,
+                                 int32_t c, int32_t n_sets, const int32_t* set_start, int32_t weight_mode, const double* d_weights,
+                                 int32_t method, const double* rho, int32_t n_rho, const double* d_xty, int64_t ld_xty, int32_t t,
+                                 const double* d_tscale /* t scales or NULL = 1 */, double* d_head, double* d_out);
+
+/* HIP-event times of the last scilmm_sets_finish_panel_dev on the handle, in milliseconds, valid after the scilmm_sync that
+ * follows it: ms[0] k_sets_spectra, ms[1] k_sets_panel_tail (tools/sets_panel_timing.py).  No counterpart in the reference. */
+int scilmm_sets_finish_panel_timing(const scilmm_symbolic* sym, double* ms);
+
 /* The finish of ONE variant set of k markers, 1 <= k <= 4 096, that ran as B = ceil(k / block) sub-blocks (DESIGN.md section
  * 22), queued on the handle's stream behind the last of them; everything scilmm_sets_finish_dev computes for a set, for a set
  * wider than one block.  With bp = block rounded up to 16: (B - 1) bp <= 4 096.

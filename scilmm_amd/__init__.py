@@ -18,4 +18,5 @@ from .panel import TraitPanel, panel_stats, panel_thresholds  # noqa: F401
 from .glmm import LogisticMixedModel, BinaryScan, BinarySetTest, BinaryWideSetTest  # noqa: F401
 from . import dosage  # noqa: F401
 from .sets import VariantSetTest  # noqa: F401
+from .set_panel import SetTraitPanel  # noqa: F401
 from ._lib import ScilmmError, NotPositiveDefiniteError  # noqa: F401

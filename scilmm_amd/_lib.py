@@ -83,6 +83,7 @@ SYMBOLS = [
     "scilmm_scan_spa_dev", "scilmm_scan_spa_bed_dev", "scilmm_scan_spa_dosage_dev", "scilmm_spa_timing",
     "scilmm_sets_finish_dev", "scilmm_sets_finish_timing", "scilmm_sets_finish_scaled_dev",
     "scilmm_sets_finish_wide_dev", "scilmm_sets_finish_wide_timing",
+    "scilmm_sets_finish_panel_dev", "scilmm_sets_finish_panel_timing",
     "scilmm_sets_spa_dev", "scilmm_sets_spa_bed_dev", "scilmm_sets_spa_dosage_dev", "scilmm_sets_spa_timing",
     "scilmm_sets_collapse_dev", "scilmm_sets_collapse_bed_dev", "scilmm_sets_collapse_dosage_dev",
     "scilmm_sets_spa_wide_dev", "scilmm_sets_finish_wide_scaled_dev", "scilmm_sets_spa_wide_timing",
@@ -201,6 +202,9 @@ def lib():
     L.scilmm_sets_finish_timing.argtypes = [vp, P(dbl)]
     L.scilmm_sets_finish_wide_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp]
     L.scilmm_sets_finish_wide_timing.argtypes = [vp, P(dbl)]
+    # fac, r, q, d_stats, d_gram, d_R, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_xty, ld_xty, t, d_tscale, d_head, d_out
+    L.scilmm_sets_finish_panel_dev.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i64, i32, vp, vp, vp]
+    L.scilmm_sets_finish_panel_timing.argtypes = [vp, P(dbl)]
     L.scilmm_sets_finish_scaled_dev.argtypes = L.scilmm_sets_finish_dev.argtypes + [vp]     # ... d_vscale
     # d_stats, d_gram, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa, n_sets, set_start, weight_mode, d_weights, d_bspa, d_vscale
     sspa = [vp, vp, vp, vp, vp, vp, i32, vp, dbl, vp, i32, vp, i32, vp, vp, vp]

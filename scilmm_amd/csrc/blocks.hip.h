@@ -359,6 +359,97 @@ int sets_finish(scilmm_factor* fac, const FinishArgs& a, const char* who) {
   return SCILMM_OK;
 }
 
+// What scilmm_sets_finish_panel_dev takes beside the factor: the block and the sets of FinishArgs without u, the scores and the
+// scales of the t traits, and the two outputs.
+struct PanelFinishArgs {
+  FinishArgs fin;               // d_u, d_out, ld_out, d_lam are not used
+  const double* d_xty;
+  int64_t ld_xty;
+  int32_t t;
+  const double* d_tscale;
+  double *d_head, *d_out;
+  // the scales where the host can read them (pinned or managed memory): finite and positive.  Device memory is the caller's to check.
+  static bool scales_ok(const double* d_tscale, int32_t t) {
+    if (!d_tscale) return true;
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, d_tscale) != hipSuccess) {
+      (void)hipGetLastError();
+      return true;
+    }
+    if (at.type != hipMemoryTypeHost && !at.isManaged) return true;
+    for (int32_t i = 0; i < t; ++i)
+      if (!(d_tscale[i] > 0.0 && std::isfinite(d_tscale[i]))) return false;
+    return true;
+  }
+  // before anything of the handle is read
+  static bool args_ok(const scilmm_factor* fac, const PanelFinishArgs& a) {
+    if (!a.d_xty || !a.d_head || !a.d_out || a.t < 1 || a.t > PT_TMAX || a.ld_xty < a.t) return false;
+    return FinishArgs::args_ok(fac, a.fin) && scales_ok(a.d_tscale, a.t);
+  }
+};
+
+// Traits per workgroup of k_sets_panel_tail: enough groups that sets x groups covers the device PT_COVER times over, a group no
+// larger than PT_GROUP_MAX; SCILMM_SETS_PANEL_GROUP=<1 .. 32>, read per call, takes its place (the numbers do not depend on it:
+// tools/sets_panel_timing.py times the sizes side by side, the tests run a ragged last group with it).
+constexpr int PT_COVER = 8;
+inline int32_t panel_tail_group(int32_t n_sets, int32_t t, int32_t n_cu) {
+  if (const char* e = getenv("SCILMM_SETS_PANEL_GROUP")) {
+    const int g = atoi(e);
+    if (g >= 1 && g <= PT_GROUP_MAX) return g;
+  }
+  const int64_t want = (int64_t)PT_COVER * std::max(n_cu, 1);
+  const int64_t g = ((int64_t)n_sets * t + want - 1) / want;
+  return (int32_t)std::min<int64_t>(std::max<int64_t>(g, 1), PT_GROUP_MAX);
+}
+
+// The finish of the sets of a Gram block against the t traits of a panel (scilmm_sets_finish_panel_dev; setpanel.hip.h, DESIGN.md
+// section 24): the refusals of sets_finish, the records (grown for more sets, wider sets or a longer grid only: the stream is
+// synchronised first, and nothing is allocated afterwards for the same or a smaller call), then k_sets_spectra, one workgroup per
+// set, and k_sets_panel_tail, one per (set, trait group), between the call's own events.  Nothing of the factor is read and
+// nothing of the work buffers is touched.
+int sets_finish_panel(scilmm_factor* fac, const PanelFinishArgs& p, const char* who) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const FinishArgs& a = p.fin;
+  FinSets sets{};
+  int32_t widest = 0;
+  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
+  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
+  for (int32_t j = 0; j < a.n_rho; ++j) sets.grid.rho[j] = a.rho[j];
+  const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
+  const int64_t ld_rec = rec_doubles(cap, a.n_rho);
+  const size_t need = (size_t)ld_rec * (size_t)a.n_sets;
+  if (D->pfin_rec_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  TRY(grow(sym, &D->pfin_rec, &D->pfin_rec_cap, need));
+  if (D->pfin_cu == 0) {
+    int cu = 0;
+    HIPCHK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, D->device));
+    D->pfin_cu = std::max(cu, 1);
+  }
+  const int32_t group = panel_tail_group(a.n_sets, p.t, D->pfin_cu);
+  const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
+  const size_t lds_tail = sizeof(double) * (size_t)ptail_lds_doubles(cap, a.n_rho, group);
+  // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
+  HIPCHK(hipFuncSetAttribute((const void*)k_sets_spectra, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
+  if (!D->pfin_ev[0])
+    for (auto& e : D->pfin_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->pfin_ev[0], s0));
+  hipLaunchKernelGGL(k_sets_spectra, dim3((unsigned)a.n_sets), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, sets,
+                     a.weight_mode, a.d_weights, a.n_rho, cap, D->pfin_rec, ld_rec, p.d_head);
+  HIPCHK(hipEventRecord(D->pfin_ev[1], s0));
+  hipLaunchKernelGGL(k_sets_panel_tail, dim3((unsigned)a.n_sets, (unsigned)((p.t + group - 1) / group)), dim3(PT_NT), lds_tail, s0, cap,
+                     a.n_rho, sets.grid, a.method, (const double*)D->pfin_rec, ld_rec, p.d_xty, p.ld_xty, p.t, p.d_tscale, group, p.d_out);
+  HIPCHK(hipEventRecord(D->pfin_ev[2], s0));
+  D->pfin_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
 // What scilmm_sets_finish_wide_dev takes beside the factor.
 struct WideArgs {
   int32_t k, block, q;

@@ -342,6 +342,13 @@ struct Dev {
   hipEvent_t fin_ev[2] = {nullptr, nullptr};  // k_sets_finish begin | done (the first finish call creates them)
   bool fin_pending = false;             // a finish call whose events have not been read yet (scilmm_sync)
   double fin_ms = 0.0;                  // the last call's k_sets_finish (scilmm_sets_finish_timing)
+  // the finish of a block's sets against a phenotype panel (scilmm_sets_finish_panel_dev): a record per set (setpanel.hip.h)
+  double* pfin_rec = nullptr;           // grown for more or wider sets behind a stream synchronise; nothing is allocated afterwards
+  size_t pfin_rec_cap = 0;              // doubles
+  int pfin_cu = 0;                      // compute units of the device (the first panel finish asks), for the tail's grid
+  hipEvent_t pfin_ev[3] = {nullptr, nullptr, nullptr};  // begin | k_sets_spectra done | k_sets_panel_tail done
+  bool pfin_pending = false;            // a panel finish whose events have not been read yet (scilmm_sync)
+  double pfin_ms[2] = {0.0, 0.0};       // the last call's k_sets_spectra | k_sets_panel_tail (scilmm_sets_finish_panel_timing)
   hipEvent_t sspa_ev[2] = {nullptr, nullptr};  // k_sets_spa begin | done (the first set SPA call creates them)
   bool sspa_pending = false;            // a set SPA call whose events have not been read yet (scilmm_sync)
   double sspa_ms = 0.0;                 // the last call's k_sets_spa (scilmm_sets_spa_timing)

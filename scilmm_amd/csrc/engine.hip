@@ -1,9 +1,9 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setmath.hip.h, setfinish.hip.h, setwide.hip.h, setspa.hip.h, setspawide.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setmath.hip.h, setfinish.hip.h, setpanel.hip.h, setwide.hip.h, setspa.hip.h, setspawide.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide, rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_panel, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide, rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
@@ -37,6 +37,7 @@
 #include "dosage.hip.h"
 #include "spa.hip.h"
 #include "setfinish.hip.h"
+#include "setpanel.hip.h"
 #include "setwide.hip.h"
 #include "setspa.hip.h"
 #include "setspawide.hip.h"
@@ -379,6 +380,19 @@ int scilmm_sets_finish_scaled_dev(scilmm_factor* fac, int32_t r, int32_t q, cons
   return sets_finish(fac, a, __func__);
 }
 
+// The variant-set finish of a Gram block against the traits of a panel, behind the block and its scilmm_scan_panel_dev
+int scilmm_sets_finish_panel_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram, const double* d_R,
+                                 int32_t c, int32_t n_sets, const int32_t* set_start, int32_t weight_mode, const double* d_weights,
+                                 int32_t method, const double* rho, int32_t n_rho, const double* d_xty, int64_t ld_xty, int32_t t,
+                                 const double* d_tscale, double* d_head, double* d_out) {
+  // (there is no u and one fixed row layout: what FinishArgs checks of them is given what passes)
+  const FinishArgs f{r, q, d_stats, d_gram, d_R, d_R, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_out,
+                     FIN_HEAD + FIN_RHO_MAX, nullptr};
+  const PanelFinishArgs a{f, d_xty, ld_xty, t, d_tscale, d_head, d_out};
+  if (!PanelFinishArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_finish_panel(fac, a, __func__);
+}
+
 // The finish of ONE set of up to 4 096 markers behind its sub-blocks: a pure function of what they left behind
 int scilmm_sets_finish_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
                                 const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, int32_t c,
@@ -694,6 +708,14 @@ int scilmm_sync(scilmm_symbolic* sym) {
     HIPCHK(hipEventElapsedTime(&a, D->fin_ev[0], D->fin_ev[1]));
     D->fin_ms = a;
   }
+  if (D->pfin_pending) {
+    D->pfin_pending = false;
+    for (int i = 0; i < 2; ++i) {
+      float a = 0;
+      HIPCHK(hipEventElapsedTime(&a, D->pfin_ev[i], D->pfin_ev[i + 1]));
+      D->pfin_ms[i] = a;
+    }
+  }
   if (D->wide_pending) {
     D->wide_pending = false;
     for (int i = 0; i < 4; ++i) {
@@ -772,6 +794,13 @@ int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms) {
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   ms[0] = ((const Dev*)sym->device)->fin_ms;
+  return SCILMM_OK;
+}
+
+int scilmm_sets_finish_panel_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const Dev* D = (const Dev*)sym->device;
+  for (int i = 0; i < 2; ++i) ms[i] = D->pfin_ms[i];
   return SCILMM_OK;
 }
 

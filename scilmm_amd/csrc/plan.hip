@@ -49,6 +49,9 @@ void dev_free(void* p) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->sspa_ev)
     if (e) (void)hipEventDestroy(e);
+  if (D->pfin_rec) (void)hipFree(D->pfin_rec);
+  for (auto& e : D->pfin_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->gxe_ev)

@@ -289,6 +289,12 @@ class Symbolic(object):
         check(lib().scilmm_sets_finish_wide_timing(self._h, ms), self._h)
         return tuple(float(v) for v in ms)
 
+    def sets_finish_panel_timing(self):
+        """(``k_sets_spectra``, ``k_sets_panel_tail``) of the last ``Factor.sets_finish_panel_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 2)()
+        check(lib().scilmm_sets_finish_panel_timing(self._h, ms), self._h)
+        return tuple(float(v) for v in ms)
+
     def sets_spa_timing(self):
         """``k_sets_spa`` of the last ``Factor.sets_spa*_dev`` in ms, after ``sync()``."""
         ms = (C.c_double * 1)()
@@ -540,6 +546,22 @@ class Factor(object):
         rho = np.ascontiguousarray(rho, dtype=np.float64)
         check(lib().scilmm_sets_finish_wide_dev(self._h, k, block, q, dstats_ptr, dgram_ptr, dcross_ptr, ld_cross, dR_ptr, du_ptr, c,
                                                 weight_mode, dweights_ptr, method, ptr(rho), rho.size, dout_ptr, dlam_ptr), self.sym._h)
+
+    def sets_finish_panel_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method, rho,
+                              dxty_ptr, ld_xty, t, dtscale_ptr, dhead_ptr, dout_ptr):
+        """Everything after a Gram block and its ``scan_panel_dev``, for the block's sets against the ``t`` traits of the panel
+        (``scilmm_sets_finish_panel_dev``): a set's spectra once, then a tail per trait from the scores ``dxty_ptr`` (r x ``t``,
+        ``ld_xty`` apart).  ``set_start`` and ``rho`` as for ``sets_finish_dev``; ``dtscale_ptr``: ``t`` positive scales on the
+        device, or None (all 1).  ``n_sets`` rows of 4 doubles (n_used, w'Kw, flags, 0) go to ``dhead_ptr`` and ``n_sets * t`` rows
+        of 8 (1'(w o s), burden_chi2, skat_q, skat_p, skato_p, skato_pmin, skato_rho, flags; row = set * t + trait) to
+        ``dout_ptr``; enqueues without synchronising (``scilmm_amd.set_panel.SetTraitPanel`` is the interface).  The traits of a tail
+        workgroup are chosen by the engine; the environment variable ``SCILMM_SETS_PANEL_GROUP`` (1 .. 32), read per call, takes
+        its place -- the numbers do not depend on it."""
+        set_start = np.ascontiguousarray(set_start, dtype=np.int32)
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        check(lib().scilmm_sets_finish_panel_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, c, n_sets, ptr(set_start), weight_mode,
+                                                 dweights_ptr, method, ptr(rho), rho.size, dxty_ptr, ld_xty, t, dtscale_ptr, dhead_ptr,
+                                                 dout_ptr), self.sym._h)
 
     def sets_finish_scaled_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method,
                                rho, dout_ptr, ld_out, dlam_ptr, dvscale_ptr):

@@ -18,8 +18,8 @@ permuting phenotypes is wrong under a kinship covariance, Bonferroni ignores LD.
 ``w(y*) = w(C) beta + z``, ``z ~ N(0, I)``, so the replicates are drawn where they are used and need no solve at all.
 
 Out of scope: per-trait missing phenotypes (``check_traits`` refuses a NaN: drop the individuals or run the traits one by one),
-another V per trait, panels on ``InteractionScan`` or ``VariantSetTest`` (a panel is built from an ``AssociationScan`` only),
-distributed handles and fp32 fronts (the C entry point refuses both).  There is no CPU form of the device side; the host
+another V per trait, panels on ``InteractionScan`` (a marker panel is built from an ``AssociationScan`` only; the variant-set
+tests of a ``VariantSetTest`` against a panel are ``tester.set_traits(Y)``, ``scilmm_amd.set_panel``), distributed handles and fp32 fronts (the C entry point refuses both).  There is no CPU form of the device side; the host
 algebra (``panel_stats``, ``panel_thresholds``) and the argument checks are pure NumPy.
 """
 import numpy as np

@@ -202,7 +202,32 @@ def skato_breaks(al, be, level):
     return z0, np.unique(pts)
 
 
-def skato_pvalue(t, A, rho=RHO_DEFAULT, method="saddlepoint"):
+def skato_spectra(A, rho):
+    """What ``skato_pvalue`` takes from ``A`` alone (r x r, symmetric; ``rho`` checked): ``(lams, lamB)``, the spectra above the
+    floor of ``L_rho' A L_rho`` per grid value (capped at ``RHO_CAP``) and of ``B = A - a a' / s11`` (empty where the remainder term
+    does not exist).  A caller with many score vectors against one ``A`` computes it once (``scilmm_amd.set_panel``)."""
+    r = A.shape[0]
+    lams, one = [], np.ones((r, r))
+    for x in np.minimum(rho, RHO_CAP):
+        if r == 1:
+            lam = _floor(A.ravel())
+        else:
+            L = la.cholesky((1.0 - x) * np.eye(r) + x * one, lower=True)
+            M = L.T.dot(A).dot(L)
+            lam = _floor(la.eigvalsh(0.5 * (M + M.T)))
+        lams.append(lam)
+    tr = float(np.trace(A))
+    a = A.sum(axis=1)
+    s11 = float(a.sum())
+    lamB = np.empty(0)
+    if r > 1 and s11 > LAMBDA_FLOOR * tr:
+        B = A - np.outer(a, a) / s11
+        B = 0.5 * (B + B.T)
+        lamB = _floor(la.eigvalsh(B), LAMBDA_FLOOR * tr)
+    return lams, lamB
+
+
+def skato_pvalue(t, A, rho=RHO_DEFAULT, method="saddlepoint", spectra=None):
     """SKAT-O from ``t = w o s`` and ``A = diag(w) K diag(w)`` (r x r, positive semidefinite): ``(p, pmin, rho_at_min, p_rho)``.
 
     Per grid value: ``Q_rho = (1 - rho) t't + rho (1't)^2`` against the mixture with the eigenvalues of ``L_rho' A L_rho``
@@ -218,41 +243,32 @@ def skato_pvalue(t, A, rho=RHO_DEFAULT, method="saddlepoint"):
     of ``delta`` and up to ``z0``, where the argument reaches 0 and the rest is ``2 Phi(-z0)``; then ``p <- min(p, n_rho T)``.
     A value of ``rho`` above 0.999 is computed as 0.999.  One marker, ``s11 <= LAMBDA_FLOOR trace(A)`` or no eigenvalue of ``B``
     above ``LAMBDA_FLOOR trace(A)`` (rank one: what is left of ``B`` is rounding): every ``p_rho`` is the same up to rounding,
-    ``p = T`` and ``rho_at_min`` is the first grid value."""
+    ``p = T`` and ``rho_at_min`` is the first grid value.  ``spectra``: None, or ``skato_spectra(A, rho)`` of the same ``A`` and
+    ``rho``, computed once for many ``t``."""
     t = np.asarray(t, dtype=np.float64).ravel()
     A = np.asarray(A, dtype=np.float64).reshape(t.size, t.size)
     rho, sf = check_rho(rho), check_method(method)
     r, nr = t.size, rho.size
     rc = np.minimum(rho, RHO_CAP)
     tt, t1 = float(t.dot(t)), float(t.sum())
-    p_rho, lams = np.full(nr, np.nan), []
-    one = np.ones((r, r))
+    p_rho = np.full(nr, np.nan)
+    lams, lamB = skato_spectra(A, rho) if spectra is None else spectra
     for j, x in enumerate(rc):
-        if r == 1:
-            q, lam = tt, _floor(A.ravel())                  # ((1 - rho) q + rho q is not q bit for bit)
-        else:
-            L = la.cholesky((1.0 - x) * np.eye(r) + x * one, lower=True)
-            M = L.T.dot(A).dot(L)
-            q, lam = (1.0 - x) * tt + x * t1 * t1, _floor(la.eigvalsh(0.5 * (M + M.T)))
-        lams.append(lam)
+        q, lam = tt if r == 1 else (1.0 - x) * tt + x * t1 * t1, lams[j]   # ((1 - rho) q + rho q is not q bit for bit)
         if lam.size:
             p_rho[j] = sf(q, lam)
     if np.any(np.isnan(p_rho)):
         return np.nan, np.nan, np.nan, p_rho
     j0 = int(np.argmin(p_rho))
     T = float(p_rho[j0])
-    tr = float(np.trace(A))
     a = A.sum(axis=1)
     s11 = float(a.sum())
-    lamB = np.empty(0)
-    if r > 1 and s11 > LAMBDA_FLOOR * tr:
-        B = A - np.outer(a, a) / s11
-        B = 0.5 * (B + B.T)
-        lamB = _floor(la.eigvalsh(B), LAMBDA_FLOOR * tr)
     if not lamB.size:                  # every p_rho is the same up to rounding: the first grid value stands for the minimiser
         return T, T, float(rho[0]), p_rho
     if T == 0.0:                       # (T has underflowed: so has p, and the quantile of 0 is infinite)
         return T, T, float(rho[j0]), p_rho
+    B = A - np.outer(a, a) / s11
+    B = 0.5 * (B + B.T)
     l2 = float(np.sum(lamB ** 2))
     mu, var, df = float(lamB.sum()), 2.0 * l2 + 4.0 * max(float(a.dot(B).dot(a)), 0.0) / s11, l2 * l2 / float(np.sum(lamB ** 4))
     sd = np.sqrt(var)
@@ -478,6 +494,15 @@ class VariantSetTest(AssociationScan):
         markers in deterministic mode.  ``skato``, ``rho``, ``finish``, ``max_markers``: as for ``__call__``."""
         return self._run(self._dosage_source(dosages, sample_index), sets, weights, method, return_kernel, skato, rho, finish,
                          max_markers=max_markers)
+
+    def set_traits(self, Y, scale="fixed"):
+        """The variant-set tests of this tester against a panel of T quantitative traits under the same V: a ``SetTraitPanel``
+        (``scilmm_amd.set_panel``) on this tester's factor and whitening.  ``Y``: n x T float64, finite, 1 <= T <= 4096, rows in
+        the order of ``mats``; ``scale``: "fixed" or "profile", as for ``traits`` (which stays the MARKER panel of the scan).
+        ``panel(genotypes, sets, ...)`` tests every set against every trait for one sweep, one Gram pass and one
+        eigendecomposition per set, whatever T is."""
+        from .set_panel import SetTraitPanel
+        return SetTraitPanel(self, Y, scale)
 
     def _block(self, src):
         """rows -> ((q + 4) x r statistics, r x r Gram matrix) of one block of the marker source ``src``, on the host: the rows
