@@ -519,6 +519,49 @@ int scilmm_sets_finish_panel_dev(scilmm_factor* fac, int32_t r, int32_t q, const
  * follows it: ms[0] k_sets_spectra, ms[1] k_sets_panel_tail (tools/sets_panel_timing.py).  No counterpart in the reference. */
 int scilmm_sets_finish_panel_timing(const scilmm_symbolic* sym, double* ms);
 
+/* Variant-set tests under annotation masks and MAF cutoffs: scilmm_sets_finish_dev for every set of a
+ * Gram block under n_ann masks crossed with n_cut cutoffs of the minor allele frequency, with ACAT-V (Liu et al. 2019, in
+ * STAAR's form) next to burden, SKAT and SKAT-O, queued on the handle's stream behind the block.  Every cell of a set is a
+ * principal submatrix of the set's K and a sub-vector of its score: the block is swept once, and one workgroup per
+ * (set, annotation, cutoff) finishes its cell from the statistics and the Gram matrix where the block left them
+ * (k_sets_finish_masks, the threads and the LDS of k_sets_finish).
+ *   r, q, d_stats, d_gram, d_R, d_u, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho: as for
+ *            scilmm_sets_finish_dev.
+ *   d_ann, n_ann: r uint32 words on the device, one per column of the block: bit a set = the column is in annotation a;
+ *            1 <= n_ann <= 32 (bits from n_ann up are not looked at).
+ *   maf_cut, n_cut: HOST, 1 .. 8 cutoffs in (0, 0.5], read before the call returns.
+ *   acat_mac: >= 0 and finite: ACAT-V pools the markers whose minor allele count is at most this.
+ *   d_out  : n_sets n_ann n_cut rows of ld_out >= 12 + n_rho doubles, row = (set n_ann + a) n_cut + f.  Cell (a, f) of a set
+ *            holds the columns that scilmm_sets_finish_dev keeps AND that carry bit a AND whose maf <= maf_cut[f], with
+ *            maf = min(0.5 mean, 1 - 0.5 mean) from the `mean` row (the expression of weight mode 0; scilmm_amd.set_masks.maf_of
+ *            is the same expression on the host, so membership cannot differ between the two).  The first 10 + n_rho doubles
+ *            are the row of scilmm_sets_finish_dev for a block that holds the cell's columns alone -- the same routines on the
+ *            cell's index list, the same bits --, then  acatv_p | n_pooled.  An empty cell: n_used = 0, flags = 0,
+ *            n_pooled = 0, the rest NaN.  Exactly 12 + n_rho doubles of every row are written.
+ * ACAT-V of a cell, from s, w and K of its kept markers: mac_j = 2 n_obs_j maf_j; a marker with mac_j > acat_mac and K_jj > 0
+ * is a term p_j = erfc(sqrt(s_j^2 / 2 K_jj)) of weight omega_j = w_j^2 maf_j (1 - maf_j); the markers with mac_j <= acat_mac
+ * (n_pooled of them) are one term, p = erfc(sqrt((sum w_j s_j)^2 / 2 sum_ij w_i K_ij w_j)) over the pool, left out where the
+ * quadratic form is not positive, of weight the mean of the pool's omega_j.  Terms of weight 0 are left out; without a term
+ * acatv_p is NaN.  T = sum omega tan((0.5 - p) pi) / sum omega, with p capped at 1 - 1e-15 and 1 / (p pi) for the tangent
+ * where p < 1e-15; acatv_p = 0.5 - atan(T) / pi, 1 / (T pi) where T > 1e15; a term with p = 0 gives 0.  (The two functions
+ * are evaluated without their cancellations: the tangent as 1 / tan(p pi) below p = 0.5, the p-value as atan(1 / T) / pi above
+ * T = 1, so a small p keeps its digits and the branches are continuous.  The kernel takes s_j^2 / K_jj as t_j^2 / A_jj from
+ * t = w o s and A = diag(w) K diag(w) while A is in LDS: the same number wherever omega_j > 0, and no division by a weight.)
+ * No atomics: every sum runs in ascending column order or by the fixed fold, a
+ * cell's numbers depend on its own inputs alone, and scilmm_timing.n_float_atomic_launches is not touched.  Enqueued without
+ * synchronising; nothing is allocated and nothing of the factor is read.  SCILMM_ERR_ARG before anything of the handle or of
+ * the device is read: what scilmm_sets_finish_dev rejects, a null d_ann or maf_cut, n_ann outside 1 .. 32, n_cut outside
+ * 1 .. 8, a cutoff outside (0, 0.5] or NaN, acat_mac negative or not finite, ld_out < 12 + n_rho.  Refusals as for
+ * scilmm_sets_finish_dev.  scilmm_amd.VariantSetTest.masks is the interface.  No counterpart in the reference. */
+int scilmm_sets_finish_masks_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram, const double* d_R,
+                                 const double* d_u, int32_t c, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                                 const double* d_weights, int32_t method, const double* rho, int32_t n_rho, const uint32_t* d_ann,
+                                 int32_t n_ann, const double* maf_cut, int32_t n_cut, double acat_mac, double* d_out, int64_t ld_out);
+
+/* HIP-event time of the last scilmm_sets_finish_masks_dev on the handle, in milliseconds, valid after the scilmm_sync that
+ * follows it: ms[0] k_sets_finish_masks (tools/sets_masks_timing.py).  No counterpart in the reference. */
+int scilmm_sets_finish_masks_timing(const scilmm_symbolic* sym, double* ms);
+
 /* The finish of ONE variant set of k markers, 1 <= k <= 4 096, that ran as B = ceil(k / block) sub-blocks (DESIGN.md section
  * 22), queued on the handle's stream behind the last of them; everything scilmm_sets_finish_dev computes for a set, for a set
  * wider than one block.  With bp = block rounded up to 16: (B - 1) bp <= 4 096.

@@ -19,4 +19,5 @@ from .glmm import LogisticMixedModel, BinaryScan, BinarySetTest, BinaryWideSetTe
 from . import dosage  # noqa: F401
 from .sets import VariantSetTest  # noqa: F401
 from .set_panel import SetTraitPanel  # noqa: F401
+from .set_masks import MaskedSetTest, acat  # noqa: F401
 from ._lib import ScilmmError, NotPositiveDefiniteError  # noqa: F401

@@ -84,6 +84,7 @@ SYMBOLS = [
     "scilmm_sets_finish_dev", "scilmm_sets_finish_timing", "scilmm_sets_finish_scaled_dev",
     "scilmm_sets_finish_wide_dev", "scilmm_sets_finish_wide_timing",
     "scilmm_sets_finish_panel_dev", "scilmm_sets_finish_panel_timing",
+    "scilmm_sets_finish_masks_dev", "scilmm_sets_finish_masks_timing",
     "scilmm_sets_spa_dev", "scilmm_sets_spa_bed_dev", "scilmm_sets_spa_dosage_dev", "scilmm_sets_spa_timing",
     "scilmm_sets_collapse_dev", "scilmm_sets_collapse_bed_dev", "scilmm_sets_collapse_dosage_dev",
     "scilmm_sets_spa_wide_dev", "scilmm_sets_finish_wide_scaled_dev", "scilmm_sets_spa_wide_timing",
@@ -205,6 +206,9 @@ def lib():
     # fac, r, q, d_stats, d_gram, d_R, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_xty, ld_xty, t, d_tscale, d_head, d_out
     L.scilmm_sets_finish_panel_dev.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, i64, i32, vp, vp, vp]
     L.scilmm_sets_finish_panel_timing.argtypes = [vp, P(dbl)]
+    # ... as scilmm_sets_finish_dev up to n_rho, then d_ann, n_ann, maf_cut, n_cut, acat_mac, d_out, ld_out
+    L.scilmm_sets_finish_masks_dev.argtypes = L.scilmm_sets_finish_dev.argtypes[:15] + [vp, i32, vp, i32, dbl, vp, i64]
+    L.scilmm_sets_finish_masks_timing.argtypes = [vp, P(dbl)]
     L.scilmm_sets_finish_scaled_dev.argtypes = L.scilmm_sets_finish_dev.argtypes + [vp]     # ... d_vscale
     # d_stats, d_gram, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa, n_sets, set_start, weight_mode, d_weights, d_bspa, d_vscale
     sspa = [vp, vp, vp, vp, vp, vp, i32, vp, dbl, vp, i32, vp, i32, vp, vp, vp]

@@ -450,6 +450,62 @@ int sets_finish_panel(scilmm_factor* fac, const PanelFinishArgs& p, const char* 
   return SCILMM_OK;
 }
 
+// What scilmm_sets_finish_masks_dev takes beside the factor: the block and the sets of FinishArgs (d_lam is not used), the
+// annotation words, the cutoffs (a HOST array, read here) and ACAT-V's pooling bound.
+struct MasksFinishArgs {
+  FinishArgs fin;
+  const uint32_t* d_ann;
+  int32_t n_ann;
+  const double* maf_cut;
+  int32_t n_cut;
+  double acat_mac;
+  // before anything of the handle is read (a NaN cutoff or bound fails its comparison)
+  static bool args_ok(const scilmm_factor* fac, const MasksFinishArgs& a) {
+    if (!a.d_ann || !a.maf_cut || a.n_ann < 1 || a.n_ann > MASK_ANN_MAX || a.n_cut < 1 || a.n_cut > MASK_CUT_MAX ||
+        !(a.acat_mac >= 0.0 && std::isfinite(a.acat_mac)) || a.fin.n_rho < 0 || a.fin.ld_out < FIN_HEAD + MASK_TAIL + (int64_t)a.fin.n_rho)
+      return false;
+    for (int32_t i = 0; i < a.n_cut; ++i)
+      if (!(a.maf_cut[i] > 0.0 && a.maf_cut[i] <= 0.5)) return false;
+    return FinishArgs::args_ok(fac, a.fin);
+  }
+};
+
+// The finish of the sets of a Gram block under n_ann annotation masks crossed with n_cut MAF cutoffs
+// (scilmm_sets_finish_masks_dev; setmasks.hip.h): the refusals of sets_finish, then k_sets_finish_masks
+// between the call's own events, one workgroup per (set, annotation, cutoff), its LDS sized by the block's largest set.  Nothing of
+// the factor is read and nothing of the work buffers is touched; nothing is allocated.
+int sets_finish_masks(scilmm_factor* fac, const MasksFinishArgs& p, const char* who) {
+  scilmm_symbolic* sym = fac->sym;
+  const DevGuard guard(sym);
+  TRY(check_half(fac, who));
+  TRY(settle(fac, who));
+  Dev* D = (Dev*)sym->device;
+  const FinishArgs& a = p.fin;
+  FinSets sets{};
+  FinCuts cuts{};
+  int32_t widest = 0;
+  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
+  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
+  for (int32_t j = 0; j < a.n_rho; ++j) sets.grid.rho[j] = a.rho[j];
+  for (int32_t j = 0; j < p.n_cut; ++j) cuts.cut[j] = p.maf_cut[j];
+  const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
+  const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
+  // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
+  HIPCHK(hipFuncSetAttribute((const void*)k_sets_finish_masks, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
+  if (!D->mfin_ev[0])
+    for (auto& e : D->mfin_ev) HIPCHK(hipEventCreate(&e));
+  hipStream_t s0 = D->stream;
+  HIPCHK(hipEventRecord(D->mfin_ev[0], s0));
+  hipLaunchKernelGGL(k_sets_finish_masks, dim3((unsigned)(a.n_sets * p.n_ann * p.n_cut)), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats,
+                     a.d_gram, a.d_R, a.d_u, sets, a.weight_mode, a.d_weights, a.method, a.n_rho, cap, p.d_ann, p.n_ann, cuts, p.n_cut,
+                     p.acat_mac, a.d_out, a.ld_out);
+  HIPCHK(hipEventRecord(D->mfin_ev[1], s0));
+  D->mfin_pending = true;
+  HIPCHK(hipGetLastError());
+  return SCILMM_OK;
+}
+
 // What scilmm_sets_finish_wide_dev takes beside the factor.
 struct WideArgs {
   int32_t k, block, q;

@@ -349,6 +349,9 @@ struct Dev {
   hipEvent_t pfin_ev[3] = {nullptr, nullptr, nullptr};  // begin | k_sets_spectra done | k_sets_panel_tail done
   bool pfin_pending = false;            // a panel finish whose events have not been read yet (scilmm_sync)
   double pfin_ms[2] = {0.0, 0.0};       // the last call's k_sets_spectra | k_sets_panel_tail (scilmm_sets_finish_panel_timing)
+  hipEvent_t mfin_ev[2] = {nullptr, nullptr};  // k_sets_finish_masks begin | done (the first masks finish creates them)
+  bool mfin_pending = false;            // a masks finish whose events have not been read yet (scilmm_sync)
+  double mfin_ms = 0.0;                 // the last call's k_sets_finish_masks (scilmm_sets_finish_masks_timing)
   hipEvent_t sspa_ev[2] = {nullptr, nullptr};  // k_sets_spa begin | done (the first set SPA call creates them)
   bool sspa_pending = false;            // a set SPA call whose events have not been read yet (scilmm_sync)
   double sspa_ms = 0.0;                 // the last call's k_sets_spa (scilmm_sets_spa_timing)

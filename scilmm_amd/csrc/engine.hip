@@ -1,9 +1,9 @@
 // The numeric C-ABI entry points of include/scilmm_hip.h.  This is the one translation unit of the numeric phase's kernels
-// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setmath.hip.h, setfinish.hip.h, setpanel.hip.h, setwide.hip.h, setspa.hip.h, setspawide.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
+// (kernels.hip.h, scan.hip.h, gram.hip.h, panel.hip.h, bed.hip.h, dosage.hip.h, spa.hip.h, setmath.hip.h, setfinish.hip.h, setpanel.hip.h, setmasks.hip.h, setwide.hip.h, setspa.hip.h, setspawide.hip.h, blup.hip.h); the host side behind the entry points is included by feature:
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_panel, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide, rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_panel, sets_finish_masks, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide, rel_block, rows_block;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
@@ -38,6 +38,7 @@
 #include "spa.hip.h"
 #include "setfinish.hip.h"
 #include "setpanel.hip.h"
+#include "setmasks.hip.h"
 #include "setwide.hip.h"
 #include "setspa.hip.h"
 #include "setspawide.hip.h"
@@ -393,6 +394,17 @@ int scilmm_sets_finish_panel_dev(scilmm_factor* fac, int32_t r, int32_t q, const
   return sets_finish_panel(fac, a, __func__);
 }
 
+// The variant-set finish of a Gram block under annotation masks and MAF cutoffs: a cell per (set, annotation, cutoff), with ACAT-V
+int scilmm_sets_finish_masks_dev(scilmm_factor* fac, int32_t r, int32_t q, const double* d_stats, const double* d_gram, const double* d_R,
+                                 const double* d_u, int32_t c, int32_t n_sets, const int32_t* set_start, int32_t weight_mode,
+                                 const double* d_weights, int32_t method, const double* rho, int32_t n_rho, const uint32_t* d_ann,
+                                 int32_t n_ann, const double* maf_cut, int32_t n_cut, double acat_mac, double* d_out, int64_t ld_out) {
+  const FinishArgs f{r, q, d_stats, d_gram, d_R, d_u, c, n_sets, set_start, weight_mode, d_weights, method, rho, n_rho, d_out, ld_out, nullptr};
+  const MasksFinishArgs a{f, d_ann, n_ann, maf_cut, n_cut, acat_mac};
+  if (!MasksFinishArgs::args_ok(fac, a)) return SCILMM_ERR_ARG;
+  return sets_finish_masks(fac, a, __func__);
+}
+
 // The finish of ONE set of up to 4 096 markers behind its sub-blocks: a pure function of what they left behind
 int scilmm_sets_finish_wide_dev(scilmm_factor* fac, int32_t k, int32_t block, int32_t q, const double* d_stats, const double* d_gram,
                                 const double* d_cross, int64_t ld_cross, const double* d_R, const double* d_u, int32_t c,
@@ -708,6 +720,12 @@ int scilmm_sync(scilmm_symbolic* sym) {
     HIPCHK(hipEventElapsedTime(&a, D->fin_ev[0], D->fin_ev[1]));
     D->fin_ms = a;
   }
+  if (D->mfin_pending) {
+    D->mfin_pending = false;
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, D->mfin_ev[0], D->mfin_ev[1]));
+    D->mfin_ms = a;
+  }
   if (D->pfin_pending) {
     D->pfin_pending = false;
     for (int i = 0; i < 2; ++i) {
@@ -801,6 +819,12 @@ int scilmm_sets_finish_panel_timing(const scilmm_symbolic* sym, double* ms) {
   if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
   const Dev* D = (const Dev*)sym->device;
   for (int i = 0; i < 2; ++i) ms[i] = D->pfin_ms[i];
+  return SCILMM_OK;
+}
+
+int scilmm_sets_finish_masks_timing(const scilmm_symbolic* sym, double* ms) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  ms[0] = ((const Dev*)sym->device)->mfin_ms;
   return SCILMM_OK;
 }
 

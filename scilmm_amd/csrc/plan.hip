@@ -52,6 +52,8 @@ void dev_free(void* p) {
   if (D->pfin_rec) (void)hipFree(D->pfin_rec);
   for (auto& e : D->pfin_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : D->mfin_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : D->scan_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : D->gxe_ev)

@@ -295,6 +295,12 @@ class Symbolic(object):
         check(lib().scilmm_sets_finish_panel_timing(self._h, ms), self._h)
         return tuple(float(v) for v in ms)
 
+    def sets_finish_masks_timing(self):
+        """``k_sets_finish_masks`` of the last ``Factor.sets_finish_masks_dev`` in ms, after ``sync()``."""
+        ms = (C.c_double * 1)()
+        check(lib().scilmm_sets_finish_masks_timing(self._h, ms), self._h)
+        return float(ms[0])
+
     def sets_spa_timing(self):
         """``k_sets_spa`` of the last ``Factor.sets_spa*_dev`` in ms, after ``sync()``."""
         ms = (C.c_double * 1)()
@@ -562,6 +568,22 @@ class Factor(object):
         check(lib().scilmm_sets_finish_panel_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, c, n_sets, ptr(set_start), weight_mode,
                                                  dweights_ptr, method, ptr(rho), rho.size, dxty_ptr, ld_xty, t, dtscale_ptr, dhead_ptr,
                                                  dout_ptr), self.sym._h)
+
+    def sets_finish_masks_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method,
+                              rho, dann_ptr, n_ann, maf_cut, acat_mac, dout_ptr, ld_out):
+        """Everything after a Gram block for the block's sets under ``n_ann`` annotation masks crossed with the MAF cutoffs
+        ``maf_cut``, one workgroup per (set, annotation, cutoff) (``scilmm_sets_finish_masks_dev``).  ``set_start`` and ``rho`` as
+        for ``sets_finish_dev``; ``dann_ptr``: ``r`` uint32 words on the device, bit a = the column is in annotation a;
+        ``maf_cut`` (host float64, 1 .. 8 values in (0, 0.5]) is read before the call returns; ``acat_mac``: ACAT-V's pooling
+        bound.  ``n_sets * n_ann * len(maf_cut)`` rows of ``12 + len(rho)`` doubles go to ``dout_ptr`` (row = (set n_ann + a)
+        n_cut + f: the row of ``sets_finish_dev``, then acatv_p and n_pooled); enqueues without synchronising
+        (``scilmm_amd.set_masks.MaskedSetTest`` is the interface)."""
+        set_start = np.ascontiguousarray(set_start, dtype=np.int32)
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        maf_cut = np.ascontiguousarray(maf_cut, dtype=np.float64)
+        check(lib().scilmm_sets_finish_masks_dev(self._h, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, ptr(set_start),
+                                                 weight_mode, dweights_ptr, method, ptr(rho), rho.size, dann_ptr, n_ann, ptr(maf_cut),
+                                                 maf_cut.size, float(acat_mac), dout_ptr, ld_out), self.sym._h)
 
     def sets_finish_scaled_dev(self, r, q, dstats_ptr, dgram_ptr, dR_ptr, du_ptr, c, n_sets, set_start, weight_mode, dweights_ptr, method,
                                rho, dout_ptr, ld_out, dlam_ptr, dvscale_ptr):

@@ -504,6 +504,16 @@ class VariantSetTest(AssociationScan):
         from .set_panel import SetTraitPanel
         return SetTraitPanel(self, Y, scale)
 
+    def masks(self, annotations, max_maf=(0.01, 0.001, 0.0001), acat_mac=10):
+        """The variant-set tests of this tester under functional annotation masks crossed with MAF cutoffs, with ACAT-V per cell
+        and the ACAT-O combination per set: a ``MaskedSetTest`` (``scilmm_amd.set_masks``) on this tester's factor and whitening.
+        ``annotations``: m x A booleans (rows as ``sets`` index the marker source), or a sequence aligned with ``sets`` of k_i x A
+        booleans, 1 <= A <= 32; ``max_maf``: 1 .. 8 cutoffs in (0, 0.5]; ``acat_mac``: ACAT-V pools the markers whose minor allele
+        count is at most this.  ``masked(genotypes, sets, ...)`` tests every (set, annotation, cutoff) cell for one sweep and one
+        Gram pass per block of sets."""
+        from .set_masks import MaskedSetTest
+        return MaskedSetTest(self, annotations, max_maf, acat_mac)
+
     def _block(self, src):
         """rows -> ((q + 4) x r statistics, r x r Gram matrix) of one block of the marker source ``src``, on the host: the rows
         are brought to the device, one call of the form's Gram entry point, one wait, two device-to-host copies."""
