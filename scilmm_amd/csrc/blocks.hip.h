@@ -1,9 +1,20 @@
 // The block calls on a resident factor (included by engine.hip only, behind sweep.hip.h; the entry points' argument checks
 // stay there): BlockCall, marker_block for the marker scan's input forms and their fills (with environment columns: the gxe
-// blocks), rel_block and rows_block for the BLUP.
+// blocks), rel_block and rows_block for the BLUP; PostCall, the frame of every call that runs behind a block (the panel, the
+// keep, the saddlepoints, the set finishes, the collapse), with grow_synced for the handle's buffers such a call grows and
+// set_layout for what the finishes of a block's sets derive from the offsets.  Every call family times itself with its
+// StageTimer of the device state (dev.h): start, mark .., close; scilmm_sync reads them.
 #pragma once
 
 namespace {
+
+// A grow-only buffer of the handle that something queued may still read: the stream is synchronised first, and only where
+// the buffer has to grow.
+template <typename T>
+int grow_synced(scilmm_symbolic* sym, Dev* D, T** ptr, size_t* cap, size_t need) {
+  if (*cap < need) HIPCHK(hipStreamSynchronize(D->stream));
+  return grow(sym, ptr, cap, need);
+}
 
 // What makes a marker block a marker x environment block: m environment columns d_E (n x m row-major, PERMUTED order), r markers
 // of d = 1 + m terms each (column a r + c of the block = term a of marker c), the cross products' rows of the statistics.
@@ -39,33 +50,24 @@ struct BlockCall {
   explicit BlockCall(scilmm_factor* f) : fac(f), sym(f->sym), guard(f->sym) {}
 
   // the refusals, the slice partial sums (allocated on the first call on a handle, or for a wider q; nothing is allocated
-  // per block afterwards), the events and the inverse permutation; `gram`: the partial tiles of X^T X as well (allocated on
-  // the first Gram block on a handle, for the widest block: never again); `pairs`: a gxe block's rows of cross products, which
-  // take the statistics' partial sums over once those are folded, and its two events
+  // per block afterwards) and the inverse permutation; `gram`: the partial tiles of X^T X as well (allocated on the first
+  // Gram block on a handle, for the widest block: never again); `pairs`: a gxe block's rows of cross products, which take the
+  // statistics' partial sums over once those are folded
   int begin(int32_t q, const char* who, bool gram = false, int32_t pairs = 0) {
     TRY(check_half(fac, who));
     TRY(begin_rhs(fac, who));
     D = (Dev*)sym->device;
     const int64_t nslice = ((int64_t)sym->S->n + SCAN_SLICE - 1) / SCAN_SLICE;
     const size_t need = (size_t)nslice * (size_t)std::max(q + 1, pairs) * RPMAX;
-    if (D->scan_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-    TRY(grow(sym, &D->scan_partial, &D->scan_partial_cap, need));
-    if (gram) {
-      const size_t gneed = (size_t)gram_slices(GRAM_SLICE_MIN) * GRAM_TILES * 256;
-      if (D->gram_partial_cap < gneed) HIPCHK(hipStreamSynchronize(D->stream));
-      TRY(grow(sym, &D->gram_partial, &D->gram_partial_cap, gneed));
-    }
-    if (!D->scan_ev[0])
-      for (auto& e : D->scan_ev) HIPCHK(hipEventCreate(&e));
-    if (pairs > 0 && !D->gxe_ev[0])
-      for (auto& e : D->gxe_ev) HIPCHK(hipEventCreate(&e));
+    TRY(grow_synced(sym, D, &D->scan_partial, &D->scan_partial_cap, need));
+    if (gram) TRY(grow_synced(sym, D, &D->gram_partial, &D->gram_partial_cap, (size_t)gram_slices(GRAM_SLICE_MIN) * GRAM_TILES * 256));
     return ensure_iperm(sym, D);
   }
 
   int open(int32_t r, bool zero_W) {
     sw.emplace(fac, D);
     sw->set_block(r);
-    HIPCHK(hipEventRecord(D->scan_ev[0], D->stream));
+    HIPCHK(D->scan_t.start(D->stream));
     if (zero_W) HIPCHK(hipMemsetAsync(D->W, 0, sizeof(double) * (size_t)sw->tot, D->stream));
     return SCILMM_OK;
   }
@@ -81,9 +83,9 @@ struct BlockCall {
     const int32_t n = sym->S->n;
     hipStream_t s0 = D->stream;
     const int64_t nslice = ((int64_t)n + SCAN_SLICE - 1) / SCAN_SLICE;
-    HIPCHK(hipEventRecord(D->scan_ev[1], s0));
+    HIPCHK(D->scan_t.mark(s0, 1));
     TRY(sw->forward_single());
-    HIPCHK(hipEventRecord(D->scan_ev[2], s0));
+    HIPCHK(D->scan_t.mark(s0, 2));
     const auto k_stats = q <= 8 ? k_scan_stats<8, 4> : q <= 16 ? k_scan_stats<16, 2> : k_scan_stats<SCAN_QMAX, 1>;
     hipLaunchKernelGGL(k_stats, dim3((unsigned)nslice), dim3(256), 0, s0, n, sw->rp, (const double*)D->X, d_Q, q, D->scan_partial);
     hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)(q + 1)), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, q, r, d_out);
@@ -96,14 +98,13 @@ struct BlockCall {
     }
     if (gxe) {
       const int32_t pairs = gxe->pairs();
-      HIPCHK(hipEventRecord(D->gxe_ev[1], s0));
+      HIPCHK(D->scan_t.mark(s0, 5));
       hipLaunchKernelGGL(cross_kernel(gxe->m + 1, gxe->r), dim3((unsigned)nslice), dim3(256), 0, s0, n, gxe->r, sw->rp, (const double*)D->X,
                          D->scan_partial);
       hipLaunchKernelGGL(k_scan_fold, dim3((unsigned)pairs), dim3(SCAN_FOLD * RPMAX), 0, s0, nslice, (const double*)D->scan_partial, pairs - 1,
                          gxe->r, gxe->d_cross);
     }
-    HIPCHK(hipEventRecord(D->scan_ev[3], s0));
-    D->scan_pending = true;
+    HIPCHK(D->scan_t.close(s0));
     D->gxe_pending = gxe != nullptr;
     D->block_r = r;  // X holds this block until the work buffers are asked for again (scan_panel)
     D->block_rp = sw->rp;
@@ -131,7 +132,7 @@ int marker_block(scilmm_factor* fac, const char* who, int32_t r, const double* d
   const int32_t n = sym->S->n;
   fill(b.D, n, b.sw->rp);
   if (d_E) {
-    HIPCHK(hipEventRecord(b.D->gxe_ev[0], b.D->stream));
+    HIPCHK(b.D->scan_t.mark(b.D->stream, 4));
     hipLaunchKernelGGL(k_scan_expand<4>, dim3((unsigned)(((int64_t)n + GXE_ROWS - 1) / GXE_ROWS)), dim3(256), 0, b.D->stream, n, r, m, b.sw->rp,
                        d_E, b.D->W);
   }
@@ -167,6 +168,27 @@ auto fill_dosage(const void* d_dos, int64_t ld, int32_t n_samples, const int32_t
   };
 }
 
+// The frame of a call that runs behind a block and sweeps nothing itself: the handle's device made current, the refusals of
+// the half-solves, the factor settled -- in that order --, then the device state, n and the stream.  Whatever the call asks
+// next (block_left, its buffers) comes after begin.
+struct PostCall {
+  scilmm_factor* const fac;
+  scilmm_symbolic* const sym;
+  const DevGuard guard;
+  Dev* D = nullptr;
+  int32_t n = 0;
+  hipStream_t s0 = nullptr;
+  explicit PostCall(scilmm_factor* f) : fac(f), sym(f->sym), guard(f->sym) {}
+  int begin(const char* who) {
+    TRY(check_half(fac, who));
+    TRY(settle(fac, who));
+    D = (Dev*)sym->device;
+    n = sym->S->n;
+    s0 = D->stream;
+    return SCILMM_OK;
+  }
+};
+
 // What reads the block the last scan block on the handle left in X asks first: that it is still there, and that r is its.
 int block_left(scilmm_symbolic* sym, const Dev* D, const char* who, int32_t r) {
   if (D->block_r == 0) {
@@ -187,30 +209,25 @@ int block_left(scilmm_symbolic* sym, const Dev* D, const char* who, int32_t r) {
 // the work buffers is written: the block stays where it is, and any number of panels may follow one block.
 int scan_panel(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, int32_t t, double* d_xty, int64_t ld_out) {
   const char* who = "scilmm_scan_panel_dev";
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   TRY(block_left(sym, D, who, r));
-  const int32_t n = sym->S->n, rp = D->block_rp, ntile = (rp / 16) * PANEL_NJ;
+  const int32_t n = c.n, rp = D->block_rp, ntile = (rp / 16) * PANEL_NJ;
   const int32_t npanel = (t + PANEL_COLS - 1) / PANEL_COLS;
   const int slice = panel_slice();
   const int64_t nslice = ((int64_t)n + slice - 1) / slice;
   const size_t need = (size_t)(((int64_t)n + PANEL_SLICE_MIN - 1) / PANEL_SLICE_MIN) * (size_t)npanel * PANEL_NI * PANEL_NJ * 256;
-  if (D->panel_partial_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-  TRY(grow(sym, &D->panel_partial, &D->panel_partial_cap, need));
-  if (!D->panel_ev[0])
-    for (auto& e : D->panel_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->panel_ev[0], s0));
+  TRY(grow_synced(sym, D, &D->panel_partial, &D->panel_partial_cap, need));
+  hipStream_t s0 = c.s0;
+  HIPCHK(D->panel_t.start(s0));
   hipLaunchKernelGGL(panel_kernel(slice), dim3((unsigned)nslice, (unsigned)npanel), dim3(256), 0, s0, n, rp, (const double*)D->X, d_Y, ld_y, t,
                      D->panel_partial);
-  HIPCHK(hipEventRecord(D->panel_ev[1], s0));
+  HIPCHK(D->panel_t.mark(s0, 1));
   hipLaunchKernelGGL(k_panel_fold, dim3((unsigned)(npanel * ntile)), dim3(PANEL_FOLD * 256), 0, s0, nslice, npanel, ntile,
                      (const double*)D->panel_partial, r, t, d_xty, ld_out);
-  HIPCHK(hipEventRecord(D->panel_ev[2], s0));
-  D->panel_pending = true;
+  HIPCHK(D->panel_t.close(s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -220,15 +237,13 @@ int scan_panel(scilmm_factor* fac, int32_t r, const double* d_Y, int64_t ld_y, i
 // work buffers is written and the record stays: a Gram pass, panels and further keeps may follow the same block.
 int scan_keep(scilmm_factor* fac, int32_t r, double* d_dst, int64_t ld_dst, int64_t col0) {
   const char* who = "scilmm_scan_block_keep_dev";
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   TRY(block_left(sym, D, who, r));
-  const int32_t n = sym->S->n;
-  const int64_t nchunk = ((int64_t)n + KEEP_ROWS - 1) / KEEP_ROWS;
-  hipLaunchKernelGGL(k_scan_keep, dim3((unsigned)std::min<int64_t>(nchunk, KEEP_GRID)), dim3(256), 0, D->stream, n, D->block_rp,
+  const int64_t nchunk = ((int64_t)c.n + KEEP_ROWS - 1) / KEEP_ROWS;
+  hipLaunchKernelGGL(k_scan_keep, dim3((unsigned)std::min<int64_t>(nchunk, KEEP_GRID)), dim3(256), 0, c.s0, c.n, D->block_rp,
                      (const double*)D->X, d_dst, ld_dst, col0);
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
@@ -251,9 +266,7 @@ struct SpaArgs {
 // The scratch of g^ rows both saddlepoint kernels write (RPMAX x n doubles): allocated by the first call on the handle after a
 // stream synchronise, never again.
 int spa_scratch(scilmm_symbolic* sym, Dev* D) {
-  const size_t need = (size_t)RPMAX * (size_t)std::max(sym->S->n, 1);
-  if (D->spa_scratch_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-  return grow(sym, &D->spa_scratch, &D->spa_scratch_cap, need);
+  return grow_synced(sym, D, &D->spa_scratch, &D->spa_scratch_cap, (size_t)RPMAX * (size_t)std::max(sym->S->n, 1));
 }
 
 // The saddlepoint p-values of the r markers of the plain block queued before this call (scilmm_scan_spa*_dev): the refusals of
@@ -261,21 +274,15 @@ int spa_scratch(scilmm_symbolic* sym, Dev* D) {
 // is touched: the block stays available to scilmm_scan_panel_dev.
 template <class Reader>
 int scan_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const SpaArgs& a) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
-  const int32_t n = sym->S->n;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   TRY(spa_scratch(sym, D));
-  if (!D->spa_ev[0])
-    for (auto& e : D->spa_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->spa_ev[0], s0));
-  hipLaunchKernelGGL(k_scan_spa<Reader>, dim3((unsigned)r), dim3(256), 0, s0, n, r, a.c, rd, a.d_stats, a.d_R, a.d_u, a.d_mu, a.d_C, a.d_Minv, a.cutoff,
-                     D->spa_scratch, a.d_spa);
-  HIPCHK(hipEventRecord(D->spa_ev[1], s0));
-  D->spa_pending = true;
+  HIPCHK(D->spa_t.start(c.s0));
+  hipLaunchKernelGGL(k_scan_spa<Reader>, dim3((unsigned)r), dim3(256), 0, c.s0, c.n, r, a.c, rd, a.d_stats, a.d_R, a.d_u, a.d_mu, a.d_C, a.d_Minv,
+                     a.cutoff, D->spa_scratch, a.d_spa);
+  HIPCHK(D->spa_t.close(c.s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -328,33 +335,42 @@ struct FinishArgs {
   }
 };
 
+// What the three finishes of a block's sets derive from the offsets and the grid (HOST arrays, read here): the kernels' copy
+// of both, the capacity the block's widest set asks for, the workgroup size and the dynamic LDS that go with it.  `kernel` is
+// the one that takes the LDS: more than 64 KiB has to be asked for (for the widest block there can be; the call is cheap and
+// idempotent).
+struct SetLayout {
+  FinSets sets{};
+  int32_t cap = 0, nt = 0;
+  size_t lds = 0;
+};
+int set_layout(scilmm_symbolic* sym, const FinishArgs& a, const void* kernel, SetLayout* l) {
+  int32_t widest = 0;
+  for (int32_t i = 0; i <= a.n_sets; ++i) l->sets.start[i] = a.set_start[i];
+  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
+  for (int32_t j = 0; j < a.n_rho; ++j) l->sets.grid.rho[j] = a.rho[j];
+  l->cap = std::max(2, (widest + 1) & ~1);
+  l->nt = l->cap > 64 ? FIN_NT_MAX : 256;
+  l->lds = sizeof(double) * (size_t)fin_lds_doubles(l->cap, l->nt);
+  HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
+  return SCILMM_OK;
+}
+
 // Everything after a Gram block, for the sets of the block (scilmm_sets_finish_dev, scilmm_sets_finish_scaled_dev): the
 // refusals of the scan blocks, then k_sets_finish between the call's own events, one workgroup per set, its LDS sized by the
 // block's largest set.  Nothing of the factor is read and nothing of the work buffers is touched; nothing is allocated.
 int sets_finish(scilmm_factor* fac, const FinishArgs& a, const char* who) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
-  FinSets sets{};
-  int32_t widest = 0;
-  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
-  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
-  for (int32_t j = 0; j < a.n_rho; ++j) sets.grid.rho[j] = a.rho[j];
-  const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
-  const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
-  // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
-  HIPCHK(hipFuncSetAttribute((const void*)k_sets_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
-  if (!D->fin_ev[0])
-    for (auto& e : D->fin_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->fin_ev[0], s0));
-  hipLaunchKernelGGL(k_sets_finish, dim3((unsigned)a.n_sets), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, a.d_u, sets,
-                     a.weight_mode, a.d_weights, a.method, a.n_rho, cap, a.d_out, a.ld_out, a.d_lam, a.d_vscale);
-  HIPCHK(hipEventRecord(D->fin_ev[1], s0));
-  D->fin_pending = true;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
+  SetLayout l;
+  TRY(set_layout(sym, a, (const void*)k_sets_finish, &l));
+  HIPCHK(D->fin_t.start(c.s0));
+  hipLaunchKernelGGL(k_sets_finish, dim3((unsigned)a.n_sets), dim3((unsigned)l.nt), l.lds, c.s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, a.d_u,
+                     l.sets, a.weight_mode, a.d_weights, a.method, a.n_rho, l.cap, a.d_out, a.ld_out, a.d_lam, a.d_vscale);
+  HIPCHK(D->fin_t.close(c.s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -408,44 +424,30 @@ inline int32_t panel_tail_group(int32_t n_sets, int32_t t, int32_t n_cu) {
 // set, and k_sets_panel_tail, one per (set, trait group), between the call's own events.  Nothing of the factor is read and
 // nothing of the work buffers is touched.
 int sets_finish_panel(scilmm_factor* fac, const PanelFinishArgs& p, const char* who) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   const FinishArgs& a = p.fin;
-  FinSets sets{};
-  int32_t widest = 0;
-  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
-  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
-  for (int32_t j = 0; j < a.n_rho; ++j) sets.grid.rho[j] = a.rho[j];
-  const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
-  const int64_t ld_rec = rec_doubles(cap, a.n_rho);
-  const size_t need = (size_t)ld_rec * (size_t)a.n_sets;
-  if (D->pfin_rec_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-  TRY(grow(sym, &D->pfin_rec, &D->pfin_rec_cap, need));
+  SetLayout l;
+  TRY(set_layout(sym, a, (const void*)k_sets_spectra, &l));
+  const int64_t ld_rec = rec_doubles(l.cap, a.n_rho);
+  TRY(grow_synced(sym, D, &D->pfin_rec, &D->pfin_rec_cap, (size_t)ld_rec * (size_t)a.n_sets));
   if (D->pfin_cu == 0) {
     int cu = 0;
     HIPCHK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, D->device));
     D->pfin_cu = std::max(cu, 1);
   }
   const int32_t group = panel_tail_group(a.n_sets, p.t, D->pfin_cu);
-  const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
-  const size_t lds_tail = sizeof(double) * (size_t)ptail_lds_doubles(cap, a.n_rho, group);
-  // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
-  HIPCHK(hipFuncSetAttribute((const void*)k_sets_spectra, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
-  if (!D->pfin_ev[0])
-    for (auto& e : D->pfin_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->pfin_ev[0], s0));
-  hipLaunchKernelGGL(k_sets_spectra, dim3((unsigned)a.n_sets), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, sets,
-                     a.weight_mode, a.d_weights, a.n_rho, cap, D->pfin_rec, ld_rec, p.d_head);
-  HIPCHK(hipEventRecord(D->pfin_ev[1], s0));
-  hipLaunchKernelGGL(k_sets_panel_tail, dim3((unsigned)a.n_sets, (unsigned)((p.t + group - 1) / group)), dim3(PT_NT), lds_tail, s0, cap,
-                     a.n_rho, sets.grid, a.method, (const double*)D->pfin_rec, ld_rec, p.d_xty, p.ld_xty, p.t, p.d_tscale, group, p.d_out);
-  HIPCHK(hipEventRecord(D->pfin_ev[2], s0));
-  D->pfin_pending = true;
+  const size_t lds_tail = sizeof(double) * (size_t)ptail_lds_doubles(l.cap, a.n_rho, group);
+  hipStream_t s0 = c.s0;
+  HIPCHK(D->pfin_t.start(s0));
+  hipLaunchKernelGGL(k_sets_spectra, dim3((unsigned)a.n_sets), dim3((unsigned)l.nt), l.lds, s0, a.r, a.c, a.d_stats, a.d_gram, a.d_R, l.sets,
+                     a.weight_mode, a.d_weights, a.n_rho, l.cap, D->pfin_rec, ld_rec, p.d_head);
+  HIPCHK(D->pfin_t.mark(s0, 1));
+  hipLaunchKernelGGL(k_sets_panel_tail, dim3((unsigned)a.n_sets, (unsigned)((p.t + group - 1) / group)), dim3(PT_NT), lds_tail, s0, l.cap,
+                     a.n_rho, l.sets.grid, a.method, (const double*)D->pfin_rec, ld_rec, p.d_xty, p.ld_xty, p.t, p.d_tscale, group, p.d_out);
+  HIPCHK(D->pfin_t.close(s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -475,33 +477,20 @@ struct MasksFinishArgs {
 // between the call's own events, one workgroup per (set, annotation, cutoff), its LDS sized by the block's largest set.  Nothing of
 // the factor is read and nothing of the work buffers is touched; nothing is allocated.
 int sets_finish_masks(scilmm_factor* fac, const MasksFinishArgs& p, const char* who) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   const FinishArgs& a = p.fin;
-  FinSets sets{};
+  SetLayout l;
+  TRY(set_layout(sym, a, (const void*)k_sets_finish_masks, &l));
   FinCuts cuts{};
-  int32_t widest = 0;
-  for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
-  for (int32_t i = 0; i < a.n_sets; ++i) widest = std::max(widest, a.set_start[i + 1] - a.set_start[i]);
-  for (int32_t j = 0; j < a.n_rho; ++j) sets.grid.rho[j] = a.rho[j];
   for (int32_t j = 0; j < p.n_cut; ++j) cuts.cut[j] = p.maf_cut[j];
-  const int32_t cap = std::max(2, (widest + 1) & ~1), nt = cap > 64 ? FIN_NT_MAX : 256;
-  const size_t lds = sizeof(double) * (size_t)fin_lds_doubles(cap, nt);
-  // more than 64 KiB of dynamic LDS has to be asked for (for the widest block there can be; the call is cheap and idempotent)
-  HIPCHK(hipFuncSetAttribute((const void*)k_sets_finish_masks, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)(sizeof(double) * (size_t)fin_lds_doubles(RPMAX, FIN_NT_MAX))));
-  if (!D->mfin_ev[0])
-    for (auto& e : D->mfin_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->mfin_ev[0], s0));
-  hipLaunchKernelGGL(k_sets_finish_masks, dim3((unsigned)(a.n_sets * p.n_ann * p.n_cut)), dim3((unsigned)nt), lds, s0, a.r, a.c, a.d_stats,
-                     a.d_gram, a.d_R, a.d_u, sets, a.weight_mode, a.d_weights, a.method, a.n_rho, cap, p.d_ann, p.n_ann, cuts, p.n_cut,
+  HIPCHK(D->mfin_t.start(c.s0));
+  hipLaunchKernelGGL(k_sets_finish_masks, dim3((unsigned)(a.n_sets * p.n_ann * p.n_cut)), dim3((unsigned)l.nt), l.lds, c.s0, a.r, a.c, a.d_stats,
+                     a.d_gram, a.d_R, a.d_u, l.sets, a.weight_mode, a.d_weights, a.method, a.n_rho, l.cap, p.d_ann, p.n_ann, cuts, p.n_cut,
                      p.acat_mac, a.d_out, a.ld_out);
-  HIPCHK(hipEventRecord(D->mfin_ev[1], s0));
-  D->mfin_pending = true;
+  HIPCHK(D->mfin_t.close(c.s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -519,14 +508,15 @@ struct WideArgs {
   int32_t n_rho;
   double *d_out, *d_lam;
   const double* d_vscale = nullptr;   // the markers' variance scales (scilmm_sets_finish_wide_scaled_dev), or null: all 1
-  int32_t bp() const { return (block + 15) / 16 * 16; }
+  static int32_t bp(int32_t block) { return (block + 15) / 16 * 16; }   // a sub-block's columns in the cross store
+  int32_t bp() const { return bp(block); }
   int32_t nsub() const { return (k + block - 1) / block; }
   // before anything of the handle is read
   // the shape of a wide set's pieces, which the set saddlepoint checks as well
   static bool shape_ok(int32_t k, int32_t block, const double* d_cross, int64_t ld_cross) {
     if (k < 1 || k > WIDE_KMAX || block < 1 || block > RPMAX) return false;
     const int32_t nsub = (k + block - 1) / block;
-    const int64_t kept = (int64_t)(nsub - 1) * ((block + 15) / 16 * 16);    // the columns of the cross store
+    const int64_t kept = (int64_t)(nsub - 1) * bp(block);    // the columns of the cross store
     return kept <= WIDE_KMAX && (nsub == 1) == (d_cross == nullptr) && (nsub == 1 || ld_cross >= kept);
   }
   static bool args_ok(const scilmm_factor* fac, const WideArgs& a) {
@@ -541,28 +531,23 @@ struct WideArgs {
 // the pre-step and k - 1 steps of the reduction, two launches each, sized by k (the number of kept markers is the device's) |
 // scale, eig | tails.  Nothing of the factor is read and nothing of the work buffers is touched.
 int sets_finish_wide(scilmm_factor* fac, const WideArgs& a, const char* who) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   const int32_t k = a.k;
-  const size_t need = wide_doubles((size_t)k);
-  if (D->wide_ws_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-  TRY(grow(sym, &D->wide_ws, &D->wide_ws_cap, need));
-  if (!D->wide_ev[0])
-    for (auto& e : D->wide_ev) HIPCHK(hipEventCreate(&e));
+  TRY(grow_synced(sym, D, &D->wide_ws, &D->wide_ws_cap, wide_doubles((size_t)k)));
   const WideWs ws = wide_cut(D->wide_ws, (size_t)k);
   const WideIn in{k, a.block, a.bp(), a.q, a.d_stats, a.d_gram, a.d_cross, a.ld_cross};
   FinGrid grid{};
   for (int32_t j = 0; j < a.n_rho; ++j) grid.rho[j] = a.rho[j];
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->wide_ev[0], s0));
+  hipStream_t s0 = c.s0;
+  HIPCHK(D->wide_t.start(s0));
   hipLaunchKernelGGL(k_wide_prep, dim3(1), dim3(WIDE_PREP_NT), 0, s0, in, a.c, a.d_R, a.d_u, a.weight_mode, a.d_weights, ws, a.n_rho, a.d_out,
                      a.d_lam, a.d_vscale);
   hipLaunchKernelGGL(k_wide_form, dim3((unsigned)k), dim3(256), 0, s0, in, a.c, ws);
   hipLaunchKernelGGL(k_wide_burden, dim3(1), dim3(256), 0, s0, ws, a.d_out);
-  HIPCHK(hipEventRecord(D->wide_ev[1], s0));
+  HIPCHK(D->wide_t.mark(s0, 1));
   // step j works on the trailing matrix of order at most k - 1 - j; the last one (order 1) only stores d and e, as does "step"
   // k - 1, which has nothing behind it but the last diagonal entry
   for (int32_t j = -1; j < k; ++j) {
@@ -570,13 +555,12 @@ int sets_finish_wide(scilmm_factor* fac, const WideArgs& a, const char* who) {
     hipLaunchKernelGGL(k_wide_symv, dim3(wgs), dim3(256), 0, s0, j, ws);
     if (k - 1 - j >= 2 || j < 0) hipLaunchKernelGGL(k_wide_rank2, dim3(wgs), dim3(256), 0, s0, j, ws);
   }
-  HIPCHK(hipEventRecord(D->wide_ev[2], s0));
+  HIPCHK(D->wide_t.mark(s0, 2));
   hipLaunchKernelGGL(k_wide_scale, dim3((unsigned)(a.n_rho + 2)), dim3(256), 0, s0, k, a.n_rho, grid, ws);
   hipLaunchKernelGGL(k_wide_eig, dim3((unsigned)((k + 63) / 64), (unsigned)(a.n_rho + 2)), dim3(64), 0, s0, k, ws, a.d_lam);
-  HIPCHK(hipEventRecord(D->wide_ev[3], s0));
+  HIPCHK(D->wide_t.mark(s0, 3));
   hipLaunchKernelGGL(k_wide_tails, dim3(1), dim3(256), 0, s0, k, a.n_rho, grid, a.method, ws, a.d_out);
-  HIPCHK(hipEventRecord(D->wide_ev[4], s0));
-  D->wide_pending = true;
+  HIPCHK(D->wide_t.close(s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -603,24 +587,18 @@ struct SetSpaArgs {
 // the set's), k_sets_spa between the call's own events, one workgroup per set.  Nothing of the work buffers is touched.
 template <class Reader>
 int sets_spa(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const SetSpaArgs& a) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
-  const int32_t n = sym->S->n;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
   TRY(spa_scratch(sym, D));
   SpaSets sets{};
   for (int32_t i = 0; i <= a.n_sets; ++i) sets.start[i] = a.set_start[i];
-  if (!D->sspa_ev[0])
-    for (auto& e : D->sspa_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->sspa_ev[0], s0));
-  hipLaunchKernelGGL(k_sets_spa<Reader>, dim3((unsigned)a.n_sets), dim3(256), 0, s0, n, r, a.spa.c, rd, a.spa.d_stats, a.d_gram, a.spa.d_R,
+  HIPCHK(D->sspa_t.start(c.s0));
+  hipLaunchKernelGGL(k_sets_spa<Reader>, dim3((unsigned)a.n_sets), dim3(256), 0, c.s0, c.n, r, a.spa.c, rd, a.spa.d_stats, a.d_gram, a.spa.d_R,
                      a.spa.d_u, a.spa.d_mu, a.spa.d_C, a.spa.d_Minv, a.spa.cutoff, (const double*)a.spa.d_spa, sets, a.weight_mode,
                      a.d_weights, D->spa_scratch, a.d_bspa, a.d_vscale);
-  HIPCHK(hipEventRecord(D->sspa_ev[1], s0));
-  D->sspa_pending = true;
+  HIPCHK(D->sspa_t.close(c.s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -644,20 +622,14 @@ struct CollapseArgs {
 
 template <class Reader>
 int sets_collapse(scilmm_factor* fac, const char* who, int32_t r, Reader rd, const CollapseArgs& a) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
-  const int32_t n = sym->S->n;
-  if (!D->coll_ev[0])
-    for (auto& e : D->coll_ev) HIPCHK(hipEventCreate(&e));
-  hipStream_t s0 = D->stream;
-  const unsigned wgs = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)n + 255) / 256, COLLAPSE_GRID));
-  HIPCHK(hipEventRecord(D->coll_ev[0], s0));
-  hipLaunchKernelGGL(k_sets_collapse<Reader>, dim3(wgs), dim3(256), 0, s0, n, r, rd, a.d_stats, a.weight_mode, a.d_weights, a.first, a.d_gB);
-  HIPCHK(hipEventRecord(D->coll_ev[1], s0));
-  D->coll_pending = true;
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
+  const unsigned wgs = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)c.n + 255) / 256, COLLAPSE_GRID));
+  HIPCHK(D->coll_t.start(c.s0));
+  hipLaunchKernelGGL(k_sets_collapse<Reader>, dim3(wgs), dim3(256), 0, c.s0, c.n, r, rd, a.d_stats, a.weight_mode, a.d_weights, a.first, a.d_gB);
+  HIPCHK(D->coll_t.close(c.s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }
@@ -690,29 +662,23 @@ struct SpaWideArgs {
 // space by the wide finish's growth rule (the finish that follows for the same k allocates nothing), then keep, markers, pairs | burden
 // between the call's own events.  No genotype is read: the collapsed row is the caller's.
 int sets_spa_wide(scilmm_factor* fac, const SpaWideArgs& a, const char* who) {
-  scilmm_symbolic* sym = fac->sym;
-  const DevGuard guard(sym);
-  TRY(check_half(fac, who));
-  TRY(settle(fac, who));
-  Dev* D = (Dev*)sym->device;
-  const int32_t k = a.k, n = sym->S->n;
-  const size_t need = wide_doubles((size_t)k);
-  if (D->wide_ws_cap < need) HIPCHK(hipStreamSynchronize(D->stream));
-  TRY(grow(sym, &D->wide_ws, &D->wide_ws_cap, need));
-  if (!D->swide_ev[0])
-    for (auto& e : D->swide_ev) HIPCHK(hipEventCreate(&e));
+  PostCall c(fac);
+  TRY(c.begin(who));
+  scilmm_symbolic* sym = c.sym;
+  Dev* D = c.D;
+  const int32_t k = a.k;
+  TRY(grow_synced(sym, D, &D->wide_ws, &D->wide_ws_cap, wide_doubles((size_t)k)));
   const SwideWs ws = swide_cut(D->wide_ws, (size_t)k);
-  const WideIn in{k, a.block, (a.block + 15) / 16 * 16, a.q, a.d_stats, a.d_gram, a.d_cross, a.ld_cross};
-  hipStream_t s0 = D->stream;
-  HIPCHK(hipEventRecord(D->swide_ev[0], s0));
+  const WideIn in{k, a.block, WideArgs::bp(a.block), a.q, a.d_stats, a.d_gram, a.d_cross, a.ld_cross};
+  hipStream_t s0 = c.s0;
+  HIPCHK(D->swide_t.start(s0));
   hipLaunchKernelGGL(k_swide_keep, dim3(1), dim3(WIDE_PREP_NT), 0, s0, in, ws);
   hipLaunchKernelGGL(k_swide_markers, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, s0, in, a.c, a.d_R, a.d_u, a.d_spa, a.weight_mode,
                      a.d_weights, ws);
   hipLaunchKernelGGL(k_swide_pairs, dim3((unsigned)k), dim3(256), 0, s0, in, a.c, ws);
-  HIPCHK(hipEventRecord(D->swide_ev[1], s0));
-  hipLaunchKernelGGL(k_swide_burden, dim3(1), dim3(256), 0, s0, in, n, a.c, a.d_mu, a.d_C, a.d_Minv, a.cutoff, ws, a.d_gB, a.d_bspa, a.d_vscale);
-  HIPCHK(hipEventRecord(D->swide_ev[2], s0));
-  D->swide_pending = true;
+  HIPCHK(D->swide_t.mark(s0, 1));
+  hipLaunchKernelGGL(k_swide_burden, dim3(1), dim3(256), 0, s0, in, c.n, a.c, a.d_mu, a.d_C, a.d_Minv, a.cutoff, ws, a.d_gB, a.d_bspa, a.d_vscale);
+  HIPCHK(D->swide_t.close(s0));
   HIPCHK(hipGetLastError());
   return SCILMM_OK;
 }

@@ -136,6 +136,49 @@ inline Tuning read_tuning() {
 // SCILMM_VERBOSE only prints (the [scilmm plan] lines); it is not gated by SCILMM_TUNING.
 inline bool verbose() { return getenv("SCILMM_VERBOSE") != nullptr; }
 
+// The HIP-event timer of one call family behind a block (Dev holds one per family): n intervals between n + 1 events on the
+// call's stream, plus `extra` marks that belong to no interval (the scan block's gxe marks).  A call does start, mark .., close;
+// scilmm_sync reads whatever is pending, and ms keeps the last read call's figures until a later call of the family has been
+// read.  The events are created by the family's first call on the handle.
+struct StageTimer {
+  static constexpr int MAX_EVENTS = 6;
+  const int n, extra;
+  hipEvent_t ev[MAX_EVENTS] = {};
+  bool pending = false;                 // a call whose events have not been read yet
+  double ms[MAX_EVENTS - 1] = {};
+  explicit StageTimer(int intervals, int extra_marks = 0) : n(intervals), extra(extra_marks) {}
+  hipError_t mark(hipStream_t s, int i) { return hipEventRecord(ev[i], s); }
+  hipError_t start(hipStream_t s) {
+    if (!ev[0])
+      for (int i = 0; i <= n + extra; ++i)
+        if (const hipError_t e = hipEventCreate(&ev[i]); e != hipSuccess) return e;
+    return mark(s, 0);
+  }
+  hipError_t close(hipStream_t s) {
+    const hipError_t e = mark(s, n);
+    pending = pending || e == hipSuccess;
+    return e;
+  }
+  // the time from mark a to mark b of a call that has finished
+  hipError_t between(int a, int b, double* out) const {
+    float t = 0;
+    const hipError_t e = hipEventElapsedTime(&t, ev[a], ev[b]);
+    if (e == hipSuccess) *out = t;
+    return e;
+  }
+  hipError_t read() {
+    if (!pending) return hipSuccess;
+    pending = false;
+    for (int i = 0; i < n; ++i)
+      if (const hipError_t e = between(i, i + 1, &ms[i]); e != hipSuccess) return e;
+    return hipSuccess;
+  }
+  void destroy() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct Dev {
   int device = 0;                  // HIP device the handle was created on; every entry point runs on it (DevGuard)
   hipStream_t stream = nullptr;
@@ -319,55 +362,43 @@ struct Dev {
   double* gram_partial = nullptr;       // [slices of GRAM_SLICE rows][GRAM_TILES][256]: partial tiles of X^T X (the first Gram block allocates it)
   size_t gram_partial_cap = 0;          // doubles
   const int32_t* d_iperm = nullptr;
-  hipEvent_t scan_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // block begin | W ready | forward sweep done | statistics done
-  bool scan_pending = false;            // a scan block whose events have not been read yet (scilmm_sync)
-  double scan_ms[3] = {0.0, 0.0, 0.0};  // the last block's moments + dequantise | forward sweep | statistics (scilmm_scan_timing)
-  hipEvent_t gxe_ev[2] = {nullptr, nullptr};  // a gxe block's: the form's fill done | k_scan_fold done (the first gxe block creates them)
+  StageTimer scan_t{3, 2};              // block begin | W ready | forward sweep done | statistics done: the last block's moments + dequantise |
+                                        // forward sweep | statistics (scilmm_scan_timing); marks 4, 5: a gxe block's fill done | k_scan_fold done
   bool gxe_pending = false;             // the pending scan block is a gxe block
-  double gxe_ms[2] = {0.0, 0.0};        // the last block's k_scan_expand | k_scan_cross + its fold; 0 after a plain block (scilmm_gxe_timing)
+  double gxe_ms[2] = {0.0, 0.0};        // the last block's k_scan_expand (mark 4 to 1) | k_scan_cross + its fold (mark 5 to 3); 0 after a plain
+                                        // block (scilmm_gxe_timing)
   // phenotype panels (scilmm_scan_panel_dev): X^T Y for the forward solution the last scan block left in X
   int32_t block_r = 0, block_rp = 0;    // X holds a block of block_r columns padded to block_rp (BlockCall::finish); 0: it does not --
                                         // whatever may overwrite the work buffers or replaces the factor clears the record (clear_block)
   double* panel_partial = nullptr;      // [slices of PANEL_SLICE rows][column panels][tiles][256]: partial tiles of X^T Y
   size_t panel_partial_cap = 0;         // doubles (grown for a wider panel only)
-  hipEvent_t panel_ev[3] = {nullptr, nullptr, nullptr};  // panel begin | k_scan_panel done | k_panel_fold done (the first panel call creates them)
-  bool panel_pending = false;           // a panel call whose events have not been read yet (scilmm_sync)
-  double panel_ms[2] = {0.0, 0.0};      // the last call's k_scan_panel | k_panel_fold (scilmm_panel_timing)
+  StageTimer panel_t{2};                // the last call's k_scan_panel | k_panel_fold (scilmm_panel_timing)
   // saddlepoint score scan (scilmm_scan_spa*_dev): the covariate-adjusted marker rows of one block
   double* spa_scratch = nullptr;        // [RPMAX][n] (the first SPA call on the handle allocates it; never reallocated)
   size_t spa_scratch_cap = 0;           // doubles
-  hipEvent_t spa_ev[2] = {nullptr, nullptr};  // k_scan_spa begin | done (the first SPA call creates them)
-  bool spa_pending = false;             // an SPA call whose events have not been read yet (scilmm_sync)
-  double spa_ms = 0.0;                  // the last call's k_scan_spa (scilmm_spa_timing)
-  hipEvent_t fin_ev[2] = {nullptr, nullptr};  // k_sets_finish begin | done (the first finish call creates them)
-  bool fin_pending = false;             // a finish call whose events have not been read yet (scilmm_sync)
-  double fin_ms = 0.0;                  // the last call's k_sets_finish (scilmm_sets_finish_timing)
+  StageTimer spa_t{1};                  // the last call's k_scan_spa (scilmm_spa_timing)
+  StageTimer fin_t{1};                  // the last call's k_sets_finish (scilmm_sets_finish_timing)
   // the finish of a block's sets against a phenotype panel (scilmm_sets_finish_panel_dev): a record per set (setpanel.hip.h)
   double* pfin_rec = nullptr;           // grown for more or wider sets behind a stream synchronise; nothing is allocated afterwards
   size_t pfin_rec_cap = 0;              // doubles
   int pfin_cu = 0;                      // compute units of the device (the first panel finish asks), for the tail's grid
-  hipEvent_t pfin_ev[3] = {nullptr, nullptr, nullptr};  // begin | k_sets_spectra done | k_sets_panel_tail done
-  bool pfin_pending = false;            // a panel finish whose events have not been read yet (scilmm_sync)
-  double pfin_ms[2] = {0.0, 0.0};       // the last call's k_sets_spectra | k_sets_panel_tail (scilmm_sets_finish_panel_timing)
-  hipEvent_t mfin_ev[2] = {nullptr, nullptr};  // k_sets_finish_masks begin | done (the first masks finish creates them)
-  bool mfin_pending = false;            // a masks finish whose events have not been read yet (scilmm_sync)
-  double mfin_ms = 0.0;                 // the last call's k_sets_finish_masks (scilmm_sets_finish_masks_timing)
-  hipEvent_t sspa_ev[2] = {nullptr, nullptr};  // k_sets_spa begin | done (the first set SPA call creates them)
-  bool sspa_pending = false;            // a set SPA call whose events have not been read yet (scilmm_sync)
-  double sspa_ms = 0.0;                 // the last call's k_sets_spa (scilmm_sets_spa_timing)
+  StageTimer pfin_t{2};                 // the last call's k_sets_spectra | k_sets_panel_tail (scilmm_sets_finish_panel_timing)
+  StageTimer mfin_t{1};                 // the last call's k_sets_finish_masks (scilmm_sets_finish_masks_timing)
+  StageTimer sspa_t{1};                 // the last call's k_sets_spa (scilmm_sets_spa_timing)
   // the finish of a wide set (scilmm_sets_finish_wide_dev): the m x m matrix, the vectors and the spectra (WideWs, setwide.hip.h)
   double* wide_ws = nullptr;            // grown for the widest set seen, behind a stream synchronise; nothing is allocated afterwards
   size_t wide_ws_cap = 0;               // doubles
-  hipEvent_t wide_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // begin | A formed | reduced | spectra | tails done
-  bool wide_pending = false;            // a wide finish whose events have not been read yet (scilmm_sync)
-  double wide_ms[4] = {0.0, 0.0, 0.0, 0.0};  // the last call's prep + form | reduction | eigenvalues | tails (scilmm_sets_finish_wide_timing)
+  StageTimer wide_t{4};                 // the last call's prep + form | reduction | eigenvalues | tails (scilmm_sets_finish_wide_timing)
   // the set saddlepoint of a wide set (scilmm_sets_collapse*_dev, scilmm_sets_spa_wide_dev): it cuts wide_ws its own way (SwideWs)
-  hipEvent_t coll_ev[2] = {nullptr, nullptr};           // k_sets_collapse begin | done (the first collapse creates them)
-  hipEvent_t swide_ev[3] = {nullptr, nullptr, nullptr};  // begin | markers + pairs done | k_swide_burden done
-  bool coll_pending = false, swide_pending = false;     // calls whose events have not been read yet (scilmm_sync)
-  double swide_ms[3] = {0.0, 0.0, 0.0};  // the last collapse | the last call's markers + pairs | its burden kernel (scilmm_sets_spa_wide_timing)
+  StageTimer coll_t{1};                 // the last k_sets_collapse: element 0 of scilmm_sets_spa_wide_timing
+  StageTimer swide_t{2};                // the last call's markers + pairs | its burden kernel: elements 1 and 2
   void clear_block() { block_r = block_rp = 0; }
+  // every stage timer, in the order scilmm_sync reads them (dev_free destroys them): a new call family adds its member here
+  static constexpr int N_TIMERS = 10;
+  static StageTimer Dev::*const TIMERS[N_TIMERS];
 };
+inline StageTimer Dev::*const Dev::TIMERS[Dev::N_TIMERS] = {&Dev::scan_t, &Dev::panel_t, &Dev::spa_t,  &Dev::fin_t,  &Dev::mfin_t,
+                                                            &Dev::pfin_t, &Dev::wide_t,  &Dev::sspa_t, &Dev::coll_t, &Dev::swide_t};
 
 #define HIPCHK(call)                                                                                   \
   do {                                                                                                 \

@@ -3,13 +3,18 @@
 //   launch.hip.h     the typed launchers (FactorLaunch, SweepLaunch, the selected inverse's);
 //   factorize.hip.h  Factorization / run_factorize, finish_factorize, ProfRead, settle, the factor's storage;
 //   sweep.hip.h      Sweep / run_rhs (solve, L*R, half-solves), host_rhs, finish_rhs_timing;
-//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), scan_panel, scan_spa, sets_finish, sets_finish_panel, sets_finish_masks, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide, rel_block, rows_block;
+//   blocks.hip.h     BlockCall, marker_block and the fills of its input forms (int8, .bed, dosage), rel_block, rows_block; PostCall, the
+//                    frame of the calls behind a block (scan_panel, scan_keep, scan_spa, sets_finish, sets_finish_panel,
+//                    sets_finish_masks, sets_finish_wide, sets_spa, sets_collapse, sets_spa_wide), grow_synced, set_layout;
 //   products.hip.h   run_quad, run_spmm and their host forms, the HE moments, fold_blocks;
 //   values.hip.h     the A_k values on the device: upload, download, IBD and dominance values;
 //   sinv.hip.h       the selected inverse and its traces.
 // The device state they run on (struct Dev, dev.h) is built once per handle by plan.hip.  Everything runs on one HIP stream
 // per symbolic handle; host entry points synchronise only where they hand data back to the caller.  An entry point is its
-// argument checks (before anything is dereferenced), a DevGuard (a block call's sits in its BlockCall) and one call.
+// argument checks (before anything is dereferenced), a DevGuard (a block call's sits in its BlockCall or PostCall) and one
+// call.  The three marker input forms (Int8Form, BedForm, DosageForm, below) state their checks, fill and reader once for the
+// four call families that read markers.  Every call family behind a block times itself with a StageTimer of the device state
+// (dev.h): scilmm_sync reads them in one loop, dev_free destroys them in one, and the timing getters are timing_out and a line each.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,6 +76,93 @@ struct scilmm_factor {
 #include "products.hip.h"
 #include "values.hip.h"
 #include "sinv.hip.h"
+
+namespace {
+
+// The three input forms of a block of markers: int8 rows, packed PLINK rows, dosage rows of uint16 or float.  Each holds the
+// form's arguments; ok(fac, rest) applies the form's checks around the caller's -- what needs no handle, then `rest` (the call
+// family's args_ok, which looks at the handle last), then what needs n: with any argument wrong that needs no handle, nothing
+// of the handle is read --; fill and reader hand the form's fill (blocks.hip.h) or its row reader (spa.hip.h) to `f`, the
+// dosage form whichever of its two element types dtype names.
+struct Int8Form {
+  const int8_t* d_geno;
+  int64_t ld;
+  template <class Rest>
+  bool ok(const scilmm_factor* fac, Rest rest) const { return d_geno && rest() && ld >= fac->sym->S->n; }
+  template <class F>
+  int fill(int32_t r, double* d_stats, F f) const { return f(fill_int8(d_geno, ld, r, d_stats)); }
+  template <class F>
+  int reader(F f) const { return f(SpaInt8{d_geno, ld}); }
+};
+
+struct BedForm {
+  const uint8_t* d_bed;
+  int64_t ld;
+  int32_t n_samples;
+  const int32_t* d_sample;
+  int32_t flags;
+  template <class Rest>
+  bool ok(const scilmm_factor* fac, Rest rest) const {
+    return d_bed && n_samples >= 1 && ld >= ((int64_t)n_samples + 3) / 4 && !(flags & ~BED_A2) && rest() &&
+           (d_sample || n_samples == fac->sym->S->n);
+  }
+  template <class F>
+  int fill(int32_t r, double* d_stats, F f) const { return f(fill_bed(d_bed, ld, n_samples, d_sample, flags, r, d_stats)); }
+  template <class F>
+  int reader(F f) const { return f(SpaBed{d_bed, ld, n_samples, d_sample, flags}); }
+};
+
+struct DosageForm {
+  const void* d_dos;
+  int32_t dtype;
+  int64_t ld;
+  int32_t n_samples;
+  const int32_t* d_sample;
+  bool u16() const { return dtype == SCILMM_DOSAGE_U16; }
+  template <class Rest>
+  bool ok(const scilmm_factor* fac, Rest rest) const {
+    return d_dos && (u16() || dtype == SCILMM_DOSAGE_F32) && (uintptr_t)d_dos % (u16() ? sizeof(uint16_t) : sizeof(float)) == 0 &&
+           n_samples >= 1 && ld >= n_samples && rest() && (d_sample || n_samples == fac->sym->S->n);
+  }
+  // (a step per element type: instantiated behind the int8 and .bed blocks, the kernels keep their order in the code object)
+  template <class T, class F>
+  int fill_as(int32_t r, double* d_stats, F f) const { return f(fill_dosage<T>(d_dos, ld, n_samples, d_sample, r, d_stats)); }
+  template <class F>
+  int fill(int32_t r, double* d_stats, F f) const { return u16() ? fill_as<uint16_t>(r, d_stats, f) : fill_as<float>(r, d_stats, f); }
+  template <class F>
+  int reader(F f) const {
+    return u16() ? f(SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}) : f(SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample});
+  }
+};
+
+// The four call families that read markers, each for any form: the form's checks around the family's own, one call.  scan_block: `gram`: the entry point (`who`) hands X^T X back as well, to d_gram (null from the others);
+// `d_E`, `m`: the gxe entry points' environment columns, which they have checked with r (null from the others).
+template <class Form>
+int scan_block(scilmm_factor* fac, const Form& g, int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram,
+               const char* who, const double* d_E = nullptr, int32_t m = 0) {
+  if ((gram && !d_gram) || !g.ok(fac, [&] { return BlockCall::args_ok(fac, r, d_Q, q, d_stats); })) return SCILMM_ERR_ARG;
+  return g.fill(r, d_stats, [&](auto fill) { return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill, d_E, m); });
+}
+
+template <class Form>
+int spa_call(scilmm_factor* fac, const Form& g, int32_t r, const SpaArgs& a, const char* who) {
+  if (!g.ok(fac, [&] { return SpaArgs::args_ok(fac, r, a); })) return SCILMM_ERR_ARG;
+  return g.reader([&](auto rd) { return scan_spa(fac, who, r, rd, a); });
+}
+
+template <class Form>
+int sets_spa_call(scilmm_factor* fac, const Form& g, int32_t r, const SetSpaArgs& a, const char* who) {
+  if (!g.ok(fac, [&] { return SetSpaArgs::args_ok(fac, r, a); })) return SCILMM_ERR_ARG;
+  return g.reader([&](auto rd) { return sets_spa(fac, who, r, rd, a); });
+}
+
+template <class Form>
+int collapse_call(scilmm_factor* fac, const Form& g, int32_t r, const CollapseArgs& a, const char* who) {
+  if (!g.ok(fac, [&] { return CollapseArgs::args_ok(fac, r, a); })) return SCILMM_ERR_ARG;
+  return g.reader([&](auto rd) { return sets_collapse(fac, who, r, rd, a); });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -234,83 +326,54 @@ int scilmm_solve_Lt_dev(scilmm_factor* fac, const double* dB, int32_t r, double*
   return rhs_entry(fac, dB, r, dX, RHS_SOLVE_LT, false, "scilmm_solve_Lt_dev");
 }
 
-// The marker scan's blocks, one checker per input form; `gram`: the entry point (`who`) hands X^T X back as well, to d_gram
-// (null from the others); `d_E`, `m`: the gxe entry points' environment columns, which they have checked with r (null from the
-// others).  What needs no handle is checked first: with it wrong, nothing of the handle is read.
-static int scan_block(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q, double* d_stats,
-                      bool gram, double* d_gram, const char* who, const double* d_E = nullptr, int32_t m = 0) {
-  if (!d_geno || (gram && !d_gram) || !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_int8(d_geno, ld_geno, r, d_stats), d_E, m);
-}
-
-static int scan_block_bed(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample, int32_t flags,
-                          int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who,
-                          const double* d_E = nullptr, int32_t m = 0) {
-  if (!d_bed || (gram && !d_gram) || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) ||
-      !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_bed(d_bed, ld_bed, n_samples, d_sample, flags, r, d_stats), d_E, m);
-}
-
-static int scan_block_dosage(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples, const int32_t* d_sample,
-                             int32_t r, const double* d_Q, int32_t q, double* d_stats, bool gram, double* d_gram, const char* who,
-                             const double* d_E = nullptr, int32_t m = 0) {
-  if (!d_dos || (gram && !d_gram) || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
-      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
-      !BlockCall::args_ok(fac, r, d_Q, q, d_stats) || (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return dtype == SCILMM_DOSAGE_U16
-             ? marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<uint16_t>(d_dos, ld, n_samples, d_sample, r, d_stats), d_E, m)
-             : marker_block(fac, who, r, d_Q, q, d_stats, d_gram, fill_dosage<float>(d_dos, ld, n_samples, d_sample, r, d_stats), d_E, m);
-}
-
+// The marker scan's blocks: a form of the markers (above the entry points), the family's call
 int scilmm_scan_block_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
                           double* d_stats) {
-  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, false, nullptr, __func__);
+  return scan_block(fac, Int8Form{d_geno, ld_geno}, r, d_Q, q, d_stats, false, nullptr, __func__);
 }
 
 int scilmm_scan_block_gram_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_Q, int32_t q,
                                double* d_stats, double* d_gram) {
-  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, true, d_gram, __func__);
+  return scan_block(fac, Int8Form{d_geno, ld_geno}, r, d_Q, q, d_stats, true, d_gram, __func__);
 }
 
 int scilmm_scan_block_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                               int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
-  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, false, nullptr, __func__);
+  return scan_block(fac, BedForm{d_bed, ld_bed, n_samples, d_sample, flags}, r, d_Q, q, d_stats, false, nullptr, __func__);
 }
 
 int scilmm_scan_block_bed_gram_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                                    int32_t flags, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
-  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, true, d_gram, __func__);
+  return scan_block(fac, BedForm{d_bed, ld_bed, n_samples, d_sample, flags}, r, d_Q, q, d_stats, true, d_gram, __func__);
 }
 
 int scilmm_scan_block_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                  const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats) {
-  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, __func__);
+  return scan_block(fac, DosageForm{d_dos, dtype, ld, n_samples, d_sample}, r, d_Q, q, d_stats, false, nullptr, __func__);
 }
 
 int scilmm_scan_block_dosage_gram_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                       const int32_t* d_sample, int32_t r, const double* d_Q, int32_t q, double* d_stats, double* d_gram) {
-  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, true, d_gram, __func__);
+  return scan_block(fac, DosageForm{d_dos, dtype, ld, n_samples, d_sample}, r, d_Q, q, d_stats, true, d_gram, __func__);
 }
 
 int scilmm_scan_block_gxe_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_E, int32_t m,
                               const double* d_Q, int32_t q, double* d_stats) {
   if (!Gxe::args_ok(d_E, m, r)) return SCILMM_ERR_ARG;
-  return scan_block(fac, d_geno, ld_geno, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
+  return scan_block(fac, Int8Form{d_geno, ld_geno}, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
 }
 
 int scilmm_scan_block_bed_gxe_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                                   int32_t flags, int32_t r, const double* d_E, int32_t m, const double* d_Q, int32_t q, double* d_stats) {
   if (!Gxe::args_ok(d_E, m, r)) return SCILMM_ERR_ARG;
-  return scan_block_bed(fac, d_bed, ld_bed, n_samples, d_sample, flags, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
+  return scan_block(fac, BedForm{d_bed, ld_bed, n_samples, d_sample, flags}, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
 }
 
 int scilmm_scan_block_dosage_gxe_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                      const int32_t* d_sample, int32_t r, const double* d_E, int32_t m, const double* d_Q, int32_t q,
                                      double* d_stats) {
   if (!Gxe::args_ok(d_E, m, r)) return SCILMM_ERR_ARG;
-  return scan_block_dosage(fac, d_dos, dtype, ld, n_samples, d_sample, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
+  return scan_block(fac, DosageForm{d_dos, dtype, ld, n_samples, d_sample}, r, d_Q, q, d_stats, false, nullptr, __func__, d_E, m);
 }
 
 // X^T Y for the block the last scan block left behind and a resident phenotype panel: what needs no handle is checked first
@@ -334,30 +397,21 @@ int scilmm_scan_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_gen
                         const double* d_u, const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff,
                         double* d_spa) {
   const SpaArgs a{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa};
-  if (!d_geno || !SpaArgs::args_ok(fac, r, a) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  return scan_spa(fac, __func__, r, SpaInt8{d_geno, ld_geno}, a);
+  return spa_call(fac, Int8Form{d_geno, ld_geno}, r, a, __func__);
 }
 
 int scilmm_scan_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                             int32_t flags, int32_t r, const double* d_stats, const double* d_R, const double* d_u, const double* d_mu,
                             const double* d_C, int32_t c, const double* d_Minv, double cutoff, double* d_spa) {
   const SpaArgs a{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa};
-  if (!d_bed || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) || !SpaArgs::args_ok(fac, r, a) ||
-      (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return scan_spa(fac, __func__, r, SpaBed{d_bed, ld_bed, n_samples, d_sample, flags}, a);
+  return spa_call(fac, BedForm{d_bed, ld_bed, n_samples, d_sample, flags}, r, a, __func__);
 }
 
 int scilmm_scan_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                const int32_t* d_sample, int32_t r, const double* d_stats, const double* d_R, const double* d_u,
                                const double* d_mu, const double* d_C, int32_t c, const double* d_Minv, double cutoff, double* d_spa) {
   const SpaArgs a{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, d_spa};
-  if (!d_dos || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
-      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
-      !SpaArgs::args_ok(fac, r, a) || (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return dtype == SCILMM_DOSAGE_U16 ? scan_spa(fac, __func__, r, SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}, a)
-                                    : scan_spa(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
+  return spa_call(fac, DosageForm{d_dos, dtype, ld, n_samples, d_sample}, r, a, __func__);
 }
 
 // The variant-set finish behind a Gram block: a pure function of what the block left behind
@@ -431,30 +485,21 @@ int scilmm_sets_finish_wide_scaled_dev(scilmm_factor* fac, int32_t k, int32_t bl
 int scilmm_sets_collapse_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_geno, int32_t r, const double* d_stats,
                              int32_t weight_mode, const double* d_weights, int32_t first, double* d_gB) {
   const CollapseArgs a{d_stats, weight_mode, d_weights, first, d_gB};
-  if (!d_geno || !CollapseArgs::args_ok(fac, r, a) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  return sets_collapse(fac, __func__, r, SpaInt8{d_geno, ld_geno}, a);
+  return collapse_call(fac, Int8Form{d_geno, ld_geno}, r, a, __func__);
 }
 
 int scilmm_sets_collapse_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
                                  int32_t flags, int32_t r, const double* d_stats, int32_t weight_mode, const double* d_weights,
                                  int32_t first, double* d_gB) {
   const CollapseArgs a{d_stats, weight_mode, d_weights, first, d_gB};
-  if (!d_bed || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) || !CollapseArgs::args_ok(fac, r, a) ||
-      (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return sets_collapse(fac, __func__, r, SpaBed{d_bed, ld_bed, n_samples, d_sample, flags}, a);
+  return collapse_call(fac, BedForm{d_bed, ld_bed, n_samples, d_sample, flags}, r, a, __func__);
 }
 
 int scilmm_sets_collapse_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
                                     const int32_t* d_sample, int32_t r, const double* d_stats, int32_t weight_mode,
                                     const double* d_weights, int32_t first, double* d_gB) {
   const CollapseArgs a{d_stats, weight_mode, d_weights, first, d_gB};
-  if (!d_dos || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
-      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
-      !CollapseArgs::args_ok(fac, r, a) || (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return dtype == SCILMM_DOSAGE_U16 ? sets_collapse(fac, __func__, r, SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}, a)
-                                    : sets_collapse(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
+  return collapse_call(fac, DosageForm{d_dos, dtype, ld, n_samples, d_sample}, r, a, __func__);
 }
 
 // The variance scales and the burden saddlepoint of ONE wide set behind its last sub-block: it reads no genotypes, so there is one
@@ -476,8 +521,7 @@ int scilmm_sets_spa_dev(scilmm_factor* fac, const int8_t* d_geno, int64_t ld_gen
                         const double* d_weights, double* d_bspa, double* d_vscale) {
   const SetSpaArgs a{{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, const_cast<double*>(d_spa)}, d_gram, n_sets, set_start, weight_mode,
                      d_weights, d_bspa, d_vscale};
-  if (!d_geno || !SetSpaArgs::args_ok(fac, r, a) || ld_geno < fac->sym->S->n) return SCILMM_ERR_ARG;
-  return sets_spa(fac, __func__, r, SpaInt8{d_geno, ld_geno}, a);
+  return sets_spa_call(fac, Int8Form{d_geno, ld_geno}, r, a, __func__);
 }
 
 int scilmm_sets_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld_bed, int32_t n_samples, const int32_t* d_sample,
@@ -487,10 +531,7 @@ int scilmm_sets_spa_bed_dev(scilmm_factor* fac, const uint8_t* d_bed, int64_t ld
                             double* d_vscale) {
   const SetSpaArgs a{{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, const_cast<double*>(d_spa)}, d_gram, n_sets, set_start, weight_mode,
                      d_weights, d_bspa, d_vscale};
-  if (!d_bed || n_samples < 1 || ld_bed < ((int64_t)n_samples + 3) / 4 || (flags & ~BED_A2) || !SetSpaArgs::args_ok(fac, r, a) ||
-      (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return sets_spa(fac, __func__, r, SpaBed{d_bed, ld_bed, n_samples, d_sample, flags}, a);
+  return sets_spa_call(fac, BedForm{d_bed, ld_bed, n_samples, d_sample, flags}, r, a, __func__);
 }
 
 int scilmm_sets_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dtype, int64_t ld, int32_t n_samples,
@@ -500,12 +541,7 @@ int scilmm_sets_spa_dosage_dev(scilmm_factor* fac, const void* d_dos, int32_t dt
                                const double* d_weights, double* d_bspa, double* d_vscale) {
   const SetSpaArgs a{{d_stats, d_R, d_u, d_mu, d_C, c, d_Minv, cutoff, const_cast<double*>(d_spa)}, d_gram, n_sets, set_start, weight_mode,
                      d_weights, d_bspa, d_vscale};
-  if (!d_dos || (dtype != SCILMM_DOSAGE_U16 && dtype != SCILMM_DOSAGE_F32) ||
-      (uintptr_t)d_dos % (dtype == SCILMM_DOSAGE_U16 ? sizeof(uint16_t) : sizeof(float)) || n_samples < 1 || ld < n_samples ||
-      !SetSpaArgs::args_ok(fac, r, a) || (!d_sample && n_samples != fac->sym->S->n))
-    return SCILMM_ERR_ARG;
-  return dtype == SCILMM_DOSAGE_U16 ? sets_spa(fac, __func__, r, SpaDos<uint16_t>{(const uint16_t*)d_dos, ld, n_samples, d_sample}, a)
-                                    : sets_spa(fac, __func__, r, SpaDos<float>{(const float*)d_dos, ld, n_samples, d_sample}, a);
+  return sets_spa_call(fac, DosageForm{d_dos, dtype, ld, n_samples, d_sample}, r, a, __func__);
 }
 
 int scilmm_rel_block_dev(scilmm_factor* fac, const double* weights, const int32_t* ids, int32_t r, const double* d_Q, int32_t q,
@@ -681,86 +717,19 @@ int scilmm_sync(scilmm_symbolic* sym) {
   DevGuard guard(sym);
   Dev* D = (Dev*)sym->device;
   HIPCHK(hipStreamSynchronize(D->stream));
-  if (D->scan_pending) {
-    D->scan_pending = false;
-    float a = 0, b = 0, c = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->scan_ev[0], D->scan_ev[1]));
-    HIPCHK(hipEventElapsedTime(&b, D->scan_ev[1], D->scan_ev[2]));
-    HIPCHK(hipEventElapsedTime(&c, D->scan_ev[2], D->scan_ev[3]));
-    D->scan_ms[0] = a;
-    D->scan_ms[1] = b;
-    D->scan_ms[2] = c;
-    a = b = 0;
+  for (auto t : Dev::TIMERS) {
+    StageTimer& timer = D->*t;
+    const bool block = timer.pending && t == &Dev::scan_t;
+    HIPCHK(timer.read());
+    if (!block) continue;
+    // the one irregular reader: a gxe block's two intervals end at marks of the block itself
+    D->gxe_ms[0] = D->gxe_ms[1] = 0.0;
     if (D->gxe_pending) {
-      HIPCHK(hipEventElapsedTime(&a, D->gxe_ev[0], D->scan_ev[1]));
-      HIPCHK(hipEventElapsedTime(&b, D->gxe_ev[1], D->scan_ev[3]));
+      HIPCHK(timer.between(4, 1, &D->gxe_ms[0]));
+      HIPCHK(timer.between(5, 3, &D->gxe_ms[1]));
     }
-    D->gxe_ms[0] = a;
-    D->gxe_ms[1] = b;
     // (the queued copy behind the block's sweep has arrived)
     if (D->h_chain_err && *D->h_chain_err != 0) return report_chain_timeout(sym, D, " (scan block)");
-  }
-  if (D->panel_pending) {
-    D->panel_pending = false;
-    float a = 0, b = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->panel_ev[0], D->panel_ev[1]));
-    HIPCHK(hipEventElapsedTime(&b, D->panel_ev[1], D->panel_ev[2]));
-    D->panel_ms[0] = a;
-    D->panel_ms[1] = b;
-  }
-  if (D->spa_pending) {
-    D->spa_pending = false;
-    float a = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->spa_ev[0], D->spa_ev[1]));
-    D->spa_ms = a;
-  }
-  if (D->fin_pending) {
-    D->fin_pending = false;
-    float a = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->fin_ev[0], D->fin_ev[1]));
-    D->fin_ms = a;
-  }
-  if (D->mfin_pending) {
-    D->mfin_pending = false;
-    float a = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->mfin_ev[0], D->mfin_ev[1]));
-    D->mfin_ms = a;
-  }
-  if (D->pfin_pending) {
-    D->pfin_pending = false;
-    for (int i = 0; i < 2; ++i) {
-      float a = 0;
-      HIPCHK(hipEventElapsedTime(&a, D->pfin_ev[i], D->pfin_ev[i + 1]));
-      D->pfin_ms[i] = a;
-    }
-  }
-  if (D->wide_pending) {
-    D->wide_pending = false;
-    for (int i = 0; i < 4; ++i) {
-      float a = 0;
-      HIPCHK(hipEventElapsedTime(&a, D->wide_ev[i], D->wide_ev[i + 1]));
-      D->wide_ms[i] = a;
-    }
-  }
-  if (D->sspa_pending) {
-    D->sspa_pending = false;
-    float a = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->sspa_ev[0], D->sspa_ev[1]));
-    D->sspa_ms = a;
-  }
-  if (D->coll_pending) {
-    D->coll_pending = false;
-    float a = 0;
-    HIPCHK(hipEventElapsedTime(&a, D->coll_ev[0], D->coll_ev[1]));
-    D->swide_ms[0] = a;
-  }
-  if (D->swide_pending) {
-    D->swide_pending = false;
-    for (int i = 0; i < 2; ++i) {
-      float a = 0;
-      HIPCHK(hipEventElapsedTime(&a, D->swide_ev[i], D->swide_ev[i + 1]));
-      D->swide_ms[1 + i] = a;
-    }
   }
   if (D->rhs_pending >= 0) return finish_rhs_timing(sym, D, D->rhs_pending);
   return SCILMM_OK;
@@ -782,70 +751,46 @@ int scilmm_last_timing(const scilmm_symbolic* sym, scilmm_timing* out) {
   return SCILMM_OK;
 }
 
+// The per-family timing getters: n figures from where `src` finds them in the device state
+using TimingSrc = const double* (*)(const Dev&);
+static int timing_out(const scilmm_symbolic* sym, double* ms, int n, TimingSrc src) {
+  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
+  const double* from = src(*(const Dev*)sym->device);
+  for (int i = 0; i < n; ++i) ms[i] = from[i];
+  return SCILMM_OK;
+}
+
 int scilmm_scan_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  const Dev* D = (const Dev*)sym->device;
-  for (int i = 0; i < 3; ++i) ms[i] = D->scan_ms[i];
-  return SCILMM_OK;
+  return timing_out(sym, ms, 3, [](const Dev& D) -> const double* { return D.scan_t.ms; });
 }
-
 int scilmm_gxe_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  const Dev* D = (const Dev*)sym->device;
-  for (int i = 0; i < 2; ++i) ms[i] = D->gxe_ms[i];
-  return SCILMM_OK;
+  return timing_out(sym, ms, 2, [](const Dev& D) -> const double* { return D.gxe_ms; });
 }
-
 int scilmm_panel_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  const Dev* D = (const Dev*)sym->device;
-  for (int i = 0; i < 2; ++i) ms[i] = D->panel_ms[i];
-  return SCILMM_OK;
+  return timing_out(sym, ms, 2, [](const Dev& D) -> const double* { return D.panel_t.ms; });
 }
-
 int scilmm_spa_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  ms[0] = ((const Dev*)sym->device)->spa_ms;
-  return SCILMM_OK;
+  return timing_out(sym, ms, 1, [](const Dev& D) -> const double* { return D.spa_t.ms; });
 }
-
 int scilmm_sets_finish_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  ms[0] = ((const Dev*)sym->device)->fin_ms;
-  return SCILMM_OK;
+  return timing_out(sym, ms, 1, [](const Dev& D) -> const double* { return D.fin_t.ms; });
 }
-
 int scilmm_sets_finish_panel_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  const Dev* D = (const Dev*)sym->device;
-  for (int i = 0; i < 2; ++i) ms[i] = D->pfin_ms[i];
-  return SCILMM_OK;
+  return timing_out(sym, ms, 2, [](const Dev& D) -> const double* { return D.pfin_t.ms; });
 }
-
 int scilmm_sets_finish_masks_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  ms[0] = ((const Dev*)sym->device)->mfin_ms;
-  return SCILMM_OK;
+  return timing_out(sym, ms, 1, [](const Dev& D) -> const double* { return D.mfin_t.ms; });
 }
-
 int scilmm_sets_finish_wide_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  const Dev* D = (const Dev*)sym->device;
-  for (int i = 0; i < 4; ++i) ms[i] = D->wide_ms[i];
-  return SCILMM_OK;
+  return timing_out(sym, ms, 4, [](const Dev& D) -> const double* { return D.wide_t.ms; });
 }
-
 int scilmm_sets_spa_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  ms[0] = ((const Dev*)sym->device)->sspa_ms;
-  return SCILMM_OK;
+  return timing_out(sym, ms, 1, [](const Dev& D) -> const double* { return D.sspa_t.ms; });
 }
-
+// the last collapse, then the two intervals of the last wide set saddlepoint
 int scilmm_sets_spa_wide_timing(const scilmm_symbolic* sym, double* ms) {
-  if (!sym || !sym->device || !ms) return SCILMM_ERR_ARG;
-  const Dev* D = (const Dev*)sym->device;
-  for (int i = 0; i < 3; ++i) ms[i] = D->swide_ms[i];
-  return SCILMM_OK;
+  const int rc = timing_out(sym, ms, 1, [](const Dev& D) -> const double* { return D.coll_t.ms; });
+  return rc != SCILMM_OK ? rc : timing_out(sym, ms + 1, 2, [](const Dev& D) -> const double* { return D.swide_t.ms; });
 }
 
 int scilmm_set_front_precision(scilmm_symbolic* sym, int32_t bits) {

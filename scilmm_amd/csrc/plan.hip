@@ -37,29 +37,8 @@ void dev_free(void* p) {
   if (D->panel_partial) (void)hipFree(D->panel_partial);
   if (D->spa_scratch) (void)hipFree(D->spa_scratch);
   if (D->wide_ws) (void)hipFree(D->wide_ws);
-  for (auto& e : D->wide_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->coll_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->swide_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->spa_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->fin_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->sspa_ev)
-    if (e) (void)hipEventDestroy(e);
+  for (auto t : Dev::TIMERS) (D->*t).destroy();
   if (D->pfin_rec) (void)hipFree(D->pfin_rec);
-  for (auto& e : D->pfin_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->mfin_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->scan_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->gxe_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : D->panel_ev)
-    if (e) (void)hipEventDestroy(e);
   if (D->d_out) (void)hipFree(D->d_out);
   for (auto& e : D->ev)
     if (e) (void)hipEventDestroy(e);

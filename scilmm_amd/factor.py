@@ -252,67 +252,53 @@ class Symbolic(object):
     def quadforms_dev(self, k, dU_ptr, r, dout_ptr):
         check(lib().scilmm_quadforms_dev(self._h, k, dU_ptr, r, dout_ptr), self._h)
 
+    def _timing(self, name, count):
+        """The ``count`` intervals of ``scilmm_<name>_timing`` in ms: a float where there is one, a tuple otherwise."""
+        ms = (C.c_double * count)()
+        check(getattr(lib(), "scilmm_%s_timing" % name)(self._h, ms), self._h)
+        return float(ms[0]) if count == 1 else tuple(float(v) for v in ms)
+
     def scan_timing(self):
         """(moments + dequantise, forward sweep, statistics) of the last scan block in ms, after ``sync()``."""
-        ms = (C.c_double * 3)()
-        check(lib().scilmm_scan_timing(self._h, ms), self._h)
-        return tuple(ms)
+        return self._timing("scan", 3)
 
     def gxe_timing(self):
         """(``k_scan_expand``, ``k_scan_cross`` + its fold) of the last scan block in ms, after ``sync()``: parts of the first
         and the third interval of ``scan_timing``; zeros after a block that was no gxe block."""
-        ms = (C.c_double * 2)()
-        check(lib().scilmm_gxe_timing(self._h, ms), self._h)
-        return tuple(ms)
+        return self._timing("gxe", 2)
 
     def panel_timing(self):
         """(``k_scan_panel``, ``k_panel_fold``) of the last ``Factor.scan_panel_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 2)()
-        check(lib().scilmm_panel_timing(self._h, ms), self._h)
-        return tuple(ms)
+        return self._timing("panel", 2)
 
     def spa_timing(self):
         """``k_scan_spa`` of the last ``Factor.scan_spa*_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 1)()
-        check(lib().scilmm_spa_timing(self._h, ms), self._h)
-        return float(ms[0])
+        return self._timing("spa", 1)
 
     def sets_finish_timing(self):
         """``k_sets_finish`` of the last ``Factor.sets_finish_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 1)()
-        check(lib().scilmm_sets_finish_timing(self._h, ms), self._h)
-        return float(ms[0])
+        return self._timing("sets_finish", 1)
 
     def sets_finish_wide_timing(self):
         """(prep + form, reduction, eigenvalues, tails) of the last ``Factor.sets_finish_wide_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 4)()
-        check(lib().scilmm_sets_finish_wide_timing(self._h, ms), self._h)
-        return tuple(float(v) for v in ms)
+        return self._timing("sets_finish_wide", 4)
 
     def sets_finish_panel_timing(self):
         """(``k_sets_spectra``, ``k_sets_panel_tail``) of the last ``Factor.sets_finish_panel_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 2)()
-        check(lib().scilmm_sets_finish_panel_timing(self._h, ms), self._h)
-        return tuple(float(v) for v in ms)
+        return self._timing("sets_finish_panel", 2)
 
     def sets_finish_masks_timing(self):
         """``k_sets_finish_masks`` of the last ``Factor.sets_finish_masks_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 1)()
-        check(lib().scilmm_sets_finish_masks_timing(self._h, ms), self._h)
-        return float(ms[0])
+        return self._timing("sets_finish_masks", 1)
 
     def sets_spa_timing(self):
         """``k_sets_spa`` of the last ``Factor.sets_spa*_dev`` in ms, after ``sync()``."""
-        ms = (C.c_double * 1)()
-        check(lib().scilmm_sets_spa_timing(self._h, ms), self._h)
-        return float(ms[0])
+        return self._timing("sets_spa", 1)
 
     def sets_spa_wide_timing(self):
         """(the last ``Factor.sets_collapse*_dev``, markers + pairs and the burden kernel of the last ``Factor.sets_spa_wide_dev``)
         in ms, after ``sync()``."""
-        ms = (C.c_double * 3)()
-        check(lib().scilmm_sets_spa_wide_timing(self._h, ms), self._h)
-        return tuple(float(v) for v in ms)
+        return self._timing("sets_spa_wide", 3)
 
     def timing(self):
         t = _lib.Timing()
